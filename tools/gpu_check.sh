@@ -9,6 +9,7 @@ R="$PWD"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 STEPS=${STEPS:-5}
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the session's bench line carries the per-codec legs and CPU baselines
 run_tests() {
   [ -n "$SKIP_TESTS" ] && return 0
   timeout -k 10 1100 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread ${PYTEST_ARGS:-} \

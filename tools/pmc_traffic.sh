@@ -15,7 +15,7 @@ mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
 for c in $legs; do
   case $c in
-    *_encode) args="--codec raw --batch 1 --steps 2 --warmup 1 --legs $c --no-cpu-baseline";;
+    *_encode) args="--full --codec raw --batch 1 --steps 2 --warmup 1 --legs $c --no-cpu-baseline";;
     *) args="--codec $c --steps 2 --warmup 1 --no-extra --no-cpu-baseline";;
   esac
   for k in FETCH_SIZE WRITE_SIZE "TCC_EA0_RDREQ TCC_EA0_RDREQ_32B TCC_EA0_RDREQ_64B TCC_EA0_RDREQ_128B"; do
