@@ -56,6 +56,21 @@
 #ifndef ZIW_EST_PCT
 #define ZIW_EST_PCT 108
 #endif
+#ifndef ZIW_STEADY
+#define ZIW_STEADY 1  // 0: pass 1 always runs the edge body (A/B of the steady body)
+#endif
+#ifndef ZIW_MKFENCE
+#define ZIW_MKFENCE 1  // 0: no wave fence between a near batch's marker clear and the marker writes (a
+                       // wave's LDS stores are performed in issue order; A/B)
+#endif
+#ifndef ZIW_P2FLAT
+#define ZIW_P2FLAT 0  // 1: pass 2's step as one predicated region with a stop code instead of the
+                      // continue chain (A/B)
+#endif
+#ifndef ZIW_SUBSEL
+#define ZIW_SUBSEL 0  // 1: the subtable look-ups are unconditional second reads (index 0 when the
+                      // entry is no link) and a select, instead of a read under a branch (A/B)
+#endif
 #ifndef ZIW_DBG
 #define ZIW_DBG 0  // 1: debug counters compiled in (ZCG_FLAG_DEBUG_COUNTERS; tools/iw_stats.py cycle
                    // shares).  Out by default: their checks cost 1.4 % of the C2 launch (22.05 -> 21.74 ms)
@@ -128,12 +143,17 @@ constexpr u32 W_LCAP = 852;
 constexpr int W_DB = 8;
 constexpr u32 W_DCAP = 432;  // >= enough(30, 8, 15) = 402
 
-constexpr u32 IW_NDBG = 28;
+constexpr u32 IW_NDBG = 32;
 __device__ unsigned long long g_iw_dbg[32];
-enum { IWD_ROUNDS, IWD_BLOCKS, IWD_STAGES, IWD_GROUPS, IWD_P1_IT, IWD_P2_IT, IWD_CHAIN, IWD_SPARE7, IWD_CAPS,
+// IWD_P1_WIT / IWD_P2_WIT: outer iterations (8 steps each) the wave issued in
+// pass 1 / pass 2; with the lane sums IWD_P1_IT / IWD_P2_IT they give a pass's
+// lane efficiency, lane-steps used / (64 * 8 * outer iterations).
+// IWD_P1_STEADY: the pass-1 outer iterations that took the steady body.
+enum { IWD_ROUNDS, IWD_BLOCKS, IWD_STAGES, IWD_GROUPS, IWD_P1_IT, IWD_P2_IT, IWD_CHAIN, IWD_P1_WIT, IWD_CAPS,
        IWD_NOEOB, IWT_HDR, IWT_P1, IWT_P2, IWT_CHAIN, IWT_CLASSIFY, IWT_FAR, IWT_NEAR, IWT_PLACE,
-       IWT_COMMIT, IWT_TOTAL, IWD_FARIT, IWD_NBATCH, IWD_NPASS, IWD_NSTRAD, IWT_HTAB, IWT_REFETCH, IWT_EOB, IWT_HWALK };
-static_assert(IWT_HWALK < IW_NDBG, "debug slots");
+       IWT_COMMIT, IWT_TOTAL, IWD_FARIT, IWD_NBATCH, IWD_NPASS, IWD_NSTRAD, IWT_HTAB, IWT_REFETCH, IWT_EOB, IWT_HWALK,
+       IWD_P2_WIT, IWD_FARB, IWD_P1_STEADY, IWD_FARB2 /* far batches after a group's first */ };
+static_assert(IWD_FARB2 < IW_NDBG && IW_NDBG <= 32, "debug slots");
 
 struct IwLds {
     u32 ltab[W_LCAP];
@@ -258,35 +278,106 @@ __device__ __forceinline__ void gr_init(GRd& s, const u8* base, u32 nvec, u32 qa
     s.lo = 0;
 }
 
-// Decode one token from >= 48 valid bits: both table lookups always run, so
-// lanes holding different token kinds do not serialise.
-__device__ __forceinline__ u32 iw_decode(const IwLds& L, u64 v, u32* adv) {
-    u32 e = L.ltab[(u32)v & ((1u << W_LB) - 1)];
-    if (((e >> 24) & 15) == K_SUB)
-        e = L.ltab[(e & 0xFFFF) + (((u32)v >> W_LB) & ((1u << ((e >> 16) & 0xFF)) - 1))];
-    const u32 l = e >> 28, kind = (e >> 24) & 15, ex = (e >> 16) & 0xFF;
-    const u32 t = l + ex;
+// ---- token-ready tables ---------------------------------------------------------
+// build_table lays entries out for the serial reader (l << 28 | kind << 24 |
+// ex << 16 | value), and a token word would have to be put together from
+// those fields once per token.  After the header of a Huffman block one wave
+// pass rewrites both tables in place into a layout private to this kernel
+// (852 + 432 entries per block against 16 383 tokens), tagged like a token
+// word by bits 31:30:
+//   ltab  literal   l << 24 | byte                          (the token word)
+//         EOB / bad W_MARK | l << 24 | M_EOB / M_BAD        (the token word)
+//         length    W_MATCH | (l + ex) << 24 | (base - 3) << 16 | ex << 8 | l
+//         link      T_SUB | offset << 8 | subtable bits
+//   dtab  distance  (dl + dex) << 24 | dex << 20 | dl << 16 | (base - 1)
+//         bad       W_MARK | dl << 24 | M_BAD
+//         link      as above
+// Every reachable entry of the serial layout has exactly one image (literals
+// carry no extra bits and a value < 256, a code length is >= 1 except on a
+// link, base - 3 + extra <= 255, base - 1 < 2^15), so iw_tab_serial() gives
+// the serial entries back exactly: zlib's look-ahead (inf_lookahead) decodes
+// with these same tables in the serial layout when the output fills inside a
+// block.
+constexpr u32 T_SUB = 0xC0000000u;
+__device__ __forceinline__ u32 iw_l_wave(u32 e) {
+    const u32 l = e >> 28, kind = (e >> 24) & 15, ex = (e >> 16) & 0xFF, val = e & 0xFFFF;
+    if (kind == K_LIT) return (l << 24) | (val & 0xFF);
+    if (kind == K_EOB) return W_MARK | (l << 24) | M_EOB;
+    if (kind == K_LEN) return W_MATCH | ((l + ex) << 24) | (((val - 3) & 0xFF) << 16) | ((ex & 7) << 8) | l;
+    if (kind == K_SUB) return T_SUB | (val << 8) | (ex & 31);
+    return W_MARK | (l << 24) | M_BAD;
+}
+__device__ __forceinline__ u32 iw_l_serial(u32 x) {
+    const u32 tag = x >> 30, l = (x >> 24) & 15;
+    if (tag == 0) return mk_entry(l, K_LIT, 0, x & 0xFF);
+    if (tag == 1) return mk_entry(l, (x & 3) == M_EOB ? K_EOB : K_BAD, 0, 0);
+    if (tag == 2) return mk_entry(x & 15, K_LEN, (x >> 8) & 7, ((x >> 16) & 0xFF) + 3);
+    return mk_entry(0, K_SUB, x & 31, (x >> 8) & 0xFFFF);
+}
+__device__ __forceinline__ u32 iw_d_wave(u32 e) {
+    const u32 l = e >> 28, kind = (e >> 24) & 15, ex = (e >> 16) & 0xFF, val = e & 0xFFFF;
+    if (kind == K_DIST) return ((l + ex) << 24) | ((ex & 15) << 20) | (l << 16) | ((val - 1) & 0x7FFF);
+    if (kind == K_SUB) return T_SUB | (val << 8) | (ex & 31);
+    return W_MARK | (l << 24) | M_BAD;
+}
+__device__ __forceinline__ u32 iw_d_serial(u32 x) {
+    const u32 tag = x >> 30;
+    if (tag == 0) return mk_entry((x >> 16) & 15, K_DIST, (x >> 20) & 15, (x & 0x7FFF) + 1);
+    if (tag == 1) return mk_entry((x >> 24) & 15, K_BAD, 0, 0);
+    return mk_entry(0, K_SUB, x & 31, (x >> 8) & 0xFFFF);
+}
+// (whole tables: the words past a block's last subtable are never looked up)
+__device__ void iw_tab_wave(IwLds& L) {
+    const u32 lane = (u32)lane_id();
+    wsync();
+    for (u32 i = lane; i < W_LCAP; i += 64) L.ltab[i] = iw_l_wave(L.ltab[i]);
+    for (u32 i = lane; i < W_DCAP; i += 64) L.dtab[i] = iw_d_wave(L.dtab[i]);
+    wsync();
+}
+__device__ void iw_tab_serial(IwLds& L) {
+    const u32 lane = (u32)lane_id();
+    wsync();
+    for (u32 i = lane; i < W_LCAP; i += 64) L.ltab[i] = iw_l_serial(L.ltab[i]);
+    for (u32 i = lane; i < W_DCAP; i += 64) L.dtab[i] = iw_d_serial(L.dtab[i]);
+    wsync();
+}
+
+// Decode one token from >= 48 valid bits with the token-ready tables: both
+// table lookups always run, so lanes holding different token kinds do not
+// serialise.  The token's stream bits (the advance) are its bits field.
+// (v_bfe_u32 takes offset and width from the low 5 bits of its operands,
+// which is where the entries keep them.)
+__device__ __forceinline__ u32 iw_decode(const IwLds& L, u64 v) {
+    const u32 v0 = (u32)v;
+    u32 e = L.ltab[v0 & ((1u << W_LB) - 1)];
+#if ZIW_SUBSEL
+    {
+        const u32 e2 = L.ltab[e >= T_SUB ? ((e >> 8) & 0xFFFF) + __builtin_amdgcn_ubfe(v0, (u32)W_LB, e) : 0u];
+        e = e >= T_SUB ? e2 : e;
+    }
+#else
+    if (e >= T_SUB) e = L.ltab[((e >> 8) & 0xFFFF) + __builtin_amdgcn_ubfe(v0, (u32)W_LB, e)];
+#endif
     // 32-bit fields only: the length code and its extra bits end by bit 20,
     // and the distance code and its extra bits take <= 28 bits from t
-    const u32 vd = __builtin_amdgcn_alignbit((u32)(v >> 32), (u32)v, t);
+    const u32 t = (e >> 24) & 63;  // (a length entry: l + ex)
+    const u32 vd = __builtin_amdgcn_alignbit((u32)(v >> 32), v0, t);
     u32 de = L.dtab[vd & ((1u << W_DB) - 1)];
-    if (((de >> 24) & 15) == K_SUB)
-        de = L.dtab[(de & 0xFFFF) + ((vd >> W_DB) & ((1u << ((de >> 16) & 0xFF)) - 1))];
-    const u32 dl = de >> 28, dex = (de >> 16) & 0xFF;
-    const u32 len = (e & 0xFFFF) + (((u32)v >> l) & ((1u << ex) - 1));
-    const u32 dist = (de & 0xFFFF) + ((vd >> dl) & ((1u << dex) - 1));
-    const u32 madv = t + dl + dex;
-    const bool dok = ((de >> 24) & 15) == K_DIST;
-    u32 a = l ? l : 1;
-    u32 tk = W_MARK | (a << 24) | M_BAD;
-    if (kind == K_LIT) tk = (l << 24) | (e & 0xFF);
-    if (kind == K_EOB) tk = W_MARK | (l << 24) | M_EOB;
-    if (kind == K_LEN) {
-        a = dok ? madv : t + (dl ? dl : 1);
-        tk = dok ? (W_MATCH | (madv << 24) | ((len - 3) << 16) | (dist - 1)) : (W_MARK | (a << 24) | M_BAD);
+#if ZIW_SUBSEL
+    {
+        const u32 d2 = L.dtab[de >= T_SUB ? ((de >> 8) & 0xFFFF) + __builtin_amdgcn_ubfe(vd, (u32)W_DB, de) : 0u];
+        de = de >= T_SUB ? d2 : de;
     }
-    *adv = a;
-    return tk;
+#else
+    if (de >= T_SUB) de = L.dtab[((de >> 8) & 0xFFFF) + __builtin_amdgcn_ubfe(vd, (u32)W_DB, de)];
+#endif
+    const u32 lenx = __builtin_amdgcn_ubfe(v0, e, e >> 8);
+    const u32 distx = __builtin_amdgcn_ubfe(vd, (de >> 16) & 15, (de >> 20) & 15);
+    // the length's bits on top of the distance entry: the bad-distance marker
+    // as it stands (W_MARK | (t + dl) << 24 | M_BAD), or the match's bits field
+    const u32 c = (t << 24) + de;
+    const u32 m = (c & 0xFF00FFFFu) + (e & 0x80FF0000u) + ((lenx << 16) + distx);
+    return (e & W_MATCH) ? ((de & W_MARK) ? c : m) : e;
 }
 
 typedef __attribute__((address_space(1))) u32x4 gu32x4_a4 __attribute__((aligned(4)));
@@ -638,6 +729,9 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
                                                                &L.u.h.dh, L.dtab, L.u.h.hwin,
                                                                dbg ? &L.dbgc[IWT_HTAB] : nullptr);
         const u32 hdr_end = (u32)b.consumed;
+        if (r == R_OK && type != 0) {  // a Huffman block: the tables as the H round reads them
+            iw_tab_wave(L);
+        }
         IW_T(IWT_HDR);
         if (r != R_OK) break;
         IW_ADD(IWD_BLOCKS, 1);
@@ -698,13 +792,58 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
 #pragma unroll
             for (u32 j = 0; j < IW_MWIN; j++) L.u.hr.mwin[j][lane] = 0;
             bool run = nxt == S_NONE;
+            // flush of the staged tokens: the aligned block holding token nt0
+            // once it is complete (each block is stored once: its first words
+            // stay in the ring until then, <= 3 + IW_K < 8 entries)
+            auto flush_tokens = [&]() {
+                const u32 a0 = nt0 & ~3u, sb = a0 & 4u;
+                if (nt >= a0 + 4) {
+                    *(gu32x4_a16*)(gl + iw_ta(lane, a0)) =
+                        u32x4{L.u.hr.tst[sb][lane], L.u.hr.tst[sb + 1][lane], L.u.hr.tst[sb + 2][lane],
+                              L.u.hr.tst[sb + 3][lane]};
+                    nt0 = nt;
+                }
+            };
             while (__ballot(run) != 0) {
               const u32x4 vC = gr_vec(vbase, nvec, bs.vc), vD = gr_vec(vbase, nvec, bs.vc + 1);
+              IW_ADD(IWD_P1_WIT, 1);
+              // Once per outer step, wave-uniformly: a running lane is on the
+              // edge if its list could fill, its stream could end (8 maximal
+              // tokens of 48 bits), or its mark window is still inside the
+              // IW_MARKW words that are ever read.  With no lane on the edge
+              // the steady body runs: no cap, exhausted or mark work at all.
+              const bool edge = run && (nt + IW_K * IW_KH > IW_TCAP || q + 48 * IW_K * IW_KH > total_bits ||
+                                        w0 < IW_MARKW);
+              if (ZIW_STEADY && __ballot(edge) == 0) {
+                IW_ADD(IWD_P1_STEADY, 1);
+                for (u32 kh = 0; kh < IW_KH; kh++) {
+                    for (u32 k = 0; k < IW_K; k++) {
+                        // one predicated region per step: a lane idles when it is
+                        // done or A:B ran dry (until the absorb below)
+                        if (run && bs.bp <= 208) {
+                            gr_fill(bs);
+                            const u32 tk = iw_decode(L, bs.lo);
+                            const u32 adv = w_bits(tk);
+                            L.u.hr.tst[nt & (2 * IW_K - 1)][lane] = tk;
+                            nt++;
+                            gr_drop(bs, adv);
+                            q += adv;
+                            it1++;
+                            run = q < pend;
+                        }
+                    }
+                    flush_tokens();
+                }
+                // no marks were set and the window was not moved: it holds
+                // nothing that is stored (w0 >= IW_MARKW), so only its position
+                // follows the lane, for an edge step that may come later
+                w0 = (q - p) >> 5;
+              } else {
               for (u32 kh = 0; kh < IW_KH; kh++) {
                 for (u32 k = 0; k < IW_K; k++) {
                     if (!run || !gr_fill(bs)) continue;
-                    u32 adv;
-                    u32 tk = iw_decode(L, bs.lo, &adv);
+                    u32 tk = iw_decode(L, bs.lo);
+                    const u32 adv = w_bits(tk);
                     if (q + adv > total_bits) tk = W_MARK | M_EXH;
                     if (nt == IW_TCAP) { nxt = S_CAP; run = false; continue; }
                     L.u.hr.tst[nt & (2 * IW_K - 1)][lane] = tk;
@@ -717,19 +856,9 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
                     it1++;
                     if (q >= pend) run = false;
                 }
-                // flush: the aligned block holding token nt0 once it is complete
-                // (each block is stored once: its first words stay in the ring
-                // until then, <= 3 + IW_K < 8 entries); then the mark window
-                // (words past my position are still zero)
-                {
-                    const u32 a0 = nt0 & ~3u, sb = a0 & 4u;
-                    if (nt >= a0 + 4) {
-                        *(gu32x4_a16*)(gl + iw_ta(lane, a0)) =
-                            u32x4{L.u.hr.tst[sb][lane], L.u.hr.tst[sb + 1][lane], L.u.hr.tst[sb + 2][lane],
-                                  L.u.hr.tst[sb + 3][lane]};
-                        nt0 = nt;
-                    }
-                }
+                // flush: the staged tokens, then the mark window (words past my
+                // position are still zero)
+                flush_tokens();
                 u32 mv[IW_MWIN];
 #pragma unroll
                 for (u32 j = 0; j < IW_MWIN; j++) mv[j] = L.u.hr.mwin[j][lane];
@@ -769,6 +898,7 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
                 for (u32 j = 0; j < IW_MWIN; j++) L.u.hr.mwin[j][lane] = mv[j];
                 w0 = w1;
               }
+              }
               gr_absorb(bs, vC, vD);
             }
             static_assert(IW_K == 4 && IW_MWIN == 8, "flush layout");
@@ -793,6 +923,49 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
             bool run2 = nxt == S_NONE;
             while (__ballot(run2) != 0) {
                 const u32x4 vC = gr_vec(vbase, nvec, bs.vc), vD = gr_vec(vbase, nvec, bs.vc + 1);
+                IW_ADD(IWD_P2_WIT, 1);
+#if ZIW_P2FLAT
+                // one predicated region per step: the step's outcome is a stop
+                // code (S_NONE: go on), the state follows by selects
+                for (u32 k = 0; k < IW_K * IW_KH; k++) {
+                    if (run2) {
+                        u32 stop = S_NONE;
+                        if (q >= round_hi) {
+                            stop = S_ROUND_END;
+                        } else {
+                            if (q >= pk + seg) { ks++; pk += seg; lim = ks < 64 ? L.u.hr.mlim[ks] : 0u; cwi = 0xFFFFFFFFu; }
+                            const u32 off = q - pk;
+                            if (off < lim) {
+                                const u32 wi = off >> 5;
+                                if (wi != cwi) { cwv = wi < IW_EMW ? L.u.hr.em[wi][ks] : marks[(u64)ks * IW_MWORDS + wi]; cwi = wi; }
+                                if ((cwv >> (off & 31)) & 1u) {
+                                    give = iw_rank(L, ks, marks + (u64)ks * IW_MWORDS, wi, cwv & ((1u << (off & 31)) - 1u));
+                                    stop = ks;
+                                }
+                            }
+                        }
+                        if (stop == S_NONE && bs.bp <= 208) {  // (else A:B ran dry: wait for the refill)
+                            gr_fill(bs);
+                            u32 tk = iw_decode(L, bs.lo);
+                            const u32 adv = w_bits(tk);
+                            if (q + adv > total_bits) tk = W_MARK | M_EXH;
+                            if (nt == IW_TCAP) {
+                                stop = S_CAP;
+                            } else {
+                                gl[iw_ta(lane, nt)] = tk;
+                                nt++;
+                                it2++;
+                                const bool mkr = w_marker(tk);
+                                q += tk == (W_MARK | M_EXH) ? 0u : adv;
+                                bs.bp += mkr ? 0u : adv;
+                                stop = mkr ? S_MARKER : S_NONE;
+                            }
+                        }
+                        nxt = stop;
+                        run2 = stop == S_NONE;
+                    }
+                }
+#else
                 for (u32 k = 0; k < IW_K * IW_KH; k++) {
                     if (!run2) continue;
                     if (q >= round_hi) { nxt = S_ROUND_END; run2 = false; continue; }
@@ -809,8 +982,8 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
                         }
                     }
                     if (!gr_fill(bs)) continue;  // A:B ran dry: wait for the refill
-                    u32 adv;
-                    u32 tk = iw_decode(L, bs.lo, &adv);
+                    u32 tk = iw_decode(L, bs.lo);
+                    const u32 adv = w_bits(tk);
                     if (q + adv > total_bits) tk = W_MARK | M_EXH;
                     if (nt == IW_TCAP) { nxt = S_CAP; run2 = false; continue; }
                     gl[iw_ta(lane, nt)] = tk;
@@ -825,6 +998,7 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
                     gr_drop(bs, adv);
                     q += adv;
                 }
+#endif
                 gr_absorb(bs, vC, vD);
             }
             if (dbg) {
@@ -1029,7 +1203,9 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
                     // its part's descriptor.
                     for (u32 n0 = 0; n0 < pn_NB; n0 += 64) {
                         L.u.st.mk[lane] = 0;
+#if ZIW_MKFENCE
                         wsync();
+#endif
                         if (pn_nla && pn_na < n0 + 64 && pn_na + pn_nla > n0) {
                             const u32 sl = pn_na > n0 ? pn_na - n0 : 0u;
                             L.u.st.mk[sl] = (sl << 26) | pn_dsa;
@@ -1129,6 +1305,8 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
                         };
                         // one batch of <= 64 far parts; the first one issues the prefetch
                         auto far_batch = [&](u32 f0, auto with_prefetch) {
+                            IW_ADD(IWD_FARB, 1);
+                            if (f0) IW_ADD(IWD_FARB2, 1);
                             if (fA && rkA - f0 < 64u) L.u.st.fd[rkA - f0] = fdesc(A);
                             if (fB && rkB - f0 < 64u) L.u.st.fd[rkB - f0] = fdesc(B);
                             wsync();
@@ -1293,6 +1471,11 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
         b.cbase = ~0ull;
         wsync();
         if (b.limit >= b.consumed) {
+            // the look-ahead decodes the current block's next token with the
+            // serial reader (after a stored block it starts at a header and
+            // builds its own tables)
+            // (boundary with !after_stored: the output filled inside a Huffman block)
+            if (!after_stored) iw_tab_serial(L);
             const int la = inf_lookahead<W_LB, W_LCAP, W_DB, W_DCAP>(b, last, after_stored, L.u.h.lens, &L.u.h.lh,
                                                                      L.ltab, &L.u.h.dh, L.dtab);
             if (la == R_INVALID) r = R_INVALID;
@@ -1335,9 +1518,15 @@ static u32 iw_nslot(uint32_t n) {
     return (u32)ns;
 }
 
+// the pass-1 / look-up A/B knobs show in the tag only when they differ from the product build
+#if ZIW_STEADY != 1 || ZIW_SUBSEL != 0 || ZIW_P2FLAT != 0 || ZIW_MKFENCE != 1
+#define IW_AB_TAG ",STEADY=" ZCG_STR(ZIW_STEADY) ",SUBSEL=" ZCG_STR(ZIW_SUBSEL) ",P2FLAT=" ZCG_STR(ZIW_P2FLAT) ",MKFENCE=" ZCG_STR(ZIW_MKFENCE)
+#else
+#define IW_AB_TAG ""
+#endif
 const char* cfg_inflate_wave() {
     return "inflate_wave:S=" ZCG_STR(ZIW_S) ",TCAP=" ZCG_STR(ZIW_TCAP) ",WPE=" ZCG_STR(ZIW_WPE)
-           ",EST_PCT=" ZCG_STR(ZIW_EST_PCT) ",MARKW=" ZCG_STR(ZIW_MARKW) ",G=" ZCG_STR(ZIW_G) ",DBG=" ZCG_STR(ZIW_DBG);
+           ",EST_PCT=" ZCG_STR(ZIW_EST_PCT) ",MARKW=" ZCG_STR(ZIW_MARKW) ",G=" ZCG_STR(ZIW_G) ",DBG=" ZCG_STR(ZIW_DBG) IW_AB_TAG;
 }
 
 uint64_t inflate_wave_ws_bytes(const zcg_array* a, uint32_t n) {
