@@ -259,3 +259,22 @@ extern "C" int zh_bz2_decode(const uint8_t* src, uint64_t n, uint8_t* dst, uint6
     s.lim = n;
     return zb::bz_stream(*io, s, D);
 }
+
+// ---- the encoders' host planning (zcg_encode_plan.h) ----
+#include "../../zarr_amd/csrc/zcg_encode_plan.h"
+
+// out[0..3) = m, sm, tot
+extern "C" void zh_sub_batch_plan(uint64_t D, uint32_t n, uint64_t sub_bytes, uint64_t super_bytes, uint32_t max_m,
+                                  uint64_t* out) {
+    const zcg::SubBatch b = zcg::sub_batch_plan(D, n, sub_bytes, super_bytes, max_m);
+    out[0] = b.m;
+    out[1] = b.sm;
+    out[2] = b.tot;
+}
+
+// offs[i] = take(sizes[i]) in order; returns total()
+extern "C" uint64_t zh_ws_carve(const uint64_t* sizes, uint32_t k, uint64_t* offs) {
+    zcg::WsCarve ws;
+    for (uint32_t i = 0; i < k; i++) offs[i] = ws.take(sizes[i]);
+    return ws.total();
+}

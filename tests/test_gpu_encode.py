@@ -659,8 +659,8 @@ def test_encode_short_src_is_invalid_data(codec):
 def test_encode_sub_batch_splits_roundtrip(codec):
     """1 100 distinct 1 MiB chunks: more than one 128 MiB match-finder
     sub-batch and more than one 1 GiB coder launch (the m / sm splits of
-    lz_layout / df_layout / xe_layout).  Every stream must decode with the
-    reference libraries to its own chunk."""
+    lz_layout and of sub_batch_plan in df_ws / dz_ws / xe_ws / xo_ws).  Every
+    stream must decode with the reference libraries to its own chunk."""
     import torch
     from zarr_amd.batch import BatchCodec, make_encode_batch
     D, n = 1 << 20, 1100
@@ -687,6 +687,61 @@ def test_encode_sub_batch_splits_roundtrip(codec):
     assert (st == 0).all()
     bad = [i for i in range(n) if not np.array_equal(outs[i], base[offs[i]:offs[i] + D])]
     assert not bad, bad[:10]
+
+
+_CROSS_D = (48 << 20) + 5  # 128 MiB / D = 2: every coder's match finder takes 3 chunks as 2 + 1
+_CROSS = {}
+
+
+def _cross_chunks():
+    """Three distinct windows of one seeded random walk of <i2, as bytes."""
+    if not _CROSS:
+        rng = np.random.default_rng(33)
+        offs = [0, 40010, 80020]
+        base = np.cumsum(rng.integers(-3, 4, (_CROSS_D + offs[-1]) // 2 + 1)).astype("<i2").view(np.uint8)
+        _CROSS["chunks"] = [base[o:o + _CROSS_D] for o in offs]
+    return _CROSS["chunks"]
+
+
+@pytest.mark.parametrize("setting", ["gzip6", "gzip6_segmented", "gzip0", "xz2", "xz6"])
+def test_encode_crosses_sub_batch_small(setting):
+    """The smallest batch in which every gzip and xz coder runs more than one
+    match-finder sub-batch inside one super-batch: 3 chunks of 48 MiB + 5
+    bytes, so sub_batch_plan gives m = 2 and the shared plan, carve, sort and
+    chain-link path runs for 2 chunks and then for 1.  gzip level 6 must be
+    zlib's bytes; the segmented coder (ZCG_FLAG_GZIP_SEGMENTED, and level 0)
+    and xz must decode with the reference libraries to the chunk.  The
+    byte-exact comparison (a zlib compress of 48 MiB on the CPU) is made for
+    the first chunk and for chunk 2, the one after the sub-batch boundary;
+    every chunk is decoded and compared.  (Measured: 3-4 s per case, except
+    xz2 at 25 s: the greedy xz coder is one wave per chunk, so a 48 MiB chunk
+    is 48 M serial parse steps on the GPU whatever the CPU checks.)"""
+    import torch
+    from zarr_amd import _native
+    from zarr_amd.batch import BatchCodec, make_encode_batch
+    from zarr_amd.compression import Xz
+    comp, flags = {"gzip6": (Gzip(6), 0), "gzip6_segmented": (Gzip(6), _native.FLAG_GZIP_SEGMENTED),
+                   "gzip0": (Gzip(0), 0), "xz2": (Xz(2), 0), "xz6": (Xz(6), 0)}[setting]
+    D, n = _CROSS_D, 3
+    chunks = _cross_chunks()
+    meta = ArrayMetadata.new([n * D], [D], "u1", comp)
+    bc = BatchCodec(0)
+    elems = torch.from_numpy(np.concatenate(chunks)).to("cuda:0")
+    cap = bc.encode_bound(meta, D)
+    desc, dst, out_len, status = make_encode_batch(elems, n, cap, "cuda:0")
+    bc.encode(meta, desc, n, out_len, status, flags=flags)
+    torch.cuda.synchronize()
+    assert status.cpu().numpy().tolist() == [0, 0, 0]
+    ol = out_len.cpu().numpy()
+    host = dst.view(n, cap).cpu().numpy()
+    cid = zref.XZ if setting.startswith("xz") else zref.GZIP
+    for i in range(n):
+        s = host[i, :ol[i]].tobytes()
+        content = chunks[i].tobytes()
+        rst, dec = zref.decode(cid, s, D, 1, False, False)
+        assert rst == zref.OK and dec == content, (setting, i)
+        if cid == zref.GZIP and i != 1:
+            check_gzip_member(s, content, 0 if setting == "gzip0" else 6, exact=setting == "gzip6")
 
 
 def test_lz4_encode_block_count_limit():

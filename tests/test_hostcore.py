@@ -25,6 +25,8 @@ def host():
         _H.zh_xz_decode.restype = ctypes.c_int
         _H.zh_bz2_decode.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64]
         _H.zh_bz2_decode.restype = ctypes.c_int
+        _H.zh_sub_batch_plan.restype = None
+        _H.zh_ws_carve.restype = ctypes.c_uint64
     return _H
 
 
@@ -494,3 +496,79 @@ def test_xz_sha256_core_matches_liblzma():
             b = bytearray(s)
             b[int(rng.integers(0, len(s)))] ^= 1 << int(rng.integers(0, 8))
             same(bytes(b), n)
+
+
+# ---- the encoders' host planning (zarr_amd/csrc/zcg_encode_plan.h) ----
+MIB = 1 << 20
+PLAN_CONSTS = {  # coder: (sub_bytes, super_bytes, max_m), as its launcher passes them
+    "df": (128 * MIB, 1 << 30, 256),
+    "dz": (128 * MIB, 512 * MIB, 65536),
+    "xe": (128 * MIB, 1 << 30, 4096),
+}
+
+
+def sub_batch_plan(D, n, coder):
+    sub, sup, max_m = PLAN_CONSTS[coder]
+    out = (ctypes.c_uint64 * 3)()
+    host().zh_sub_batch_plan(ctypes.c_uint64(D), ctypes.c_uint32(n), ctypes.c_uint64(sub), ctypes.c_uint64(sup),
+                             ctypes.c_uint32(max_m), out)
+    return tuple(out)
+
+
+# (D, n, coder) -> (m, sm, tot): the sizing arithmetic of the encoders before
+# they shared sub_batch_plan, evaluated by hand and with their own code
+PLAN_PINS = [
+    (MIB, 1100, "df", (128, 1024, 134217728)),
+    (MIB, 1100, "xe", (128, 1024, 134217728)),
+    (MIB, 1100, "dz", (128, 512, 134217728)),
+    (MIB, 3, "df", (3, 3, 3145728)),
+    (MIB, 3, "dz", (3, 3, 3145728)),
+    (MIB, 3, "xe", (3, 3, 3145728)),
+    (0, 5, "df", (5, 5, 0)),
+    (0, 5, "dz", (5, 5, 0)),
+    (0, 5, "xe", (5, 5, 0)),
+    (4096, 100000, "df", (256, 100000, 1048576)),
+    (4096, 100000, "xe", (4096, 100000, 16777216)),
+    (4096, 100000, "dz", (32768, 100000, 134217728)),
+    (209715200, 4, "df", (1, 4, 209715200)),
+    (209715200, 4, "xe", (1, 4, 209715200)),
+    (209715200, 4, "dz", (1, 2, 209715200)),
+    (1 << 31, 2, "df", (1, 1, 1 << 31)),
+    (300, 1000000, "df", (256, 1000000, 76800)),
+    (300, 1000000, "dz", (65536, 1000000, 19660800)),
+]
+
+
+@pytest.mark.parametrize("D,n,coder,want", PLAN_PINS)
+def test_sub_batch_plan_pinned(D, n, coder, want):
+    assert sub_batch_plan(D, n, coder) == want
+
+
+@pytest.mark.parametrize("coder", sorted(PLAN_CONSTS))
+def test_sub_batch_plan_invariants(coder):
+    rng = np.random.default_rng(11)
+    max_m = PLAN_CONSTS[coder][2]
+    for _ in range(300):
+        # chunk sizes from a few bytes to past the super-batch, counts from 1 up
+        D = int(2 ** rng.uniform(0, 32)) + int(rng.integers(0, 7))
+        n = int(2 ** rng.uniform(0, 21))
+        m, sm, tot = sub_batch_plan(D, n, coder)
+        assert 1 <= m <= min(n, max_m), (D, n, m)
+        assert m <= sm <= n, (D, n, m, sm)
+        assert tot == m * D, (D, n, m, tot)
+
+
+def test_ws_carve_regions():
+    rng = np.random.default_rng(12)
+    for _ in range(50):
+        k = int(rng.integers(1, 24))
+        sizes = [int(x) for x in rng.choice([0, 1, 255, 256, 257, 4096, 100003, (1 << 33) + 5], k)]
+        arr = (ctypes.c_uint64 * k)(*sizes)
+        offs = (ctypes.c_uint64 * k)()
+        total = host().zh_ws_carve(arr, ctypes.c_uint32(k), offs)
+        offs = list(offs)
+        assert all(o % 256 == 0 for o in offs)
+        for i in range(k - 1):  # consecutive regions do not overlap
+            assert offs[i] + sizes[i] <= offs[i + 1]
+        assert offs[-1] + sizes[-1] <= total
+        assert total == sum((s + 255) // 256 * 256 for s in sizes)

@@ -73,9 +73,9 @@ class BatchCodec:
                                           packed.n, packed.status.data_ptr(), h)
         _raise_status(r, self.ctx, "decode_batch")
 
-    def encode(self, meta: ArrayMetadata, desc, n: int, out_len, status, stream=None):
+    def encode(self, meta: ArrayMetadata, desc, n: int, out_len, status, stream=None, flags: int = 0):
         torch = _torch()
-        arr = abi_array(meta)
+        arr = abi_array(meta, flags)
         s = stream if stream is not None else torch.cuda.current_stream(self.device)
         h = s.cuda_stream if hasattr(s, "cuda_stream") else int(s)
         r = self.ctx.lib.zcg_encode_batch(self.ctx.handle, ctypes.byref(arr), desc.data_ptr(), n,

@@ -37,6 +37,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "zcg_common.h"
+#include "zcg_encode_plan.h"
 
 namespace zcg {
 namespace {
@@ -138,28 +139,27 @@ BzeLayout make_layout(u64 D, u32 L, u32 n) {
     y.nbmax = (u64)y.maxb * y.m;
     y.outmax = y.tmax * 17 / 8 + y.nbmax * (24576 + 512);
     y.cub_bytes = cub_temp_bytes(y.tmax);
-    u64 p = 0;
-    auto take = [&](u64 bytes) { const u64 o = p; p = al256(p + bytes); return o; };
-    y.off_rle = take(y.R * y.m);
-    y.off_cinfo = take(sizeof(BzeChunkInfo) * y.m);
-    y.off_lblk = take(sizeof(BzeLocalBlk) * y.nbmax);
-    y.off_blk = take(sizeof(BzeBlk) * y.nbmax);
-    y.off_cnt = take(sizeof(BzeCounters));
-    y.off_text = take(y.tmax + 16);
-    y.off_blkof = take(4 * y.tmax);
-    y.off_rank = take(4 * y.tmax);
-    y.off_sa = take(4 * y.tmax);
-    y.off_ka = take(8 * y.tmax);
-    y.off_kb = take(8 * y.tmax);
-    y.off_va = take(4 * y.tmax);
-    y.off_vb = take(4 * y.tmax);
-    y.off_u = take(4 * y.tmax);
-    y.off_sa_scan = take(4 * y.tmax);
-    y.off_sb_scan = take(4 * y.tmax);
-    y.off_flags = take(y.tmax);
-    y.off_out = take(y.outmax);
-    y.off_cub = take(y.cub_bytes);
-    y.total = p;
+    WsCarve ws;
+    y.off_rle = ws.take(y.R * y.m);
+    y.off_cinfo = ws.take(sizeof(BzeChunkInfo) * y.m);
+    y.off_lblk = ws.take(sizeof(BzeLocalBlk) * y.nbmax);
+    y.off_blk = ws.take(sizeof(BzeBlk) * y.nbmax);
+    y.off_cnt = ws.take(sizeof(BzeCounters));
+    y.off_text = ws.take(y.tmax + 16);
+    y.off_blkof = ws.take(4 * y.tmax);
+    y.off_rank = ws.take(4 * y.tmax);
+    y.off_sa = ws.take(4 * y.tmax);
+    y.off_ka = ws.take(8 * y.tmax);
+    y.off_kb = ws.take(8 * y.tmax);
+    y.off_va = ws.take(4 * y.tmax);
+    y.off_vb = ws.take(4 * y.tmax);
+    y.off_u = ws.take(4 * y.tmax);
+    y.off_sa_scan = ws.take(4 * y.tmax);
+    y.off_sb_scan = ws.take(4 * y.tmax);
+    y.off_flags = ws.take(y.tmax);
+    y.off_out = ws.take(y.outmax);
+    y.off_cub = ws.take(y.cub_bytes);
+    y.total = ws.total();
     return y;
 }
 

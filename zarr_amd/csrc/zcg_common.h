@@ -104,6 +104,18 @@ typedef __attribute__((address_space(3))) u16 lu16;
 typedef __attribute__((address_space(3))) u32 lu32;
 typedef __attribute__((address_space(1))) u32x4 gu32x4_ua __attribute__((aligned(1)));
 typedef __attribute__((address_space(1))) u32x2 gu32x2_ua __attribute__((aligned(1)));
+typedef __attribute__((address_space(1))) u32 gu32_ua __attribute__((aligned(1)));
+
+// Serialised (write_data order) bytes of a chunk in global memory: byte x, and
+// bytes x..x+3 little-endian in the result.
+__device__ __forceinline__ u32 ser1(const u8* src, u64 x, const DType& t) {
+    return norm_byte(((const gu8*)src)[swap_pos(x, t)], t);
+}
+__device__ __forceinline__ u32 ser4(const u8* src, u64 x, const DType& t) {
+    if (!t.swap && !t.isbool) return *(const gu32_ua*)((const gu8*)src + x);  // (global, not flat)
+    return ser1(src, x, t) | (ser1(src, x + 1, t) << 8) | (ser1(src, x + 2, t) << 16) | (ser1(src, x + 3, t) << 24);
+}
+
 __device__ __forceinline__ u64 ru64(u64 x) {  // wave-uniform 64-bit value -> SGPRs
     return ((u64)__builtin_amdgcn_readfirstlane((u32)(x >> 32)) << 32) |
            (u32)__builtin_amdgcn_readfirstlane((u32)x);
@@ -237,7 +249,6 @@ struct RegionArgs {
 
 // Internal launchers (zcg_*.hip) used by zcg_api.cpp.
 namespace zcg {
-struct Workspace;  // defined in zcg_api.cpp
 // Tuning constants of a kernel source, as "name:K=V,K=V" (stringified macros):
 // zcg_build_config() reports them, and tests/test_abi.py checks that the
 // shipped library was built with the defaults.
@@ -256,8 +267,27 @@ const char* cfg_bz2();
 // device's CU count, and a kernel's dynamic-LDS limit raised to `bytes`.
 uint32_t device_cu_count();
 hipError_t lds_attr_once(const void* kernel, int bytes);
-// a second stream of the current device (created once; nullptr if that failed):
-// kernels of one call that may run side by side are forked onto it
+// Work of one call on a side stream beside its stream `s`: fork() makes `side`
+// wait for what `s` holds so far (it may be repeated), join() makes `s` wait for
+// `side`.  The destructor joins an open fork, so no return leaves `s` racing it.
+struct SideFork {
+    hipStream_t s, side;
+    hipEvent_t ev_fork, ev_join;
+    bool open = false;
+    hipError_t fork() {
+        hipError_t e = hipEventRecord(ev_fork, s);
+        if (e == hipSuccess) e = hipStreamWaitEvent(side, ev_fork, 0);
+        open = open || e == hipSuccess;
+        return e;
+    }
+    hipError_t join() {
+        if (!open) return hipSuccess;
+        open = false;
+        const hipError_t e = hipEventRecord(ev_join, side);
+        return e == hipSuccess ? hipStreamWaitEvent(s, ev_join, 0) : e;
+    }
+    ~SideFork() { (void)join(); }
+};
 hipError_t launch_raw(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n, int32_t* d_status,
                       uint64_t* d_out_len, int encode, hipStream_t s);
 // side / fork / join: the caller's side stream and events for the

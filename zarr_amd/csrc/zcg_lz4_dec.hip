@@ -1144,9 +1144,8 @@ hipError_t launch_lz4_decode(const zcg_array* a, const zcg_chunk* d_chunks, uint
             // stream at the same time: the lane kernel is latency-bound and the
             // wave kernel VALU-bound, so they share the CUs
             const u32 n1 = (u32)((u64)n * LZ_CORUN_PCT / 100);
-            hipError_t e = hipEventRecord(fork, s);
-            if (e == hipSuccess) e = hipStreamWaitEvent(s2, fork, 0);
-            if (e != hipSuccess) return e;
+            SideFork sf{s, s2, fork, join};
+            if (hipError_t e = sf.fork(); e != hipSuccess) return e;
             const u64 w2 = (u64)(n - n1) * S;
             hipLaunchKernelGGL(lz4_blocks_kernel, dim3((u32)((w2 + 3) / 4)), dim3(256), 0, s2, d_chunks + n1, n - n1,
                                D, (u32)S, a->compression.flags, (const Lz4ChunkInfo*)info + n1, slots + (u64)n1 * S);
@@ -1155,9 +1154,7 @@ hipError_t launch_lz4_decode(const zcg_array* a, const zcg_chunk* d_chunks, uint
                 hipLaunchKernelGGL(lz4_lanes_kernel, dim3((u32)((w1 + LZ_LPW_CORUN - 1) / LZ_LPW_CORUN)), dim3(LZ_LWG),
                                    0, s, d_chunks, n1, D, (u32)S, a->compression.flags, (const Lz4ChunkInfo*)info,
                                    slots, (u32)LZ_LPW_CORUN);
-            e = hipEventRecord(join, s2);
-            if (e == hipSuccess) e = hipStreamWaitEvent(s, join, 0);
-            if (e != hipSuccess) return e;
+            if (hipError_t e = sf.join(); e != hipSuccess) return e;
         } else {
             const u32 lpw = waves < LZ_LPW_THRESH ? LZ_LPW_SMALL : LZ_LWG;
             hipLaunchKernelGGL(lz4_lanes_kernel, dim3((u32)((waves + lpw - 1) / lpw)), dim3(LZ_LWG), 0, s,

@@ -1,9 +1,9 @@
 // zcg_xz_enc.h — pieces shared by the xz encoders (zcg_xz_enc.hip: the
 // greedy coder of presets 0-3; zcg_xz_opt.hip: the optimal-parse coder of
-// presets 4-9): the LZMA model layout, the wave-uniform range encoder with
-// its lane-distributed output staging, and the serialised-input readers.
+// presets 4-9): the LZMA model layout, the presets' dictionary sizes and the
+// wave-uniform range encoder with its lane-distributed output staging.
 #pragma once
-#include "zcg_common.h"
+#include "zcg_chains.h"
 
 namespace zcg {
 
@@ -24,7 +24,7 @@ enum : u32 { EL_CHOICE = 0, EL_CHOICE2 = 1, EL_LOW = 2, EL_MID = 130, EL_HIGH = 
 
 // log2 of the dictionary of lzma_easy presets 0..9: 256K, 1M, 2M, 4M, 4M, 8M,
 // 8M, 16M, 32M, 64M (the LZMA2 property is 2*(lg-12))
-__device__ __forceinline__ u32 xe_dict_lg(int preset) {
+__host__ __device__ __forceinline__ u32 xz_dict_bits(int preset) {
     const int p = (preset < 0 || preset > 9) ? 6 : preset;
     return p == 0 ? 18u : (p == 1 ? 20u : (p == 2 ? 21u : (p <= 4 ? 22u : (p <= 6 ? 23u : (u32)(p + 17)))));
 }
@@ -198,18 +198,6 @@ struct XeEnc {
     }
 };
 
-// serialised bytes x..x+3 of a chunk (little-endian in the result)
-typedef __attribute__((address_space(1))) u32 xe_gu32_ua __attribute__((aligned(1)));
-__device__ __forceinline__ u32 xe_ser4(const u8* src, u64 x, const DType& t) {
-    if (!t.swap && !t.isbool) return *(const xe_gu32_ua*)((const __attribute__((address_space(1))) u8*)src + x);  // (global, not flat)
-    return (u32)norm_byte(src[swap_pos(x, t)], t) | ((u32)norm_byte(src[swap_pos(x + 1, t)], t) << 8) |
-           ((u32)norm_byte(src[swap_pos(x + 2, t)], t) << 16) | ((u32)norm_byte(src[swap_pos(x + 3, t)], t) << 24);
-}
-
-__device__ __forceinline__ u32 xe_ser1(const u8* src, u64 x, const DType& t) {
-    return norm_byte(src[swap_pos(x, t)], t);
-}
-
 // ---- host side ----
 // presets 4-9: the optimal-parse coder (zcg_xz_opt.hip), as liblzma's
 // presets 4-9 use its normal (optimal) mode; 0-3: the greedy coder
@@ -217,11 +205,13 @@ inline bool xz_uses_opt(const zcg_array* a) {
     const int p = a->compression.xz_preset;
     return (p < 0 || p > 9 ? 6 : p) >= 4;
 }
-// radix-sort scratch bytes for `tot` (key, position) pairs
-u64 xe_sort_scratch(u64 tot);
-// keys, radix sort and chain links of one match-finder sub-batch (zcg_xz_enc.hip)
-hipError_t launch_xe_chains(const zcg_chunk* d_chunks, u32 c0, u64 D, u64 tot, DType t, u32 cbits, u32* ka, u32* kb,
-                            u32* va, u32* vb, u32* prev, void* cub, u64 cub_bytes, hipStream_t s);
+// Both xz coders: 128 MiB of input per match-finder sub-batch (sort scratch), 1 GiB
+// per coder launch (match arrays kept), 12 bits of chunk id beside the 20 hash bits.
+inline SubBatch xz_sub_batch(u64 D, u32 n) { return sub_batch_plan(D, n, 128ull << 20, 1ull << 30, 4096); }
+// The xz key kernel, the shared sort and the chain links (zcg_chains.h) of one
+// match-finder sub-batch: prev[] gets every position's hash chain (zcg_xz_enc.hip)
+hipError_t launch_xe_chains(const zcg_chunk* d_chunks, u32 c0, u64 D, u64 tot, DType t, u32 cbits, u8* w,
+                            const ChainWs& c, hipStream_t s);
 uint64_t xz_opt_ws_bytes(const zcg_array* a, uint32_t n);
 hipError_t launch_xz_opt(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n, uint64_t* d_out_len,
                          int32_t* d_status, void* ws, uint64_t ws_bytes, hipStream_t s);

@@ -12,9 +12,10 @@
 // Match finding runs ahead of the coder, data-parallel over every position of
 // a sub-batch (<= 128 MiB of input), so the whole chunk is the dictionary as in
 // liblzma (whose presets' dictionaries cover a 1 MiB chunk):
-//   * xe_keys + a hipCUB radix sort of (chunk, 20-bit hash of 4 bytes) keys
-//     with the positions as values (stable: ascending positions per key);
-//   * xe_chain: each position's predecessor with the same key = hash chain;
+//   * xe_keys + the shared radix sort (zcg_chains.h) of (chunk, 20-bit hash of
+//     4 bytes) keys with the positions as values (stable: ascending positions
+//     per key);
+//   * chain_links: each position's predecessor with the same key = hash chain;
 //   * xe_best: one thread per position walks its chain up to XE_DEPTH
 //     candidates inside the preset's dictionary and keeps the longest match
 //     (nearest on ties), up to XE_NICE bytes (then it stops walking).
@@ -30,8 +31,6 @@
 //     patched in place), the first with dictionary + state reset and props;
 //   * CRC64 of the serialised chunk by 64 lane segments (zcg_crc.h).
 // '>'-types and bool are serialised on the fly (write_data, chunk.rs:118-140).
-#include <hipcub/hipcub.hpp>
-
 #include "zcg_crc.h"
 #include "zcg_xz_enc.h"
 
@@ -79,7 +78,7 @@ __global__ __launch_bounds__(64) void xz_encode_kernel(const zcg_chunk* __restri
     e.over = false;
     e.probs = (lu16*)probs;
     e.lane = lane;
-    const u32 dlg = xe_dict_lg(preset);
+    const u32 dlg = xz_dict_bits(preset);
     const u32 dprop = 2u * (dlg - 12u);
     const u64 dsize = 1ull << dlg;
 
@@ -285,45 +284,21 @@ __global__ __launch_bounds__(64) void xz_encode_kernel(const zcg_chunk* __restri
 namespace {
 
 constexpr u32 XE_KEYBITS = 20;            // hash bits of the match-finder keys
-constexpr u64 XE_SUB_BYTES = 128ull << 20;  // input bytes per match-finder sub-batch (sort scratch)
-constexpr u64 XE_SUPER_BYTES = 1ull << 30;  // input bytes per coder launch (match arrays kept)
 
-struct XeLayout {
-    u32 m;    // chunks per match-finder sub-batch
-    u32 sm;   // chunks per coder launch (a multiple of m)
-    u64 tot;  // m * D positions
-    u64 cub_bytes;
-    u64 off_ka, off_kb, off_va, off_vb, off_prev, off_blen, off_bdist, off_cub, total;
+struct XeWs {
+    SubBatch b;  // sub-batches of the match finder, super-batches of the coder launch
+    ChainWs c;
+    u64 off_blen, off_bdist, total;
 };
 
-XeLayout xe_layout(u64 D, u32 n) {
-    XeLayout y{};
-    u64 m = D ? XE_SUB_BYTES / D : n;
-    if (m < 1) m = 1;
-    if (m > n) m = n;
-    if (m > 4096) m = 4096;
-    y.m = (u32)m;
-    y.tot = m * D;
-    u64 sm = D ? XE_SUPER_BYTES / D : n;
-    sm = sm / m * m;
-    if (sm < m) sm = m;
-    if (sm > n) sm = n;
-    y.sm = (u32)sm;
-    size_t cb = 0;
-    hipcub::DoubleBuffer<u32> k(nullptr, nullptr), v(nullptr, nullptr);
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, cb, k, v, (int)(y.tot ? y.tot : 1), 0, 32);
-    y.cub_bytes = (cb + 511) & ~255ull;
-    u64 p = 0;
-    auto take = [&](u64 bytes) { const u64 o = p; p = (p + bytes + 255) & ~255ull; return o; };
-    y.off_ka = take(4 * y.tot);
-    y.off_kb = take(4 * y.tot);
-    y.off_va = take(4 * y.tot);
-    y.off_vb = take(4 * y.tot);
-    y.off_prev = take(4 * y.tot);
-    y.off_blen = take(2 * (u64)y.sm * D);
-    y.off_bdist = take(4 * (u64)y.sm * D);
-    y.off_cub = take(y.cub_bytes);
-    y.total = p;
+XeWs xe_ws(u64 D, u32 n) {
+    XeWs y{};
+    y.b = xz_sub_batch(D, n);
+    WsCarve ws;
+    y.c = carve_chain_ws(ws, y.b.tot, true);
+    y.off_blen = ws.take(2 * (u64)y.b.sm * D);
+    y.off_bdist = ws.take(4 * (u64)y.b.sm * D);
+    y.total = ws.total();
     return y;
 }
 
@@ -334,16 +309,9 @@ __global__ void xe_keys(const zcg_chunk* __restrict__ chunks, u32 c0, u64 D, u64
     const u32 cl = (u32)(g / D);
     const u64 p = g - (u64)cl * D;
     u32 h = 0;
-    if (p + 4 <= D && chunks[c0 + cl].src_len >= D) h = (xe_ser4((const u8*)chunks[c0 + cl].src, p, t) * 2654435761u) >> (32 - XE_KEYBITS);
+    if (p + 4 <= D && chunks[c0 + cl].src_len >= D) h = (ser4((const u8*)chunks[c0 + cl].src, p, t) * 2654435761u) >> (32 - XE_KEYBITS);
     keys[g] = (cl << cshift) | h;
     vals[g] = (u32)g;
-}
-
-__global__ void xe_chain(u64 tot, const u32* __restrict__ keys, const u32* __restrict__ vals,
-                         u32* __restrict__ prev) {
-    const u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= tot) return;
-    prev[vals[j]] = (j > 0 && keys[j] == keys[j - 1]) ? vals[j - 1] : 0xFFFFFFFFu;
 }
 
 __global__ void xe_best(const zcg_chunk* __restrict__ chunks, u32 c0, u64 D, u64 tot, DType t, u64 dsize,
@@ -357,22 +325,22 @@ __global__ void xe_best(const zcg_chunk* __restrict__ chunks, u32 c0, u64 D, u64
         const u8* src = (const u8*)chunks[c0 + cl].src;
         const u64 cbase = (u64)cl * D;
         const u32 mx = (D - p) < 273 ? (u32)(D - p) : 273u;
-        const u32 v0 = xe_ser4(src, p, t);
+        const u32 v0 = ser4(src, p, t);
         u32 q = prev[g];
         for (u32 dep = 0; dep < XE_DEPTH && q != 0xFFFFFFFFu; dep++) {
             const u64 qp = q - cbase;
             if (p - qp >= dsize) break;  // beyond the preset's dictionary
             const u32 qn = prev[q];  // the next link, in flight during this candidate's compare
-            if (xe_ser4(src, qp, t) == v0) {
+            if (ser4(src, qp, t) == v0) {
                 u32 k = 4;
                 bool diff = false;
                 while (k + 4 <= mx) {
-                    const u32 x = xe_ser4(src, p + k, t) ^ xe_ser4(src, qp + k, t);
+                    const u32 x = ser4(src, p + k, t) ^ ser4(src, qp + k, t);
                     if (x) { k += (u32)__builtin_ctz(x) >> 3; diff = true; break; }
                     k += 4;
                 }
                 if (!diff)
-                    while (k < mx && xe_ser1(src, p + k, t) == xe_ser1(src, qp + k, t)) k++;
+                    while (k < mx && ser1(src, p + k, t) == ser1(src, qp + k, t)) k++;
                 if (k > best) { best = k; bd = (u32)(p - qp); }
                 if (best >= XE_NICE) break;
             }
@@ -385,23 +353,15 @@ __global__ void xe_best(const zcg_chunk* __restrict__ chunks, u32 c0, u64 D, u64
 
 }  // namespace
 
-u64 xe_sort_scratch(u64 tot) {
-    size_t cb = 0;
-    hipcub::DoubleBuffer<u32> k(nullptr, nullptr), v(nullptr, nullptr);
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, cb, k, v, (int)(tot ? tot : 1), 0, 32);
-    return (cb + 511) & ~255ull;
-}
-
-hipError_t launch_xe_chains(const zcg_chunk* d_chunks, u32 c0, u64 D, u64 tot, DType t, u32 cbits, u32* ka, u32* kb,
-                            u32* va, u32* vb, u32* prev, void* cub, u64 cub_bytes, hipStream_t s) {
-    const u32 G = (u32)((tot + 255) / 256);
-    hipLaunchKernelGGL(xe_keys, dim3(G), dim3(256), 0, s, d_chunks, c0, D, tot, t, XE_KEYBITS, ka, va);
-    hipcub::DoubleBuffer<u32> dk(ka, kb), dv(va, vb);
-    size_t cb = cub_bytes;
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs(cub, cb, dk, dv, (int)tot, 0, (int)(XE_KEYBITS + cbits), s);
+hipError_t launch_xe_chains(const zcg_chunk* d_chunks, u32 c0, u64 D, u64 tot, DType t, u32 cbits, u8* w,
+                            const ChainWs& c, hipStream_t s) {
+    u32 *keys = (u32*)(w + c.ka), *vals = (u32*)(w + c.va);
+    hipLaunchKernelGGL(xe_keys, dim3((u32)((tot + 255) / 256)), dim3(256), 0, s, d_chunks, c0, D, tot, t, XE_KEYBITS,
+                       keys, vals);
+    const hipError_t e = sort_pairs_u32(w + c.cub, c.cub_bytes, keys, (u32*)(w + c.kb), vals, (u32*)(w + c.vb), tot,
+                                        XE_KEYBITS + cbits, s, &keys, &vals);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(xe_chain, dim3(G), dim3(256), 0, s, tot, dk.Current(), dv.Current(), prev);
-    return hipGetLastError();
+    return launch_chain_links(tot, keys, vals, (u32*)(w + c.prev), s);
 }
 
 uint64_t xz_encode_ws_bytes(const zcg_array* a, uint32_t n) {
@@ -409,7 +369,7 @@ uint64_t xz_encode_ws_bytes(const zcg_array* a, uint32_t n) {
     const u64 D = a->chunk_num_elements * (u64)t.es;
     if (n == 0) return 0;
     if (xz_uses_opt(a)) return xz_opt_ws_bytes(a, n);
-    return xe_layout(D, n).total;
+    return xe_ws(D, n).total;
 }
 
 hipError_t launch_xz_encode(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n,
@@ -418,30 +378,22 @@ hipError_t launch_xz_encode(const zcg_array* a, const zcg_chunk* d_chunks, uint3
     if (xz_uses_opt(a)) return launch_xz_opt(a, d_chunks, n, d_out_len, d_status, ws, ws_bytes, s);
     const DType t = make_dtype(a->dtype);
     const u64 D = a->chunk_num_elements * (u64)t.es;
-    const XeLayout y = xe_layout(D, n);
-    if (ws_bytes < y.total || y.tot >= (1ull << 31)) return hipErrorInvalidValue;
+    const XeWs y = xe_ws(D, n);
+    if (ws_bytes < y.total || y.b.tot >= (1ull << 31)) return hipErrorInvalidValue;
     u8* w = (u8*)ws;
     const int preset = a->compression.xz_preset;
-    const int pr = (preset < 0 || preset > 9) ? 6 : preset;
-    const u32 dlg = pr == 0 ? 18u : (pr == 1 ? 20u : (pr == 2 ? 21u : (pr <= 4 ? 22u : (pr <= 6 ? 23u : (u32)(pr + 17)))));
-    u32 cbits = 0;
-    while ((1u << cbits) < y.m) cbits++;
-    for (u32 s0 = 0; s0 < n; s0 += y.sm) {
-        const u32 scnt = (n - s0) < y.sm ? (n - s0) : y.sm;
-        for (u32 c0 = s0; c0 < s0 + scnt; c0 += y.m) {  // match finding, sub-batch by sub-batch
-            const u32 cnt = (s0 + scnt - c0) < y.m ? (s0 + scnt - c0) : y.m;
-            const u64 tot = (u64)cnt * D;
+    const u32 cbits = id_bits(y.b.m);
+    for (u32 s0 = 0; s0 < n; s0 += y.b.sm) {
+        const u32 scnt = batch_count(s0, n, y.b.sm);
+        for (u32 c0 = s0; c0 < s0 + scnt; c0 += y.b.m) {  // match finding, sub-batch by sub-batch
+            const u64 tot = (u64)batch_count(c0, s0 + scnt, y.b.m) * D;
             if (!tot) continue;
-            u32 *ka = (u32*)(w + y.off_ka), *kb = (u32*)(w + y.off_kb);
-            u32 *va = (u32*)(w + y.off_va), *vb = (u32*)(w + y.off_vb);
-            const u32 G = (u32)((tot + 255) / 256);
-            hipError_t e = launch_xe_chains(d_chunks, c0, D, tot, t, cbits, ka, kb, va, vb, (u32*)(w + y.off_prev),
-                                            w + y.off_cub, y.cub_bytes, s);
+            hipError_t e = launch_xe_chains(d_chunks, c0, D, tot, t, cbits, w, y.c, s);
             if (e != hipSuccess) return e;
             const u64 mo = (u64)(c0 - s0) * D;  // this sub-batch's slice of the match arrays
-            hipLaunchKernelGGL(xe_best, dim3(G), dim3(256), 0, s, d_chunks, c0, D, tot, t, 1ull << dlg,
-                               (const u32*)(w + y.off_prev), (u16*)(w + y.off_blen) + mo,
-                               (u32*)(w + y.off_bdist) + mo);
+            hipLaunchKernelGGL(xe_best, dim3((u32)((tot + 255) / 256)), dim3(256), 0, s, d_chunks, c0, D, tot, t,
+                               1ull << xz_dict_bits(preset), (const u32*)(w + y.c.prev),
+                               (u16*)(w + y.off_blen) + mo, (u32*)(w + y.off_bdist) + mo);
         }
         hipLaunchKernelGGL(xz_encode_kernel, dim3(scnt), dim3(64), 0, s, d_chunks, s0, scnt, D, t, preset,
                            (const u16*)(w + y.off_blen), (const u32*)(w + y.off_bdist), d_out_len, d_status);

@@ -57,9 +57,6 @@ constexpr u32 XO_HIST = 0;  // bytes before a window kept in the LDS tile (a 4 K
 constexpr u32 XO_PROBS = 1846 + 0x300;  // lc = lp = 0: one literal coder
 constexpr u32 XO_PROPS = (2 * 5 + 0) * 9 + 0;
 constexpr u64 XO_SEGCAP = XO_SEG + XO_SEG / 16 + 4096;  // a segment's LZMA2 chunks (bound)
-constexpr u32 XO_KEYBITS = 20;
-constexpr u64 XO_SUB_BYTES = 128ull << 20;
-constexpr u64 XO_SUPER_BYTES = 1ull << 30;
 constexpr u32 XO_DMAX_LG = 23;  // candidate distances < 2^23 (they pack in 23 bits)
 constexpr u32 ARC_REP = 2, ARC_MATCH = 1100;  // arc ids: 0 literal, 1 short rep, 2 + r*274 + len, 1100 + len
 #ifndef XO_WPE
@@ -113,20 +110,20 @@ __global__ void xo_cands(const zcg_chunk* __restrict__ chunks, u32 c0, u64 D, u6
         auto common = [&](u64 q) -> u32 {
             u32 k = 0;
             while (k + 4 <= mx) {
-                const u32 x = xe_ser4(src, p + k, t) ^ xe_ser4(src, q + k, t);
+                const u32 x = ser4(src, p + k, t) ^ ser4(src, q + k, t);
                 if (x) return k + ((u32)__builtin_ctz(x) >> 3);
                 k += 4;
             }
-            while (k < mx && xe_ser1(src, p + k, t) == xe_ser1(src, q + k, t)) k++;
+            while (k < mx && ser1(src, p + k, t) == ser1(src, q + k, t)) k++;
             return k;
         };
         u32 best = 1;
         if (p + 3 <= D) {  // the nearest 2-byte repeat within XO_W2
-            const u32 b0 = xe_ser1(src, p, t) | (xe_ser1(src, p + 1, t) << 8);
+            const u32 b0 = ser1(src, p, t) | (ser1(src, p + 1, t) << 8);
             const u64 lo = p > XO_W2 ? p - XO_W2 : 0;
-            u32 w = p > 0 ? xe_ser1(src, p, t) : 0u;  // byte q + 1 of the pair at q (sliding down)
+            u32 w = p > 0 ? ser1(src, p, t) : 0u;  // byte q + 1 of the pair at q (sliding down)
             for (u64 q = p; q-- > lo;) {
-                const u32 v = xe_ser1(src, q, t);
+                const u32 v = ser1(src, q, t);
                 if ((v | (w << 8)) == b0) {
                     const u32 l = common(q);
                     best = l;
@@ -138,7 +135,7 @@ __global__ void xo_cands(const zcg_chunk* __restrict__ chunks, u32 c0, u64 D, u6
         }
         if (p + 4 <= D) {
             if (best < 3) best = 3;
-            const u32 v0 = xe_ser4(src, p, t);
+            const u32 v0 = ser4(src, p, t);
             const u64 cbase = (u64)cl * D;
             u32 q = prev[g];
             for (u32 dep = 0; dep < XO_DEPTH && q != 0xFFFFFFFFu; dep++) {
@@ -146,9 +143,9 @@ __global__ void xo_cands(const zcg_chunk* __restrict__ chunks, u32 c0, u64 D, u6
                 if (p - qp > dmax) break;
                 const u32 qn = prev[q];  // the next link, in flight during this compare
                 u32 l = 0;
-                if (xe_ser4(src, qp, t) == v0) l = common(qp);
+                if (ser4(src, qp, t) == v0) l = common(qp);
                 else {
-                    const u32 x = xe_ser4(src, qp, t) ^ v0;
+                    const u32 x = ser4(src, qp, t) ^ v0;
                     l = (u32)__builtin_ctz(x) >> 3;
                 }
                 if (l > mx) l = mx;
@@ -949,7 +946,7 @@ __global__ __launch_bounds__(64) void xo_assemble(const zcg_chunk* __restrict__ 
         pos++;
         const u64 csize = pos - cdata0;
         while ((pos - cdata0) & 3) { if (lane == 0) put(pos, 0); pos++; }
-        const u64 crc = wave_crc_fn<u64, CRC64_POLY>([&](u64 q) -> u32 { return xe_ser1((const u8*)ch.src, q, t); }, 0, D);
+        const u64 crc = wave_crc_fn<u64, CRC64_POLY>([&](u64 q) -> u32 { return ser1((const u8*)ch.src, q, t); }, 0, D);
         if (lane == 0)
             for (int k = 0; k < 8; k++) put(pos + k, (u32)(crc >> (8 * k)) & 0xFF);
         pos += 8;
@@ -985,39 +982,23 @@ __global__ __launch_bounds__(64) void xo_assemble(const zcg_chunk* __restrict__ 
     }
 }
 
-struct XoLayout {
-    u32 m, sm, nseg;
-    u64 tot, cub_bytes;
-    u64 off_ka, off_kb, off_va, off_vb, off_prev, off_cand, off_seg, off_len, off_cub, total;
+struct XoWs {
+    SubBatch b;
+    u32 nseg;
+    ChainWs c;
+    u64 off_cand, off_seg, off_len, total;
 };
 
-XoLayout xo_layout(u64 D, u32 n) {
-    XoLayout y{};
-    u64 m = D ? XO_SUB_BYTES / D : n;
-    if (m < 1) m = 1;
-    if (m > n) m = n;
-    if (m > 4096) m = 4096;
-    y.m = (u32)m;
-    y.tot = m * D;
-    u64 sm = D ? XO_SUPER_BYTES / D : n;
-    sm = sm / m * m;
-    if (sm < m) sm = m;
-    if (sm > n) sm = n;
-    y.sm = (u32)sm;
+XoWs xo_ws(u64 D, u32 n) {
+    XoWs y{};
+    y.b = xz_sub_batch(D, n);
     y.nseg = D ? (u32)((D + XO_SEG - 1) / XO_SEG) : 1;
-    y.cub_bytes = xe_sort_scratch(y.tot);
-    u64 p = 0;
-    auto take = [&](u64 bytes) { const u64 o = p; p = (p + bytes + 255) & ~255ull; return o; };
-    y.off_ka = take(4 * y.tot);
-    y.off_kb = take(4 * y.tot);
-    y.off_va = take(4 * y.tot);
-    y.off_vb = take(4 * y.tot);
-    y.off_prev = take(4 * y.tot);
-    y.off_cand = take(4ull * XO_K * y.sm * D);
-    y.off_seg = take(XO_SEGCAP * y.sm * y.nseg);
-    y.off_len = take(4ull * y.sm * y.nseg);
-    y.off_cub = take(y.cub_bytes);
-    y.total = p;
+    WsCarve ws;
+    y.c = carve_chain_ws(ws, y.b.tot, true);
+    y.off_cand = ws.take(4ull * XO_K * y.b.sm * D);
+    y.off_seg = ws.take(XO_SEGCAP * y.b.sm * y.nseg);
+    y.off_len = ws.take(4ull * y.b.sm * y.nseg);
+    y.total = ws.total();
     return y;
 }
 
@@ -1036,7 +1017,7 @@ uint64_t xz_opt_ws_bytes(const zcg_array* a, uint32_t n) {
     const DType t = make_dtype(a->dtype);
     const u64 D = a->chunk_num_elements * (u64)t.es;
     if (n == 0) return 0;
-    return xo_layout(D, n).total;
+    return xo_ws(D, n).total;
 }
 
 hipError_t launch_xz_opt(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n, uint64_t* d_out_len,
@@ -1044,29 +1025,21 @@ hipError_t launch_xz_opt(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t
     if (n == 0) return hipSuccess;
     const DType t = make_dtype(a->dtype);
     const u64 D = a->chunk_num_elements * (u64)t.es;
-    const XoLayout y = xo_layout(D, n);
-    if (ws_bytes < y.total || y.tot >= (1ull << 31) || D >= (1ull << 32)) return hipErrorInvalidValue;
+    const XoWs y = xo_ws(D, n);
+    if (ws_bytes < y.total || y.b.tot >= (1ull << 31) || D >= (1ull << 32)) return hipErrorInvalidValue;
     u8* w = (u8*)ws;
-    const int preset = a->compression.xz_preset;
-    const int pr = (preset < 0 || preset > 9) ? 6 : preset;
-    const u32 dlg = pr == 0 ? 18u : (pr == 1 ? 20u : (pr == 2 ? 21u : (pr <= 4 ? 22u : (pr <= 6 ? 23u : (u32)(pr + 17)))));
+    const u32 dlg = xz_dict_bits(a->compression.xz_preset);
     const u64 dmax = dlg < XO_DMAX_LG ? (1ull << dlg) : (1ull << XO_DMAX_LG);
-    u32 cbits = 0;
-    while ((1u << cbits) < y.m) cbits++;
-    for (u32 s0 = 0; s0 < n; s0 += y.sm) {
-        const u32 scnt = (n - s0) < y.sm ? (n - s0) : y.sm;
-        for (u32 c0 = s0; c0 < s0 + scnt; c0 += y.m) {
-            const u32 cnt = (s0 + scnt - c0) < y.m ? (s0 + scnt - c0) : y.m;
-            const u64 tot = (u64)cnt * D;
+    const u32 cbits = id_bits(y.b.m);
+    for (u32 s0 = 0; s0 < n; s0 += y.b.sm) {
+        const u32 scnt = batch_count(s0, n, y.b.sm);
+        for (u32 c0 = s0; c0 < s0 + scnt; c0 += y.b.m) {
+            const u64 tot = (u64)batch_count(c0, s0 + scnt, y.b.m) * D;
             if (!tot) continue;
-            u32 *ka = (u32*)(w + y.off_ka), *kb = (u32*)(w + y.off_kb);
-            u32 *va = (u32*)(w + y.off_va), *vb = (u32*)(w + y.off_vb);
-            const u32 G = (u32)((tot + 255) / 256);
-            hipError_t e = launch_xe_chains(d_chunks, c0, D, tot, t, cbits, ka, kb, va, vb, (u32*)(w + y.off_prev),
-                                            w + y.off_cub, y.cub_bytes, s);
+            hipError_t e = launch_xe_chains(d_chunks, c0, D, tot, t, cbits, w, y.c, s);
             if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(xo_cands, dim3(G), dim3(256), 0, s, d_chunks, c0, D, tot, t, dmax,
-                               (const u32*)(w + y.off_prev), (u32*)(w + y.off_cand) + (u64)(c0 - s0) * D * XO_K);
+            hipLaunchKernelGGL(xo_cands, dim3((u32)((tot + 255) / 256)), dim3(256), 0, s, d_chunks, c0, D, tot, t, dmax,
+                               (const u32*)(w + y.c.prev), (u32*)(w + y.off_cand) + (u64)(c0 - s0) * D * XO_K);
         }
         if (D > 0)
             hipLaunchKernelGGL(xo_segment, dim3(scnt * y.nseg), dim3(64), 0, s, d_chunks, s0, D, t, y.nseg,
