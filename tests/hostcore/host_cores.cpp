@@ -278,3 +278,28 @@ extern "C" uint64_t zh_ws_carve(const uint64_t* sizes, uint32_t k, uint64_t* off
     for (uint32_t i = 0; i < k; i++) offs[i] = ws.take(sizes[i]);
     return ws.total();
 }
+
+// ---- the gzip member frame's word-level parts (zcg_inflate_word.h) ----
+#include "../../zarr_amd/csrc/zcg_inflate_word.h"
+
+extern "C" uint64_t zh_inf_lookahead_limit(uint64_t h, uint64_t consumed, uint64_t n_in) {
+    return zcg::inf_lookahead_limit(h, consumed, n_in);
+}
+
+// serial table entries e[0..n) -> the wave kernel's entries and back again
+// (dist: the distance table's pair of maps)
+extern "C" void zh_iw_maps(const uint32_t* e, uint32_t n, int dist, uint32_t* wave, uint32_t* back) {
+    for (uint32_t i = 0; i < n; i++) {
+        wave[i] = dist ? zcg::iw_d_wave(e[i]) : zcg::iw_l_wave(e[i]);
+        back[i] = dist ? zcg::iw_d_serial(wave[i]) : zcg::iw_l_serial(wave[i]);
+    }
+}
+
+// out[0..5) = marker, bits, len, len_tok, dist of token word t
+extern "C" void zh_tok_word(uint32_t t, uint32_t* out) {
+    out[0] = zcg::w_marker(t);
+    out[1] = zcg::w_bits(t);
+    out[2] = zcg::w_len(t);
+    out[3] = zcg::w_len_tok(t);
+    out[4] = zcg::w_dist(t);
+}

@@ -544,7 +544,8 @@ def test_inflate_wave_capped_chain_keeps_block_positions():
     s = gzip_wrap(deflate(payload, 6, zlib.Z_HUFFMAN_ONLY), payload)
     st, ref = zref.decode(zref.GZIP, s, len(payload), 1, 0, 0)
     assert st == zref.OK and ref == payload
-    for flags in (FLAG_INFLATE_WAVE | 0x10000, FLAG_INFLATE_WAVE):
+    from zarr_amd import _native
+    for flags in (FLAG_INFLATE_WAVE | _native.FLAG_DEBUG_INFLATE_LONG_SEG, FLAG_INFLATE_WAVE):
         kind, out = gpu_decode("gzip", s, "u1", len(payload), None, flags)
         assert kind == "Ok", (kind, flags)
         assert out == payload, flags

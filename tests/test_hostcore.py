@@ -27,6 +27,12 @@ def host():
         _H.zh_bz2_decode.restype = ctypes.c_int
         _H.zh_sub_batch_plan.restype = None
         _H.zh_ws_carve.restype = ctypes.c_uint64
+        _H.zh_inf_lookahead_limit.argtypes = [ctypes.c_uint64] * 3
+        _H.zh_inf_lookahead_limit.restype = ctypes.c_uint64
+        _H.zh_iw_maps.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+        _H.zh_iw_maps.restype = None
+        _H.zh_tok_word.argtypes = [ctypes.c_uint32, ctypes.c_void_p]
+        _H.zh_tok_word.restype = None
     return _H
 
 
@@ -572,3 +578,99 @@ def test_ws_carve_regions():
             assert offs[i] + sizes[i] <= offs[i + 1]
         assert offs[-1] + sizes[-1] <= total
         assert total == sum((s + 255) // 256 * 256 for s in sizes)
+
+
+# ---- the gzip member frame's word-level parts (zcg_inflate_word.h) ----
+# (h, consumed bits, n_in) -> look-ahead limit in deflate-stream bits: the end
+# of the 32 KiB window of the member that holds the last consumed bit, or the
+# member's end.  Expected values worked out by hand from
+#   last = h + (consumed ? (consumed - 1) / 8 : 0); wend = min((last / 32768 + 1) * 32768, n_in); (wend - h) * 8
+LOOKAHEAD_PINS = [
+    # last consumed byte is byte 32 767 of the member (first and last bit of it)
+    ((10, 32757 * 8 + 1, 100000), (32768 - 10) * 8),
+    ((10, 32757 * 8 + 8, 100000), (32768 - 10) * 8),
+    # ... byte 32 768: the next window
+    ((10, 32758 * 8 + 1, 100000), (65536 - 10) * 8),
+    ((10, 32758 * 8 + 8, 100000), (65536 - 10) * 8),
+    # the member ends before the window does
+    ((10, 32758 * 8 + 1, 40000), (40000 - 10) * 8),
+    ((10, 5 * 8, 18), 8 * 8),
+    # nothing consumed: the window that holds byte h
+    ((10, 0, 100000), (32768 - 10) * 8),
+    ((10, 0, 18), 8 * 8),
+    ((40000, 0, 100000), (65536 - 40000) * 8),
+    ((32767, 0, 100000), 1 * 8),
+    ((32767, 9, 100000), (65536 - 32767) * 8),
+]
+
+
+@pytest.mark.parametrize("args,want", LOOKAHEAD_PINS)
+def test_inf_lookahead_limit_pinned(args, want):
+    assert host().zh_inf_lookahead_limit(*args) == want
+
+
+K_LIT, K_LEN, K_EOB, K_BAD, K_DIST, K_SUB = range(6)
+W_MATCH, W_MARK, M_EOB, M_BAD, M_EXH = 0x80000000, 0x40000000, 0, 1, 2
+# RFC 1951 3.2.5: (base, extra bits) of length symbols 257..285 and distance symbols 0..29
+LEN_SYMS = list(zip([3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131,
+                     163, 195, 227, 258], [0] * 8 + [1] * 4 + [2] * 4 + [3] * 4 + [4] * 4 + [5] * 4 + [0]))
+DIST_SYMS = list(zip([1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537,
+                      2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577],
+                     [0, 0, 0, 0] + [x for x in range(1, 14) for _ in range(2)]))
+assert len(LEN_SYMS) == 29 and len(DIST_SYMS) == 30
+
+
+def _mk(length, kind, extra, val):
+    return (length << 28) | (kind << 24) | (extra << 16) | val
+
+
+def _iw_maps(entries, dist):
+    e = np.asarray(entries, np.uint32)
+    wave = np.zeros_like(e)
+    back = np.zeros_like(e)
+    host().zh_iw_maps(e.ctypes.data, len(e), int(dist), wave.ctypes.data, back.ctypes.data)
+    return e, wave, back
+
+
+def test_iw_table_maps_bijective_on_reachable_entries():
+    """Every entry build_table can put into the wave kernel's tables (9-bit
+    literal/length root in 852 words, 8-bit distance root in 432) maps to the
+    wave layout and back to itself, no two entries share an image, and a
+    literal's and a marker's image is the token word itself."""
+    lens = range(1, 16)
+    lits = [_mk(l, K_LIT, 0, v) for l in lens for v in range(256)]
+    eobs = [_mk(l, K_EOB, 0, 0) for l in lens]
+    bads = [_mk(l, K_BAD, 0, 0) for l in lens]
+    lsyms = [_mk(l, K_LEN, x, b) for l in lens for b, x in LEN_SYMS]
+    llinks = [_mk(0, K_SUB, sb, off) for sb in range(1, 15 - 9 + 1) for off in range(512, 852 - (1 << sb) + 1)]
+    e, wave, back = _iw_maps(lits + eobs + bads + lsyms + llinks, dist=False)
+    assert np.array_equal(back, e)
+    assert len(set(wave.tolist())) == len(e)
+    n = len(lits)
+    assert wave[:n].tolist() == [(l << 24) | v for l in lens for v in range(256)]
+    assert wave[n:n + 15].tolist() == [W_MARK | (l << 24) | M_EOB for l in lens]
+    assert wave[n + 15:n + 30].tolist() == [W_MARK | (l << 24) | M_BAD for l in lens]
+
+    dsyms = [_mk(l, K_DIST, x, b) for l in lens for b, x in DIST_SYMS]
+    dlinks = [_mk(0, K_SUB, sb, off) for sb in range(1, 15 - 8 + 1) for off in range(256, 432 - (1 << sb) + 1)]
+    e, wave, back = _iw_maps(bads + dsyms + dlinks, dist=True)
+    assert np.array_equal(back, e)
+    assert len(set(wave.tolist())) == len(e)
+    assert wave[:15].tolist() == [W_MARK | (l << 24) | M_BAD for l in lens]
+
+
+def test_token_word_accessors():
+    def word(t):
+        out = (ctypes.c_uint32 * 5)()
+        host().zh_tok_word(t, out)
+        return list(out)
+    # literal 'A' of 8 bits; match len 258 dist 32768 of 48 bits; the three markers (with and without bits)
+    assert word((8 << 24) | 0x41) == [0, 8, 1, 1, 0x42]
+    assert word(W_MATCH | (48 << 24) | (255 << 16) | 32767) == [0, 48, 258, 258, 32768]
+    assert word(W_MATCH | (2 << 24) | (0 << 16) | 0) == [0, 2, 3, 3, 1]
+    for code in (M_EOB, M_BAD, M_EXH):
+        for bits in (0, 7, 15):
+            m, b, ln, _, _ = word(W_MARK | (bits << 24) | code)
+            assert (m, b, ln) == (1, bits, 0)
+    # the 256-lane kernel's marker words are the same words with no bit length
+    assert (W_MARK | M_EOB, W_MARK | M_BAD, W_MARK | M_EXH) == (0x40000000, 0x40000001, 0x40000002)

@@ -820,9 +820,7 @@ __global__ __launch_bounds__(256) void bz2_stage_bc_kernel(const zcg_chunk* __re
     if (!__builtin_amdgcn_readfirstlane(st->pending)) return;
     S.crct[tid] = g_bzcrc.t[tid];
     if (tid == 0) {
-        u32 b = k % nb;
-        while (atomicCAS(&owner[b], 0u, 1u) != 0u) b = (b + 1) % nb;
-        S.sh.p0 = b;  // (p0 is rewritten by the ranking stage)
+        S.sh.p0 = slot_take(owner, nb, k);  // (p0 is rewritten by the ranking stage)
         S.sh.nblock = st->s.nblock;
         S.sh.orig = st->s.orig_ptr;
         S.sh.stored_crc = st->s.stored_crc;
@@ -845,7 +843,7 @@ __global__ __launch_bounds__(256) void bz2_stage_bc_kernel(const zcg_chunk* __re
         st->final_status = fs;
         st->pending = 0;
         if (fs >= 0) status[c] = fs;
-        atomicExch(&owner[b], 0u);
+        slot_free(owner, b);
     }
 }
 
@@ -871,9 +869,7 @@ __global__ __launch_bounds__(256) void bz2_decode_kernel(const zcg_chunk* __rest
     S.crct[tid] = g_bzcrc.t[tid];
     const zcg_chunk ch = chunks[c];
     if (tid == 0) {
-        u32 b = k % nb;
-        while (atomicCAS(&owner[b], 0u, 1u) != 0u) b = (b + 1) % nb;
-        S.sh.p0 = b;
+        S.sh.p0 = slot_take(owner, nb, k);
         S.sh.out_pos = 0;
     }
     __syncthreads();
@@ -918,7 +914,7 @@ __global__ __launch_bounds__(256) void bz2_decode_kernel(const zcg_chunk* __rest
     if (tid == 0) {
         status[c] = final_status;
         st->final_status = final_status;
-        atomicExch(&owner[b], 0u);
+        slot_free(owner, b);
     }
 }
 

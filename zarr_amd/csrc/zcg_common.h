@@ -121,11 +121,12 @@ __device__ __forceinline__ u64 ru64(u64 x) {  // wave-uniform 64-bit value -> SG
            (u32)__builtin_amdgcn_readfirstlane((u32)x);
 }
 
-// In-place element transform of a decoded chunk by the whole wave.
-__device__ inline void wave_transform(u8* dst, u64 D, const DType& t) {
-    const int lane = lane_id();
+// In-place element transform of a decoded chunk by NT threads (a wave, or the
+// whole workgroup): thread `tid` of them.
+template <u32 NT>
+__device__ inline void wave_transform(u8* dst, u64 D, const DType& t, u32 tid) {
     const bool al = (((uintptr_t)dst) & 15) == 0;
-    for (u64 p = (u64)lane * 16; p < D; p += 64 * 16) {
+    for (u64 p = (u64)tid * 16; p < D; p += NT * 16) {
         if (p + 16 <= D) {
             u32x4 v = al ? *(u32x4*)(dst + p) : ld16(dst + p);
             v = transform16(v, t);
@@ -138,6 +139,17 @@ __device__ inline void wave_transform(u8* dst, u64 D, const DType& t) {
         }
     }
 }
+
+// Workspace slots of a launch: owner[s] is 0 (free) or 1 (taken), zeroed by
+// the launcher; there are at least as many slots as resident workgroups.  One
+// thread of a workgroup takes the first free slot from `start` on and frees it
+// after the workgroup's last access to the slot's memory (a barrier before).
+__device__ __forceinline__ u32 slot_take(u32* owner, u32 nslot, u32 start) {
+    u32 s = start % nslot;
+    while (atomicCAS(&owner[s], 0u, 1u) != 0u) s = (s + 1) % nslot;
+    return s;
+}
+__device__ __forceinline__ void slot_free(u32* owner, u32 slot) { atomicExch(&owner[slot], 0u); }
 
 // ---- XXH32 (LZ4 frame header / block / content checksums) --------------
 constexpr u32 XXH_P1 = 2654435761u;
@@ -300,6 +312,12 @@ hipError_t launch_lz4_encode(const zcg_array* a, const zcg_chunk* d_chunks, uint
                              uint64_t* d_out_len, int32_t* d_status, void* ws, uint64_t ws_bytes,
                              hipStream_t s);
 uint64_t lz4_encode_ws_bytes(const zcg_array* a, uint32_t n);
+// Gzip decode: the serial / 256-lane / wave pick lives in zcg_inflate.hip
+// (gzip_decode_ws_bytes and launch_gzip_decode agree on it); the three
+// launchers below it are the kernels' own.
+uint64_t gzip_decode_ws_bytes(const zcg_array* a, uint32_t n);
+hipError_t launch_gzip_decode(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n,
+                              int32_t* d_status, void* ws, uint64_t ws_bytes, hipStream_t s);
 hipError_t launch_inflate(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n,
                           int32_t* d_status, hipStream_t s);
 hipError_t launch_inflate_par(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n,

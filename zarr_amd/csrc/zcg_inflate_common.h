@@ -1,9 +1,19 @@
 // zcg_inflate_common.h — RFC 1951 / gzip machinery shared by the serial
-// (zcg_inflate.hip) and parallel (zcg_inflate_par.hip) inflate kernels:
-// Huffman tables in LDS, the wave-uniform bit reader, block headers, zlib's
-// post-N look-ahead, flate2's gzip header rules.
+// (zcg_inflate.hip), 256-lane (zcg_inflate_par.hip) and wave
+// (zcg_inflate_wave.hip) inflate kernels: Huffman tables in LDS, the
+// wave-uniform bit reader, and the gzip MEMBER FRAME that all three run their
+// own block loops inside:
+//   inf_open           guards, flate2's gzip header rules -> InfMember
+//   read_block_header  BFINAL/BTYPE, stored lengths, fixed tables; the dynamic
+//                      header reader is the kernel's own (a parameter)
+//   inf_stored_copy    a stored block through a kernel's stage (256-lane, wave)
+//   stage_commit       a stage of 16-bit entries -> dst, byte order fused
+//   inf_close          zlib's post-N look-ahead, result -> status
+// The word-level parts (table entry, token word, look-ahead window) are in
+// zcg_inflate_word.h, which the CPU suite also compiles.
 #pragma once
 #include "zcg_common.h"
+#include "zcg_inflate_word.h"
 
 namespace zcg {
 
@@ -16,10 +26,8 @@ constexpr u32 INF_RING = 32768;
 constexpr u32 INF_FLUSH = 16384;
 
 // Two-level tables: every code decodes in <= 2 LDS lookups (no bit-serial
-// path: a rare per-lane slow path would stall whole 64-lane waves).
-// entry: [31:28] code length | [27:24] kind | [23:16] extra bits | [15:0] value
-//        K_SUB: [23:16] subtable bits, [15:0] subtable offset (code length 0)
-enum : u32 { K_LIT = 0, K_LEN = 1, K_EOB = 2, K_BAD = 3, K_DIST = 4, K_SUB = 5 };
+// path: a rare per-lane slow path would stall whole 64-lane waves).  The entry
+// layout (mk_entry, K_*) is in zcg_inflate_word.h.
 
 __constant__ u16 c_len_base[29] = {3,  4,  5,  6,  7,  8,  9,  10, 11,  13,  15,  17,  19,  23, 27,
                                    31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
@@ -32,10 +40,6 @@ __constant__ u16 c_dist_base[30] = {1,    2,    3,    4,    5,    7,     9,     
 __constant__ u8 c_dist_extra[30] = {0, 0, 0, 0, 1, 1, 2, 2,  3,  3,  4,  4,  5,  5,  6,
                                     6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
 __constant__ u8 c_clen_order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-
-__device__ __forceinline__ u32 mk_entry(u32 len, u32 kind, u32 extra, u32 val) {
-    return (len << 28) | (kind << 24) | (extra << 16) | val;
-}
 
 // Canonical Huffman code description in LDS (built per block).
 struct HuffLds {
@@ -222,15 +226,49 @@ __device__ __forceinline__ void bi_init(BitIn& b, const u8* src, u64 n, u32* cac
     b.cache = cache; b.cbase = ~0ull;
 }
 
+// Little-endian load of sizeof(W) = 4, 8 or 16 bytes at src + q from a buffer
+// of n bytes: the whole word when it fits, else the bytes that exist (the rest
+// read as 0).  W is the unaligned word view in src's address space (u32_ua,
+// gu64_ua, u32x4_ua ...); the result is u32, u64 or u32x4.
+template <class W, class B>
+__device__ __forceinline__ auto ld_tail(const B* src, u64 q, u64 n) {
+    constexpr u32 NB = sizeof(W);
+    static_assert(NB == 4 || NB == 8 || NB == 16, "word size");
+    if constexpr (NB == 4) {
+        u32 w = 0;
+        if (q + 4 <= n) w = *(const W*)(src + q);
+        else
+            for (u32 i = 0; i < 4; i++)
+                if (q + i < n) w |= (u32)src[q + i] << (8 * i);
+        return w;
+    } else if constexpr (NB == 8) {
+        const bool whole = q + 8 <= n;
+        u64 w = 0;
+        if (!whole)
+            for (u32 i = 0; i < 8; i++)
+                if (q + i < n) w |= (u64)src[q + i] << (8 * i);
+        if (whole) w = *(const W*)(src + q);
+        return w;
+    } else {
+        u32x4 w = {0u, 0u, 0u, 0u};
+        if (q + 16 <= n) w = *(const W*)(src + q);
+        else {
+            u64 lo = 0, hi = 0;
+            for (u32 i = 0; i < 16; i++)
+                if (q + i < n) {
+                    const u64 b8 = (u64)src[q + i] << (8 * (i & 7));
+                    if (i < 8) lo |= b8; else hi |= b8;
+                }
+            w = u32x4{(u32)lo, (u32)(lo >> 32), (u32)hi, (u32)(hi >> 32)};
+        }
+        return w;
+    }
+}
+
 __device__ __forceinline__ u32 bi_word(BitIn& b, u64 pos) {
     if (pos < b.cbase || pos + 4 > b.cbase + 4 * BI_CACHE_WORDS) {
         const int lane = lane_id();
-        const u64 q = pos + 4 * (u64)lane;
-        u32 w = 0;
-        if (q + 4 <= b.n) w = ld32(b.src + q);
-        else
-            for (u32 i = 0; i < 4; i++)
-                if (q + i < b.n) w |= (u32)b.src[q + i] << (8 * i);
+        const u32 w = ld_tail<u32_ua>(b.src, pos + 4 * (u64)lane, b.n);
         __builtin_amdgcn_wave_barrier();
         b.cache[lane] = w;
         __builtin_amdgcn_wave_barrier();
@@ -427,10 +465,12 @@ __device__ void fixed_tables(u8* lens, HuffLds* lh, u32* ltab, HuffLds* dh, u32*
 }
 
 // Block header: 3 bits, then stored-length check / table construction.
-// *type receives BTYPE; for stored blocks *slen the LEN field.
-template <int LB = INF_LBITS, u32 LCAP = INF_LTAB, int DB = INF_DBITS, u32 DCAP = INF_DTAB>
+// *type receives BTYPE; for stored blocks *slen the LEN field.  A dynamic
+// header is read by `dyn(b)`, the calling kernel's own reader (read_dynamic
+// above, or its block- or wave-parallel restatement: same rules, same result).
+template <int LB = INF_LBITS, u32 LCAP = INF_LTAB, int DB = INF_DBITS, u32 DCAP = INF_DTAB, class Dyn>
 __device__ __attribute__((always_inline)) int read_block_header(BitIn& b, bool* last, u32* type, u32* slen, u8* lens, HuffLds* lh,
-                                 u32* ltab, HuffLds* dh, u32* dtab) {
+                                 u32* ltab, HuffLds* dh, u32* dtab, Dyn dyn) {
     if (!bi_has(b, 3)) return R_EXHAUSTED;
     const u32 hdr = bi_bits(b, 3);
     *last = hdr & 1;
@@ -446,7 +486,14 @@ __device__ __attribute__((always_inline)) int read_block_header(BitIn& b, bool* 
     }
     if (*type == 3) return R_INVALID;  // "invalid block type"
     if (*type == 1) { fixed_tables<LB, LCAP, DB, DCAP>(lens, lh, ltab, dh, dtab); return R_OK; }
-    return read_dynamic<LB, LCAP, DB, DCAP>(b, lens, lh, ltab, dh, dtab);
+    return dyn(b);
+}
+// ... with the serial dynamic-header reader
+template <int LB = INF_LBITS, u32 LCAP = INF_LTAB, int DB = INF_DBITS, u32 DCAP = INF_DTAB>
+__device__ __attribute__((always_inline)) int read_block_header(BitIn& b, bool* last, u32* type, u32* slen, u8* lens, HuffLds* lh,
+                                 u32* ltab, HuffLds* dh, u32* dtab) {
+    return read_block_header<LB, LCAP, DB, DCAP>(b, last, type, slen, lens, lh, ltab, dh, dtab,
+        [&](BitIn& bb) __attribute__((always_inline)) { return read_dynamic<LB, LCAP, DB, DCAP>(bb, lens, lh, ltab, dh, dtab); });
 }
 
 // zlib keeps decoding after the output is full until it needs to emit a
@@ -530,6 +577,110 @@ __device__ inline int gzip_header(const u8* s, u64 n_in, u64* hlen) {
     }
     *hlen = h;
     return ZCG_OK;
+}
+
+// ---- the member frame ----------------------------------------------------------------------
+// An open member: the deflate stream ds[0, n_ds) after h header bytes of the
+// n_in member bytes, and the output with the transform a kernel commits with
+// (bool waits for the end of the chunk where the output is the LZ77 window).
+struct InfMember {
+    const u8* ds;
+    u64 n_ds, h, n_in;
+    u8* dst;
+    DType tw;
+};
+
+// The guards every kernel starts with and flate2's header.  false: *st is the
+// chunk's final status (ZCG_OK for an empty chunk).  A kernel's own size
+// limits come after this.
+__device__ __forceinline__ bool inf_open(const zcg_chunk& ch, u64 D, DType t, InfMember& m, int* st) {
+    if (D == 0) { *st = ZCG_OK; return false; }
+    if (ch.dst_cap < D) { *st = ZCG_ERR_INVALID_INPUT; return false; }
+    const u8* s = (const u8*)ch.src;
+    u64 h = 0;
+    *st = gzip_header(s, ch.src_len, &h);
+    if (*st != ZCG_OK) return false;
+    m.ds = s + h;
+    m.n_ds = ch.src_len - h;
+    m.h = h;
+    m.n_in = ch.src_len;
+    m.dst = (u8*)ch.dst;
+    m.tw = t;
+    m.tw.isbool = 0;
+    return true;
+}
+
+// The end of every kernel's block loop: r = the loop's result, P = bytes
+// produced, boundary = the output filled exactly at a token boundary (then
+// zlib looks ahead, inf_lookahead, inside inf_lookahead_limit), last /
+// after_stored = the block the loop stopped in.  Returns the chunk's status.
+template <int LB = INF_LBITS, u32 LCAP = INF_LTAB, int DB = INF_DBITS, u32 DCAP = INF_DTAB>
+__device__ __attribute__((always_inline)) int inf_close(BitIn& b, const InfMember& m, int r, u64 P, u64 D, bool boundary,
+                                                        bool last, bool after_stored, u8* lens, HuffLds* lh, u32* ltab,
+                                                        HuffLds* dh, u32* dtab) {
+    if (r == R_OK && P >= D && boundary) {
+        b.limit = inf_lookahead_limit(m.h, b.consumed, m.n_in);
+        if (b.limit >= b.consumed) {
+            const int la = inf_lookahead<LB, LCAP, DB, DCAP>(b, last, after_stored, lens, lh, ltab, dh, dtab);
+            if (la == R_INVALID) r = R_INVALID;
+        }
+    }
+    if (r == R_INVALID) return ZCG_ERR_INVALID_DATA;
+    if (r == R_EXHAUSTED || P < D) return ZCG_ERR_UNEXPECTED_EOF;
+    return ZCG_OK;
+}
+
+// Stage entries (u16) of the parallel kernels: SE_VAL | byte is a final byte
+// value; anything below is the kernel's own (pointers to earlier bytes).
+constexpr u32 SE_VAL = 0xFF00u;
+
+// Flush the resolved stage bytes [from, to) to dst by NT threads (byte-order
+// transform fused): 16-byte-aligned output pieces by vector, the head and the
+// tail by bytes.  Output position q sits at stage[idx(q)], and 16 entries from
+// a 16-aligned q are contiguous there.  The barriers around it (the stage is
+// complete; the bytes are visible to the next window reads) are the caller's.
+template <u32 NT, class Idx>
+__device__ __forceinline__ void stage_commit(const u16* stage, u8* dst, u64 from, u64 to, DType t, u32 tid, Idx idx) {
+    const u64 a16 = (from + 15) & ~15ull, b16 = to & ~15ull;
+    if (a16 < b16) {
+        for (u64 p = a16 + (u64)tid * 16; p < b16; p += NT * 16) {
+            const u32 i = idx(p);
+            const u32x4 lo = *(const u32x4*)(stage + i);
+            const u32x4 hi = *(const u32x4*)(stage + i + 8);
+            // each u32 holds two 16-bit entries; keep their low bytes
+            auto pk = [](u32 a, u32 b) -> u32 { return __builtin_amdgcn_perm(b, a, 0x06040200u); };
+            const u32x4 v = u32x4{pk(lo.x, lo.y), pk(lo.z, lo.w), pk(hi.x, hi.y), pk(hi.z, hi.w)};
+            st16(dst + p, transform16(v, t));
+        }
+    }
+    const u64 e0 = a16 < b16 ? a16 : to;
+    for (u64 q = from + tid; q < e0; q += NT) dst[swap_pos(q, t)] = (u8)stage[idx(q)];
+    if (a16 < b16)
+        for (u64 q = b16 + tid; q < to; q += NT) dst[swap_pos(q, t)] = (u8)stage[idx(q)];
+}
+
+// A stored block of slen bytes at stream byte in0, copied through the stage at
+// most `cap` bytes at a time by NT threads: entry(P, i) = the stage index of
+// the i-th byte of a piece that starts at output position P, commit(from, to)
+// flushes a piece (with the kernel's barriers).  Stops at D.  Returns R_OK or
+// R_EXHAUSTED; *in_end = the stream byte after the copied ones, *whole = the
+// block was copied to its end.
+template <u32 NT, class Entry, class Commit>
+__device__ __forceinline__ int inf_stored_copy(const InfMember& m, u64 in0, u32 slen, u64& P, u64 D, u32 cap, u16* stage,
+                                               u32 tid, Entry entry, Commit commit, u64* in_end, bool* whole) {
+    u32 done = 0;
+    while (done < slen && P < D) {
+        u32 k = slen - done;
+        if (k > cap) k = cap;
+        if ((u64)k > D - P) k = (u32)(D - P);
+        if (in0 + k > m.n_ds) return R_EXHAUSTED;
+        for (u32 i = tid; i < k; i += NT) stage[entry(P, i)] = (u16)(SE_VAL | m.ds[in0 + i]);
+        commit(P, P + k);
+        P += k; in0 += k; done += k;
+    }
+    *in_end = in0;
+    *whole = done == slen;
+    return R_OK;
 }
 
 }  // namespace zcg

@@ -62,12 +62,7 @@ constexpr u32 PI_IN_PAD = PI_IN_WORDS + PI_IN_WORDS / 8 + 8;
 __device__ __forceinline__ u32 padw(u32 w) { return w + (w >> 3); }
 constexpr u32 PI_MAXSEG = 64;    // chain segments tracked per round
 
-// token word: literal = byte value; match = 1<<31 | (len-3)<<16 | (dist-1);
-// markers (bit 30): EOB, invalid code, input exhausted.
-constexpr u32 T_MATCH = 0x80000000u;
-constexpr u32 T_EOB = 0x40000000u;
-constexpr u32 T_BAD = 0x40000001u;
-constexpr u32 T_EXH = 0x40000002u;
+// (token word: zcg_inflate_word.h; this kernel's markers carry no bit length)
 
 // lane stop codes (next[] >= PI_NL)
 constexpr u32 N_ROUND_END = PI_NL;  // reached the end of the round's range
@@ -92,17 +87,11 @@ enum { TP_HDR = 16, TP_STAGE, TP_PASS1, TP_PASS2, TP_CHAIN, TP_PLACE, TP_LIT, TP
         }                                                                            \
     } while (0)
 
-__device__ __forceinline__ bool tok_is_marker(u32 t) { return (t & 0xC0000000u) == 0x40000000u; }
-__device__ __forceinline__ u32 tok_len(u32 t) { return (t & T_MATCH) ? ((t >> 16) & 0xFF) + 3 : 1; }
-__device__ __forceinline__ u32 tok_dist(u32 t) { return (t & 0x7FFF) + 1; }
-// stream bits of a literal/match token (bits 24..29; <= 48)
-__device__ __forceinline__ u32 tok_bits(u32 t) { return (t >> 24) & 63; }
-
 // Round-stage entries (u16): E_VAL|byte is a final byte value; a value below
 // PI_STAGE points at an earlier byte of the same round (offset from the round
 // start); E_FAR + k - 1 stands for the byte k (1..32768) positions before the
 // round start, read back from the chunk's committed output.
-constexpr u32 E_VAL = 0xFF00u;
+constexpr u32 E_VAL = SE_VAL;
 constexpr u32 E_FAR = 0x4000u;
 static_assert(PI_STAGE <= E_FAR && E_FAR + PI_WIN <= E_VAL, "stage entry encoding");
 __device__ __forceinline__ bool e_val(u32 v) { return v >= E_VAL; }
@@ -158,19 +147,19 @@ __device__ __forceinline__ u32 decode_token(const ParLds& L, u64 v, u32* adv) {
     const u32 l = e >> 28;
     const u32 kind = (e >> 24) & 15;
     if (kind == K_LIT) { *adv = l; return (l << 24) | (e & 0xFF); }
-    if (kind == K_EOB) { *adv = l; return T_EOB; }
-    if (kind != K_LEN) { *adv = l ? l : 1; return T_BAD; }
+    if (kind == K_EOB) { *adv = l; return W_EOB; }
+    if (kind != K_LEN) { *adv = l ? l : 1; return W_BAD; }
     const u32 ex = (e >> 16) & 0xFF;
     const u32 len = (e & 0xFFFF) + ((u32)(v >> l) & ((1u << ex) - 1));
     const u32 t = l + ex;
     const u64 vd = v >> t;
     const u32 de = table_lookup(L.dtab, INF_DBITS, (u32)vd);
     const u32 dl = de >> 28;
-    if (((de >> 24) & 15) != K_DIST) { *adv = t + (dl ? dl : 1); return T_BAD; }
+    if (((de >> 24) & 15) != K_DIST) { *adv = t + (dl ? dl : 1); return W_BAD; }
     const u32 dex = (de >> 16) & 0xFF;
     const u32 dist = (de & 0xFFFF) + ((u32)(vd >> dl) & ((1u << dex) - 1));
     *adv = t + dl + dex;
-    return T_MATCH | ((t + dl + dex) << 24) | ((len - 3) << 16) | (dist - 1);
+    return W_MATCH | ((t + dl + dex) << 24) | ((len - 3) << 16) | (dist - 1);
 }
 
 // decode_token without control flow on the token kind: both table lookups
@@ -191,11 +180,11 @@ __device__ __forceinline__ u32 decode_token_fast(const ParLds& L, u64 v, u32* ad
     const u32 dist = (de & 0xFFFF) + ((u32)(vd >> dl) & ((1u << dex) - 1));
     const u32 madv = t + dl + dex;
     const bool dok = ((de >> 24) & 15) == K_DIST;
-    u32 tk = T_BAD, a = l ? l : 1;
+    u32 tk = W_BAD, a = l ? l : 1;
     if (kind == K_LIT) { tk = (l << 24) | (e & 0xFF); a = l; }
-    if (kind == K_EOB) tk = T_EOB;
+    if (kind == K_EOB) tk = W_EOB;
     if (kind == K_LEN) {
-        tk = dok ? (T_MATCH | (madv << 24) | ((len - 3) << 16) | (dist - 1)) : T_BAD;
+        tk = dok ? (W_MATCH | (madv << 24) | ((len - 3) << 16) | (dist - 1)) : W_BAD;
         a = dok ? madv : t + (dl ? dl : 1);
     }
     *adv = a;
@@ -254,43 +243,9 @@ __device__ __forceinline__ void lb_drop(LaneBits& s, u32 k) {  // 0 < k <= 48
 // pos & mask.  The trailing barrier makes the bytes visible to the next
 // round's window reads (same workgroup, same CU).
 __device__ void par_commit(ParLds& L, u8* dst, u64 from, u64 to, DType t) {
-    const u32 tid = threadIdx.x;
     __syncthreads();
-    const u64 a16 = (from + 15) & ~15ull, b16 = to & ~15ull;
-    if (a16 < b16) {
-        for (u64 p = a16 + (u64)tid * 16; p < b16; p += PI_NL * 16) {
-            const u32 i = (u32)(p & (PI_STAGE - 1));
-            const u32x4 lo = *(const u32x4*)(L.ptr + i);
-            const u32x4 hi = *(const u32x4*)(L.ptr + i + 8);
-            // each u32 holds two 16-bit entries; keep their low bytes
-            auto pk = [](u32 a, u32 b) -> u32 {
-                return __builtin_amdgcn_perm(b, a, 0x06040200u);
-            };
-            const u32x4 v = u32x4{pk(lo.x, lo.y), pk(lo.z, lo.w), pk(hi.x, hi.y), pk(hi.z, hi.w)};
-            st16(dst + p, transform16(v, t));
-        }
-    }
-    const u64 e0 = a16 < b16 ? a16 : to;
-    for (u64 q = from + tid; q < e0; q += PI_NL) dst[swap_pos(q, t)] = (u8)L.ptr[q & (PI_STAGE - 1)];
-    if (a16 < b16)
-        for (u64 q = b16 + tid; q < to; q += PI_NL) dst[swap_pos(q, t)] = (u8)L.ptr[q & (PI_STAGE - 1)];
+    stage_commit<PI_NL>(L.ptr, dst, from, to, t, threadIdx.x, [](u64 q) -> u32 { return (u32)(q & (PI_STAGE - 1)); });
     __syncthreads();
-}
-
-// Bool arrays: byte != 0 over the whole decoded chunk, after the last round.
-__device__ void par_bool_norm(u8* dst, u64 D) {
-    __syncthreads();
-    const u32 tid = threadIdx.x;
-    const bool al = (((uintptr_t)dst) & 15) == 0;
-    for (u64 p = (u64)tid * 16; p < D; p += PI_NL * 16) {
-        if (p + 16 <= D) {
-            u32x4 v = al ? *(u32x4*)(dst + p) : ld16(dst + p);
-            v.x = bool_norm32(v.x); v.y = bool_norm32(v.y); v.z = bool_norm32(v.z); v.w = bool_norm32(v.w);
-            if (al) *(u32x4*)(dst + p) = v; else st16(dst + p, v);
-        } else {
-            for (u64 q = p; q < D; q++) dst[q] = dst[q] != 0;
-        }
-    }
 }
 
 // Block-wide exclusive scan over 256 lanes; *total receives the sum.
@@ -379,13 +334,7 @@ __device__ __attribute__((always_inline)) int read_dynamic_par(ParLds& L, BitIn&
     // hw [27648, 28256), gpos [28256, 28768), srec [28768, 30048)
     u32* hw = (u32*)(L.ptr + 3 * HD_BITS);
     for (u32 w = tid; w < HD_WORDS; w += PI_NL) {
-        const u64 q = B0 + 4ull * w;
-        u32 v = 0;
-        if (q + 4 <= b.n) v = ld32(b.src + q);
-        else
-            for (u32 k = 0; k < 4; k++)
-                if (q + k < b.n) v |= (u32)b.src[q + k] << (8 * k);
-        hw[w] = v;
+        hw[w] = ld_tail<u32_ua>(b.src, B0 + 4ull * w, b.n);
     }
     build_table(L.lens, 19, &L.lh, L.ltab, 7, false, INF_LTAB);  // barriers inside
     // one record per bit position: adv | codelen << 4 | sym << 7 (the repeat
@@ -499,26 +448,6 @@ __device__ __attribute__((always_inline)) int read_dynamic_par(ParLds& L, BitIn&
     return R_OK;
 }
 
-// read_block_header with the block-parallel dynamic header
-__device__ __attribute__((always_inline)) int read_block_header_par(ParLds& L, BitIn& b, bool* last, u32* type, u32* slen, bool dbg) {
-    if (!bi_has(b, 3)) return R_EXHAUSTED;
-    const u32 hdr = bi_bits(b, 3);
-    *last = hdr & 1;
-    *type = hdr >> 1;
-    if (*type == 0) {
-        const u32 pad = (u32)((8 - (b.consumed & 7)) & 7);  // to byte boundary
-        if (!bi_has(b, pad + 32)) return R_EXHAUSTED;
-        bi_bits(b, pad);
-        const u32 len = bi_bits(b, 16), nlen = bi_bits(b, 16);
-        if ((len ^ 0xFFFF) != nlen) return R_INVALID;  // "invalid stored block lengths"
-        *slen = len;
-        return R_OK;
-    }
-    if (*type == 3) return R_INVALID;  // "invalid block type"
-    if (*type == 1) { fixed_tables(L.lens, &L.lh, L.ltab, &L.dh, L.dtab); return R_OK; }
-    return read_dynamic_par(L, b, dbg);
-}
-
 __global__ __launch_bounds__(PI_NL, ZCG_INF_WPE) void inflate_par_kernel(const zcg_chunk* __restrict__ chunks,
                                                                u32 n, u64 D, DType t, u32 vflags,
                                                                i32* __restrict__ status,
@@ -530,29 +459,21 @@ __global__ __launch_bounds__(PI_NL, ZCG_INF_WPE) void inflate_par_kernel(const z
     const u32 tid = threadIdx.x;
     const bool dbg = (vflags & ZCG_FLAG_DEBUG_COUNTERS) != 0;
     const zcg_chunk ch = chunks[c];
-    if (D == 0) { if (tid == 0) status[c] = ZCG_OK; return; }
-    if (ch.dst_cap < D) { if (tid == 0) status[c] = ZCG_ERR_INVALID_INPUT; return; }
-    const u8* s = (const u8*)ch.src;
-    const u64 n_in = ch.src_len;
-    u64 h = 0;
-    int st = gzip_header(s, n_in, &h);
-    if (st == ZCG_OK && n_in - h >= (1ull << 28)) st = ZCG_ERR_UNSUPPORTED;  // u32 bit positions
-    if (st != ZCG_OK) { if (tid == 0) status[c] = st; return; }
+    InfMember m;
+    int st;
+    bool open = inf_open(ch, D, t, m, &st);
+    if (open && m.n_ds >= (1ull << 28)) { st = ZCG_ERR_UNSUPPORTED; open = false; }  // u32 bit positions
+    if (!open) { if (tid == 0) status[c] = st; return; }
 
-    u8* dst = (u8*)ch.dst;
-    const u8* ds = s + h;  // deflate stream
-    DType tw = t;  // commit transform: bool waits for the end (the output is the window)
-    tw.isbool = 0;
+    u8* const dst = m.dst;
+    const u8* const ds = m.ds;  // deflate stream
+    const u64 n_ds = m.n_ds;
+    const DType tw = m.tw;
     // take a token slot (released at the end; every path below reaches it)
-    if (tid == 0) {
-        u32 sl = c % PI_NSLOT;
-        while (atomicCAS(&owner[sl], 0u, 1u) != 0u) sl = (sl + 1) % PI_NSLOT;
-        L.ctl[15] = sl;
-    }
+    if (tid == 0) L.ctl[15] = slot_take(owner, PI_NSLOT, c);
     __syncthreads();
     const u32 slot = L.ctl[15];
     gu32* const gp = pools + (u64)slot * PI_SLOT_WORDS;
-    const u64 n_ds = n_in - h;
     const u32 total_bits = (u32)(n_ds * 8);
     // Every wave runs the wave-uniform header/look-ahead code redundantly on
     // the same data (block barriers inside), each with its own LDS cache.
@@ -574,28 +495,20 @@ __global__ __launch_bounds__(PI_NL, ZCG_INF_WPE) void inflate_par_kernel(const z
         // ---- block header (all waves, identical) ------------------------------------
         if (last) { r = R_EXHAUSTED; break; }
         u32 type = 0, slen = 0;
-        r = read_block_header_par(L, b, &last, &type, &slen, dbg);
+        r = read_block_header(b, &last, &type, &slen, L.lens, &L.lh, L.ltab, &L.dh, L.dtab,
+                              [&](BitIn& bb) __attribute__((always_inline)) { return read_dynamic_par(L, bb, dbg); });
         const u32 hdr_end = (u32)b.consumed;
         TSTAMP(TP_HDR);
         if (r != R_OK) break;
         if (dbg && tid == 0) DBG_ADD(DBG_BLOCKS, 1);
         if (type == 0) {
             // ---- stored block: byte copies through the stage --------------------
-            u64 in0 = hdr_end >> 3;  // byte aligned after LEN/NLEN
-            u32 done = 0;
-            while (done < slen && P < D) {
-                u32 k = slen - done;
-                if (k > PI_STAGE) k = PI_STAGE;
-                if ((u64)k > D - P) k = (u32)(D - P);
-                if (in0 + k > n_ds) { r = R_EXHAUSTED; break; }
-                for (u32 i = tid; i < k; i += PI_NL)
-                    L.ptr[(P + i) & (PI_STAGE - 1)] = (u16)(E_VAL | ds[in0 + i]);
-                par_commit(L, dst, P, P + k, tw);
-                P += k; in0 += k; done += k;
-            }
+            u64 in_end = 0;
+            r = inf_stored_copy<PI_NL>(m, hdr_end >> 3 /* byte aligned after LEN/NLEN */, slen, P, D, PI_STAGE, L.ptr, tid,
+                                       [](u64 P0, u32 i) -> u32 { return (u32)((P0 + i) & (PI_STAGE - 1)); },
+                                       [&](u64 from, u64 to) { par_commit(L, dst, from, to, tw); }, &in_end, &boundary);
             if (r != R_OK) break;
-            bi_seek(b, in0 * 8);
-            boundary = (done == slen);
+            bi_seek(b, in_end * 8);
             after_stored = true;
             continue;
         }
@@ -611,20 +524,8 @@ __global__ __launch_bounds__(PI_NL, ZCG_INF_WPE) void inflate_par_kernel(const z
 #pragma unroll
                 for (u32 k = 0; k < (PI_IN_VEC + PI_NL - 1) / PI_NL; k++) {
                     const u32 vi = tid + k * PI_NL;
-                    const u64 q = byte0 + 16ull * vi;
                     u32x4 x = {0u, 0u, 0u, 0u};
-                    if (vi < PI_IN_VEC) {
-                        if (q + 16 <= n_ds) x = ld16(ds + q);
-                        else {
-                            u64 lo = 0, hi = 0;
-                            for (u32 i = 0; i < 16; i++)
-                                if (q + i < n_ds) {
-                                    const u64 b8 = (u64)ds[q + i] << (8 * (i & 7));
-                                    if (i < 8) lo |= b8; else hi |= b8;
-                                }
-                            x = u32x4{(u32)lo, (u32)(lo >> 32), (u32)hi, (u32)(hi >> 32)};
-                        }
-                    }
+                    if (vi < PI_IN_VEC) x = ld_tail<u32x4_ua>(ds, byte0 + 16ull * vi, n_ds);
                     v[k] = x;
                 }
 #pragma unroll
@@ -655,19 +556,19 @@ __global__ __launch_bounds__(PI_NL, ZCG_INF_WPE) void inflate_par_kernel(const z
                 if (nt == PI_TMAX) return false;
                 gp[nt * PI_NL + tid] = tk;
                 nt++;
-                olen_all += tok_len(tk);
+                olen_all += w_len_tok(tk);  // (a trailing marker counts 1 here: taken off at placement)
                 return true;
             };
             while (q < pend) {
                 lb_fill(bs, L.in);
                 u32 adv;
                 u32 tk = decode_token_fast(L, bs.lo, &adv);
-                if (q + adv > total_bits) tk = T_EXH;
+                if (q + adv > total_bits) tk = W_EXH;
                 if (!push(tk)) { nxt = N_CAP; break; }
                 const u32 off = q - p;
                 atomicOr(&mymark[off >> 5], 1u << (off & 31));
-                if (tok_is_marker(tk)) {
-                    if (tk == T_EOB) q += adv;
+                if (w_marker(tk)) {
+                    if (tk == W_EOB) q += adv;
                     nxt = N_MARKER;
                     break;
                 }
@@ -696,11 +597,11 @@ __global__ __launch_bounds__(PI_NL, ZCG_INF_WPE) void inflate_par_kernel(const z
                     give = cnt;
                     break;
                 }
-                if (q + adv > total_bits) tk = T_EXH;
+                if (q + adv > total_bits) tk = W_EXH;
                 if (!push(tk)) { nxt = N_CAP; break; }
                 p2tok++;
-                if (tok_is_marker(tk)) {
-                    if (tk == T_EOB) q += adv;
+                if (w_marker(tk)) {
+                    if (tk == W_EOB) q += adv;
                     nxt = N_MARKER;
                     break;
                 }
@@ -780,7 +681,7 @@ __global__ __launch_bounds__(PI_NL, ZCG_INF_WPE) void inflate_par_kernel(const z
                 DBG_ADD(DBG_CHAIN, E + 1);
                 const u32 nx = L.next[E];
                 DBG_ADD(nx == N_CAP ? DBG_END_CAP : nx == N_ROUND_END ? DBG_END_ROUND
-                        : (tok_at(gp, E, L.ntok[E] - 1) == T_EOB ? DBG_END_EOB : DBG_END_BAD), 1);
+                        : (tok_at(gp, E, L.ntok[E] - 1) == W_EOB ? DBG_END_EOB : DBG_END_BAD), 1);
                 u32 sk = 0;
                 for (u32 x = 0; x < E; x++) sk += L.next[x] != x + 1;
                 DBG_ADD(DBG_SKIPS, sk);
@@ -798,14 +699,14 @@ __global__ __launch_bounds__(PI_NL, ZCG_INF_WPE) void inflate_par_kernel(const z
                 olen = olen_all - (vend < nt ? 1u : 0u);
 #pragma unroll
                 for (u32 u = 0; u < PF; u++)
-                    if (u < my_s) olen -= tok_len(pre[u]);
+                    if (u < my_s) olen -= w_len_tok(pre[u]);
                 for (u32 a0 = PF; a0 < my_s; a0 += 4) {
                     u32 tk4[4];
 #pragma unroll
                     for (u32 u = 0; u < 4; u++) tk4[u] = a0 + u < my_s ? tok_at(gp, tid, a0 + u) : 0u;
 #pragma unroll
                     for (u32 u = 0; u < 4; u++)
-                        if (a0 + u < my_s) olen -= tok_len(tk4[u]);
+                        if (a0 + u < my_s) olen -= w_len_tok(tk4[u]);
                 }
             }
             u32 total;
@@ -832,14 +733,14 @@ __global__ __launch_bounds__(PI_NL, ZCG_INF_WPE) void inflate_par_kernel(const z
                     bool go = true;
 #pragma unroll
                     for (u32 u = 0; u < PF; u++) {
-                        if (u < my_s) sb += tok_bits(pre[u]);
+                        if (u < my_s) sb += w_bits(pre[u]);
                         if (go && u >= my_s && u < vend) {  // a == u here
-                            const u32 len = tok_len(pre[u]);
+                            const u32 len = w_len_tok(pre[u]);
                             if (cap == room ? acc >= cap : acc + len > cap) go = false;
-                            else { acc += len; sb += tok_bits(pre[u]); a++; }
+                            else { acc += len; sb += w_bits(pre[u]); a++; }
                         }
                     }
-                    for (u32 j = PF; j < my_s; j++) sb += tok_bits(tok_at(gp, tid, j));  // rare
+                    for (u32 j = PF; j < my_s; j++) sb += w_bits(tok_at(gp, tid, j));  // rare
                     while (go && a < vend) {
                         u32 tk8[8];
 #pragma unroll
@@ -847,9 +748,9 @@ __global__ __launch_bounds__(PI_NL, ZCG_INF_WPE) void inflate_par_kernel(const z
 #pragma unroll
                         for (u32 u = 0; u < 8; u++) {
                             if (go && a < vend) {  // while go holds, a == (a at the load) + u
-                                const u32 len = tok_len(tk8[u]);
+                                const u32 len = w_len_tok(tk8[u]);
                                 if (cap == room ? acc >= cap : acc + len > cap) go = false;
-                                else { acc += len; sb += tok_bits(tk8[u]); a++; }
+                                else { acc += len; sb += w_bits(tk8[u]); a++; }
                             }
                         }
                     }
@@ -873,8 +774,8 @@ __global__ __launch_bounds__(PI_NL, ZCG_INF_WPE) void inflate_par_kernel(const z
                 round_end = L.ctl[11];
             }
             // ---- errors on the taken range ----------------------------------------------------
-            if (mk == T_BAD) { r = R_INVALID; break; }
-            if (mk == T_EXH) { r = R_EXHAUSTED; break; }
+            if (mk == W_BAD) { r = R_INVALID; break; }
+            if (mk == W_EXH) { r = R_EXHAUSTED; break; }
             // ---- token heads: one entry per taken token ----------------------------------
             // literal -> E_VAL|byte (final); match -> dist-1 at its first byte,
             // plus a token-start bit in head[] over the round's output bytes.
@@ -886,11 +787,11 @@ __global__ __launch_bounds__(PI_NL, ZCG_INF_WPE) void inflate_par_kernel(const z
                 auto put = [&](u32 tk) {
                     u16 v;
                     u32 len;
-                    if (tk & T_MATCH) {
-                        const u32 d = tok_dist(tk);
+                    if (tk & W_MATCH) {
+                        const u32 d = w_dist(tk);
                         if (d > P + o) far = true;  // before the stream start
                         v = (u16)(d - 1);
-                        len = tok_len(tk);
+                        len = w_len_tok(tk);
                     } else {
                         v = (u16)(E_VAL | (tk & 0xFF));
                         len = 1;
@@ -1026,27 +927,19 @@ __global__ __launch_bounds__(PI_NL, ZCG_INF_WPE) void inflate_par_kernel(const z
                 bi_seek(b, round_end);
                 break;
             }
-            if (mk == T_EOB) {
+            if (mk == W_EOB) {
                 block_end = true;
                 bi_seek(b, round_end);  // bit after the EOB code
             }
             R0 = round_end;
         }
     }
-    // zlib's post-N look-ahead (all waves, identical); see zcg_inflate_common.h
-    if (r == R_OK && P >= D && boundary) {
-        const u64 last_byte = h + (b.consumed ? (b.consumed - 1) / 8 : 0);
-        u64 wend = (last_byte / 32768 + 1) * 32768;
-        if (wend > n_in) wend = n_in;
-        b.limit = (wend - h) * 8;
-        if (b.limit >= b.consumed) {
-            const int la = inf_lookahead(b, last, after_stored, L.lens, &L.lh, L.ltab, &L.dh, L.dtab);
-            if (la == R_INVALID) r = R_INVALID;
-        }
+    // zlib's post-N look-ahead (all waves, identical)
+    st = inf_close(b, m, r, P, D, boundary, last, after_stored, L.lens, &L.lh, L.ltab, &L.dh, L.dtab);
+    if (t.isbool) {  // byte != 0 over the whole decoded chunk, after the last round
+        __syncthreads();
+        wave_transform<PI_NL>(dst, P < D ? P : D, DType{1, 0, 1}, tid);
     }
-    if (r == R_INVALID) st = ZCG_ERR_INVALID_DATA;
-    else if (r == R_EXHAUSTED || P < D) st = ZCG_ERR_UNEXPECTED_EOF;
-    if (t.isbool) par_bool_norm(dst, P < D ? P : D);
     if (dbg) {
         if (tid == 0) L.dbgc[TP_TOTAL] = (u32)(__builtin_readcyclecounter() - t_start);
         __syncthreads();
@@ -1055,7 +948,7 @@ __global__ __launch_bounds__(PI_NL, ZCG_INF_WPE) void inflate_par_kernel(const z
     __syncthreads();  // every token-slot access of this workgroup is done
     if (tid == 0) {
         status[c] = st;
-        atomicExch(&owner[slot], 0u);
+        slot_free(owner, slot);
     }
 }
 

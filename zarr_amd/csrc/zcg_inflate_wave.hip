@@ -56,21 +56,6 @@
 #ifndef ZIW_EST_PCT
 #define ZIW_EST_PCT 108
 #endif
-#ifndef ZIW_STEADY
-#define ZIW_STEADY 1  // 0: pass 1 always runs the edge body (A/B of the steady body)
-#endif
-#ifndef ZIW_MKFENCE
-#define ZIW_MKFENCE 1  // 0: no wave fence between a near batch's marker clear and the marker writes (a
-                       // wave's LDS stores are performed in issue order; A/B)
-#endif
-#ifndef ZIW_P2FLAT
-#define ZIW_P2FLAT 0  // 1: pass 2's step as one predicated region with a stop code instead of the
-                      // continue chain (A/B)
-#endif
-#ifndef ZIW_SUBSEL
-#define ZIW_SUBSEL 0  // 1: the subtable look-ups are unconditional second reads (index 0 when the
-                      // entry is no link) and a select, instead of a read under a branch (A/B)
-#endif
 #ifndef ZIW_DBG
 #define ZIW_DBG 0  // 1: debug counters compiled in (ZCG_FLAG_DEBUG_COUNTERS; tools/iw_stats.py cycle
                    // shares).  Out by default: their checks cost 1.4 % of the C2 launch (22.05 -> 21.74 ms)
@@ -111,18 +96,7 @@ static_assert(IW_MARKW + IW_MWIN <= IW_MWORDS, "mark window inside the bitmap");
 constexpr u32 IW_EST0 = 64 * 3072;  // first block's body estimate (zlib-6 blocks: ~195 Kbit)
 static_assert(IW_S == 2048 && IW_BLK == 32, "the L phase keeps one 32-entry block per lane in registers");
 
-// token word (same layout as zcg_inflate_par.hip, plus bit lengths on markers):
-//   literal  = bits << 24 | byte
-//   match    = 1 << 31 | bits << 24 | (len - 3) << 16 | (dist - 1)
-//   marker   = 1 << 30 | bits << 24 | code   (EOB / invalid code / input exhausted)
-// bits = the token's stream bits (<= 48), so a token's start is the lane's
-// segment start plus the bits of the tokens before it in the lane's list.
-constexpr u32 W_MATCH = 0x80000000u;
-constexpr u32 W_MARK = 0x40000000u;
-enum : u32 { M_EOB = 0, M_BAD = 1, M_EXH = 2, M_END = 3 /* synthetic: no more tokens in the round */ };
-__device__ __forceinline__ bool w_marker(u32 t) { return (t & 0xC0000000u) == W_MARK; }
-__device__ __forceinline__ u32 w_bits(u32 t) { return (t >> 24) & 63; }
-__device__ __forceinline__ u32 w_len(u32 t) { return (t & W_MATCH) ? ((t >> 16) & 0xFF) + 3 : (w_marker(t) ? 0u : 1u); }
+// (token word: zcg_inflate_word.h; this kernel's markers carry their bit length)
 
 // lane stop codes (>= 64)
 constexpr u32 S_NONE = 0xFFFFFFFFu;
@@ -132,7 +106,7 @@ constexpr u32 S_CAP = 66;        // token list full
 
 // stage entries (u16): IE_VAL|byte = a final byte; a value below IW_S = the
 // ring index of an earlier byte of the stage (a near byte not yet resolved)
-constexpr u32 IE_VAL = 0xFF00u;
+constexpr u32 IE_VAL = SE_VAL;
 static_assert(IW_S <= IE_VAL, "stage entry encoding");
 
 // Table geometry: a 9-bit literal/length root (zlib's ENOUGH_LENS = 852
@@ -279,53 +253,10 @@ __device__ __forceinline__ void gr_init(GRd& s, const u8* base, u32 nvec, u32 qa
 }
 
 // ---- token-ready tables ---------------------------------------------------------
-// build_table lays entries out for the serial reader (l << 28 | kind << 24 |
-// ex << 16 | value), and a token word would have to be put together from
-// those fields once per token.  After the header of a Huffman block one wave
-// pass rewrites both tables in place into a layout private to this kernel
-// (852 + 432 entries per block against 16 383 tokens), tagged like a token
-// word by bits 31:30:
-//   ltab  literal   l << 24 | byte                          (the token word)
-//         EOB / bad W_MARK | l << 24 | M_EOB / M_BAD        (the token word)
-//         length    W_MATCH | (l + ex) << 24 | (base - 3) << 16 | ex << 8 | l
-//         link      T_SUB | offset << 8 | subtable bits
-//   dtab  distance  (dl + dex) << 24 | dex << 20 | dl << 16 | (base - 1)
-//         bad       W_MARK | dl << 24 | M_BAD
-//         link      as above
-// Every reachable entry of the serial layout has exactly one image (literals
-// carry no extra bits and a value < 256, a code length is >= 1 except on a
-// link, base - 3 + extra <= 255, base - 1 < 2^15), so iw_tab_serial() gives
-// the serial entries back exactly: zlib's look-ahead (inf_lookahead) decodes
-// with these same tables in the serial layout when the output fills inside a
-// block.
-constexpr u32 T_SUB = 0xC0000000u;
-__device__ __forceinline__ u32 iw_l_wave(u32 e) {
-    const u32 l = e >> 28, kind = (e >> 24) & 15, ex = (e >> 16) & 0xFF, val = e & 0xFFFF;
-    if (kind == K_LIT) return (l << 24) | (val & 0xFF);
-    if (kind == K_EOB) return W_MARK | (l << 24) | M_EOB;
-    if (kind == K_LEN) return W_MATCH | ((l + ex) << 24) | (((val - 3) & 0xFF) << 16) | ((ex & 7) << 8) | l;
-    if (kind == K_SUB) return T_SUB | (val << 8) | (ex & 31);
-    return W_MARK | (l << 24) | M_BAD;
-}
-__device__ __forceinline__ u32 iw_l_serial(u32 x) {
-    const u32 tag = x >> 30, l = (x >> 24) & 15;
-    if (tag == 0) return mk_entry(l, K_LIT, 0, x & 0xFF);
-    if (tag == 1) return mk_entry(l, (x & 3) == M_EOB ? K_EOB : K_BAD, 0, 0);
-    if (tag == 2) return mk_entry(x & 15, K_LEN, (x >> 8) & 7, ((x >> 16) & 0xFF) + 3);
-    return mk_entry(0, K_SUB, x & 31, (x >> 8) & 0xFFFF);
-}
-__device__ __forceinline__ u32 iw_d_wave(u32 e) {
-    const u32 l = e >> 28, kind = (e >> 24) & 15, ex = (e >> 16) & 0xFF, val = e & 0xFFFF;
-    if (kind == K_DIST) return ((l + ex) << 24) | ((ex & 15) << 20) | (l << 16) | ((val - 1) & 0x7FFF);
-    if (kind == K_SUB) return T_SUB | (val << 8) | (ex & 31);
-    return W_MARK | (l << 24) | M_BAD;
-}
-__device__ __forceinline__ u32 iw_d_serial(u32 x) {
-    const u32 tag = x >> 30;
-    if (tag == 0) return mk_entry((x >> 16) & 15, K_DIST, (x >> 20) & 15, (x & 0x7FFF) + 1);
-    if (tag == 1) return mk_entry((x >> 24) & 15, K_BAD, 0, 0);
-    return mk_entry(0, K_SUB, x & 31, (x >> 8) & 0xFFFF);
-}
+// The entry maps iw_l_wave / iw_d_wave and their inverses are in
+// zcg_inflate_word.h: one wave pass after a Huffman block's header rewrites
+// both tables in place (852 + 432 entries per block against 16 383 tokens), and
+// iw_tab_serial() gives the serial entries back for zlib's look-ahead.
 // (whole tables: the words past a block's last subtable are never looked up)
 __device__ void iw_tab_wave(IwLds& L) {
     const u32 lane = (u32)lane_id();
@@ -350,27 +281,13 @@ __device__ void iw_tab_serial(IwLds& L) {
 __device__ __forceinline__ u32 iw_decode(const IwLds& L, u64 v) {
     const u32 v0 = (u32)v;
     u32 e = L.ltab[v0 & ((1u << W_LB) - 1)];
-#if ZIW_SUBSEL
-    {
-        const u32 e2 = L.ltab[e >= T_SUB ? ((e >> 8) & 0xFFFF) + __builtin_amdgcn_ubfe(v0, (u32)W_LB, e) : 0u];
-        e = e >= T_SUB ? e2 : e;
-    }
-#else
     if (e >= T_SUB) e = L.ltab[((e >> 8) & 0xFFFF) + __builtin_amdgcn_ubfe(v0, (u32)W_LB, e)];
-#endif
     // 32-bit fields only: the length code and its extra bits end by bit 20,
     // and the distance code and its extra bits take <= 28 bits from t
     const u32 t = (e >> 24) & 63;  // (a length entry: l + ex)
     const u32 vd = __builtin_amdgcn_alignbit((u32)(v >> 32), v0, t);
     u32 de = L.dtab[vd & ((1u << W_DB) - 1)];
-#if ZIW_SUBSEL
-    {
-        const u32 d2 = L.dtab[de >= T_SUB ? ((de >> 8) & 0xFFFF) + __builtin_amdgcn_ubfe(vd, (u32)W_DB, de) : 0u];
-        de = de >= T_SUB ? d2 : de;
-    }
-#else
     if (de >= T_SUB) de = L.dtab[((de >> 8) & 0xFFFF) + __builtin_amdgcn_ubfe(vd, (u32)W_DB, de)];
-#endif
     const u32 lenx = __builtin_amdgcn_ubfe(v0, e, e >> 8);
     const u32 distx = __builtin_amdgcn_ubfe(vd, (de >> 16) & 15, (de >> 20) & 15);
     // the length's bits on top of the distance entry: the bad-distance marker
@@ -427,42 +344,12 @@ __device__ __forceinline__ u32 iw_pos(const gu32* gl, u32 lm, u32 j, u32 seg0) {
 // q - (S & ~15): 16-byte-aligned output pieces are 16-entry-aligned in the
 // ring, and a stage of at most IW_S - 16 bytes never wraps.
 __device__ void iw_commit(IwLds& L, u8* dst, u64 from, u64 to, DType t) {
-    const u32 lane = (u32)lane_id();
     wsync();
     const u64 base = from & ~15ull;
-    const u64 a16 = (from + 15) & ~15ull, b16 = to & ~15ull;
-    if (a16 < b16) {
-        for (u64 p = a16 + (u64)lane * 16; p < b16; p += 64 * 16) {
-            const u32 i = (u32)(p - base);
-            const u32x4 lo = *(const u32x4*)(L.u.st.ptr + i);
-            const u32x4 hi = *(const u32x4*)(L.u.st.ptr + i + 8);
-            auto pk = [](u32 a, u32 b) -> u32 { return __builtin_amdgcn_perm(b, a, 0x06040200u); };
-            const u32x4 v = u32x4{pk(lo.x, lo.y), pk(lo.z, lo.w), pk(hi.x, hi.y), pk(hi.z, hi.w)};
-            st16(dst + p, transform16(v, t));
-        }
-    }
-    const u64 e0 = a16 < b16 ? a16 : to;
-    for (u64 q = from + lane; q < e0; q += 64) dst[swap_pos(q, t)] = (u8)L.u.st.ptr[q - base];
-    if (a16 < b16)
-        for (u64 q = b16 + lane; q < to; q += 64) dst[swap_pos(q, t)] = (u8)L.u.st.ptr[q - base];
+    stage_commit<64>(L.u.st.ptr, dst, from, to, t, (u32)lane_id(), [base](u64 q) -> u32 { return (u32)(q - base); });
     // the next stage's far reads come back through this CU's L1/L2: wait
     // for the stores (same-CU stores refresh the L1)
     __syncthreads();
-}
-
-__device__ void iw_bool_norm(u8* dst, u64 D) {
-    __syncthreads();
-    const u32 lane = (u32)lane_id();
-    const bool al = (((uintptr_t)dst) & 15) == 0;
-    for (u64 p = (u64)lane * 16; p < D; p += 64 * 16) {
-        if (p + 16 <= D) {
-            u32x4 v = al ? *(u32x4*)(dst + p) : ld16(dst + p);
-            v.x = bool_norm32(v.x); v.y = bool_norm32(v.y); v.z = bool_norm32(v.z); v.w = bool_norm32(v.w);
-            if (al) *(u32x4*)(dst + p) = v; else st16(dst + p, v);
-        } else {
-            for (u64 q = p; q < D; q++) dst[q] = dst[q] != 0;
-        }
-    }
 }
 
 #define IW_T(slot)                                                              \
@@ -515,14 +402,7 @@ __device__ __attribute__((always_inline)) int read_dynamic_wave(BitIn& b, u8* le
     // walk below waits on LDS, not on a global round trip per window.
     const u64 wb = (b.consumed >> 3) & ~7ull;  // window base byte
     {
-        const u64 by = wb + 8ull * lane;
-        u64 w = 0;
-        if (by + 8 <= nbytes) {
-            w = *(const gu64_ua*)(src + by);
-        } else {
-            for (u32 k = 0; k < 8; k++)
-                if (by + k < nbytes) w |= (u64)src[by + k] << (8 * k);
-        }
+        const u64 w = ld_tail<gu64_ua>(src, wb + 8ull * lane, nbytes);
         hwin[2 * lane] = (u32)w;
         hwin[2 * lane + 1] = (u32)(w >> 32);
         if (lane < 2) hwin[128 + lane] = 0;
@@ -536,11 +416,7 @@ __device__ __attribute__((always_inline)) int read_dynamic_wave(BitIn& b, u8* le
             const u64 x = ((u64)hwin[wi + 1] << 32) | hwin[wi];
             return (u32)(x >> (r & 31));
         }
-        const u64 by = q >> 3;
-        u64 w = 0;
-        for (u32 k = 0; k < 8; k++)
-            if (by + k < nbytes) w |= (u64)src[by + k] << (8 * k);
-        return (u32)(w >> (q & 7));
+        return (u32)(ld_tail<gu64_ua>(src, q >> 3, nbytes) >> (q & 7));
     };
     // the 3-bit code-length code lengths: lane i < ncode reads its own field
     const u64 c0 = b.consumed;
@@ -641,27 +517,262 @@ __device__ __attribute__((always_inline)) int read_dynamic_wave(BitIn& b, u8* le
     return R_OK;
 }
 
-template <int LB, u32 LCAP, int DB, u32 DCAP>
-__device__ __attribute__((always_inline)) int read_block_header_wave(BitIn& b, bool* last, u32* type, u32* slen,
-                                                                     u8* lens, HuffLds* lh, u32* ltab, HuffLds* dh,
-                                                                     u32* dtab, u32* hwin, u32* tcyc) {
-    if (!bi_has(b, 3)) return R_EXHAUSTED;
-    const u32 hdr = bi_bits(b, 3);
-    *last = hdr & 1;
-    *type = hdr >> 1;
-    if (*type != 2) {  // stored / fixed / invalid: the serial reader's rules
-        b.cbase = ~0ull;
-        bi_seek(b, b.consumed - 3);
-        return read_block_header<LB, LCAP, DB, DCAP>(b, last, type, slen, lens, lh, ltab, dh, dtab);
-    }
-    return read_dynamic_wave<LB, LCAP, DB, DCAP>(b, lens, lh, ltab, dh, dtab, hwin, tcyc);
-}
-
 constexpr u32 IW_NSLOT_MAX = 8192;
 constexpr u64 IW_LIST_WORDS = 64ull * IW_TSTR;              // token lists of a slot (u32)
 constexpr u64 IW_MARK_WORDS = 64ull * IW_MWORDS;            // token-start bitmaps of a slot (u32)
 constexpr u64 IW_SLOT_WORDS = IW_LIST_WORDS + IW_MARK_WORDS;
 constexpr u64 IW_OWNER_BYTES = IW_NSLOT_MAX * 4;
+
+// ---- H round ------------------------------------------------------------------------------------
+// One H round over the 64 segments of `seg` bits from stream bit R0: pass 1
+// (every lane decodes its own segment into its list and marks its token
+// starts), pass 2 (every lane follows its path on until it meets a marked
+// start of a later lane), and the chain of sync points from lane 0, which is
+// true by construction.
+// The result is all the L phase may take from a round:
+//   p      THIS round's segment start of the lane (R0 + lane * seg with the seg
+//          the round ran with)
+//   ncm    chain members; member m lives in lane m's chL / chS / chE = its
+//          lane, its first valid token, its list length
+//   endq   stream bit after the last member's list
+// `seg` comes back already halved for the NEXT round when the chain's last
+// list was capped, so positions of this round's tokens come from p only,
+// never from R0 + lane * seg.
+struct IwRound {
+    u32 p, ncm, chL, chS, chE, endq;
+};
+__device__ __attribute__((always_inline)) IwRound iw_h_round(IwLds& L, u32 R0, u32& seg, u32 total_bits,
+                                                             const u8* vbase, u32 nvec, u32 a0b, gu32* gl,
+                                                             gu32* marks, gu32* mk, bool dbg, u64& t_last) {
+    const u32 lane = threadIdx.x;
+    IW_ADD(IWD_ROUNDS, 1);
+    const u32 round_hi = R0 + 64 * seg;
+    const u32 p = R0 + lane * seg;
+    const u32 pend = p + seg;
+    u32 q = p, nt = 0, nxt = S_NONE, give = 0;
+    const bool active = p < total_bits;
+    GRd bs;
+    gr_init(bs, vbase, nvec, (active ? p : 0u) + a0b);
+    if (!active) {
+        if (lane == 0) {  // the block body starts at the stream end
+            gl[iw_ta(0, 0)] = W_EXH;
+            nt = 1;
+            nxt = S_MARKER;
+        } else {
+            nxt = S_ROUND_END;  // (never on the chain: the lane before it ends in EXH)
+        }
+    }
+    // pass 1: my segment; markers other than EXH do not stop it.  Each
+    // step stages its token and sets its start bit in an LDS window of
+    // IW_MWIN mark words; every IW_K steps all lanes flush both to the
+    // workspace with unconditional stores and refill the reader.
+    u32 it1 = 0, w0 = 0, nt0 = nt;
+#pragma unroll
+    for (u32 j = 0; j < IW_MWIN; j++) L.u.hr.mwin[j][lane] = 0;
+    bool run = nxt == S_NONE;
+    // flush of the staged tokens: the aligned block holding token nt0
+    // once it is complete (each block is stored once: its first words
+    // stay in the ring until then, <= 3 + IW_K < 8 entries)
+    auto flush_tokens = [&]() {
+        const u32 a0 = nt0 & ~3u, sb = a0 & 4u;
+        if (nt >= a0 + 4) {
+            *(gu32x4_a16*)(gl + iw_ta(lane, a0)) =
+                u32x4{L.u.hr.tst[sb][lane], L.u.hr.tst[sb + 1][lane], L.u.hr.tst[sb + 2][lane],
+                      L.u.hr.tst[sb + 3][lane]};
+            nt0 = nt;
+        }
+    };
+    while (__ballot(run) != 0) {
+      const u32x4 vC = gr_vec(vbase, nvec, bs.vc), vD = gr_vec(vbase, nvec, bs.vc + 1);
+      IW_ADD(IWD_P1_WIT, 1);
+      // Once per outer step, wave-uniformly: a running lane is on the
+      // edge if its list could fill, its stream could end (8 maximal
+      // tokens of 48 bits), or its mark window is still inside the
+      // IW_MARKW words that are ever read.  With no lane on the edge
+      // the steady body runs: no cap, exhausted or mark work at all.
+      const bool edge = run && (nt + IW_K * IW_KH > IW_TCAP || q + 48 * IW_K * IW_KH > total_bits ||
+                                w0 < IW_MARKW);
+      if (__ballot(edge) == 0) {
+        IW_ADD(IWD_P1_STEADY, 1);
+        for (u32 kh = 0; kh < IW_KH; kh++) {
+            for (u32 k = 0; k < IW_K; k++) {
+                // one predicated region per step: a lane idles when it is
+                // done or A:B ran dry (until the absorb below)
+                if (run && bs.bp <= 208) {
+                    gr_fill(bs);
+                    const u32 tk = iw_decode(L, bs.lo);
+                    const u32 adv = w_bits(tk);
+                    L.u.hr.tst[nt & (2 * IW_K - 1)][lane] = tk;
+                    nt++;
+                    gr_drop(bs, adv);
+                    q += adv;
+                    it1++;
+                    run = q < pend;
+                }
+            }
+            flush_tokens();
+        }
+        // no marks were set and the window was not moved: it holds
+        // nothing that is stored (w0 >= IW_MARKW), so only its position
+        // follows the lane, for an edge step that may come later
+        w0 = (q - p) >> 5;
+      } else {
+      for (u32 kh = 0; kh < IW_KH; kh++) {
+        for (u32 k = 0; k < IW_K; k++) {
+            if (!run || !gr_fill(bs)) continue;
+            u32 tk = iw_decode(L, bs.lo);
+            const u32 adv = w_bits(tk);
+            if (q + adv > total_bits) tk = W_EXH;
+            if (nt == IW_TCAP) { nxt = S_CAP; run = false; continue; }
+            L.u.hr.tst[nt & (2 * IW_K - 1)][lane] = tk;
+            nt++;
+            const u32 off = q - p;  // (<= 5 words past w0 within one flush period)
+            atomicOr(&L.u.hr.mwin[(off >> 5) - w0][lane], 1u << (off & 31));
+            if (tk == (W_EXH)) { nxt = S_MARKER; run = false; continue; }
+            gr_drop(bs, adv);
+            q += adv;
+            it1++;
+            if (q >= pend) run = false;
+        }
+        // flush: the staged tokens, then the mark window (words past my
+        // position are still zero)
+        flush_tokens();
+        u32 mv[IW_MWIN];
+#pragma unroll
+        for (u32 j = 0; j < IW_MWIN; j++) mv[j] = L.u.hr.mwin[j][lane];
+        // marks are kept for the first IW_MARKW words of the segment only
+        // (a misaligned decoder syncs within ~450 bits at p99); later
+        // flushes store nothing (stores to a dummy slot instead cost
+        // 14 GB of writes and 11 % of the time per C2 launch: the slot
+        // lines do not stay in L2 under 4 096 chunks' token lists)
+        // Only words w0 .. w1 (the word of my next token start) can hold
+        // marks yet, and w1 - w0 < 4 in almost every period: the second
+        // half of the window is stored only when the lane got that far
+        // (its zero words are stored when the window has slid onto them;
+        // pass 2 and iw_rank read no word past the marked extent)
+        const u32 w1 = (q - p) >> 5;
+        if (w0 < IW_MARKW) {
+            *(gu32x4_a4*)(mk + w0) = u32x4{mv[0], mv[1], mv[2], mv[3]};
+            if (w1 >= w0 + 4) *(gu32x4_a4*)(mk + w0 + 4) = u32x4{mv[4], mv[5], mv[6], mv[7]};
+        }
+        // the first IW_EMW words also into LDS (rewritten until the
+        // window has moved past them: then they are final)
+        static_assert(IW_EMW == 2, "early mark words");
+        if (w0 == 0) {
+            L.u.hr.em[0][lane] = mv[0];
+            L.u.hr.em[1][lane] = mv[1];
+        } else if (w0 == 1) {
+            L.u.hr.em[1][lane] = mv[0];
+        }
+        // slide the window to the word of my next token start (< 8 words on)
+        const u32 dw = w1 - w0;
+#pragma unroll
+        for (u32 sb = 1; sb < IW_MWIN; sb <<= 1) {
+            const bool t = (dw & sb) != 0;
+#pragma unroll
+            for (u32 j = 0; j < IW_MWIN; j++) mv[j] = t ? (j + sb < IW_MWIN ? mv[j + sb] : 0u) : mv[j];
+        }
+#pragma unroll
+        for (u32 j = 0; j < IW_MWIN; j++) L.u.hr.mwin[j][lane] = mv[j];
+        w0 = w1;
+      }
+      }
+      gr_absorb(bs, vC, vD);
+    }
+    static_assert(IW_K == 4 && IW_MWIN == 8, "flush layout");
+    // the last, incomplete block (an inactive lane's list never went through the ring)
+    if (active && nt > (nt0 & ~3u)) {
+        const u32 a0 = nt0 & ~3u, sb = a0 & 4u;
+        *(gu32x4_a16*)(gl + iw_ta(lane, a0)) =
+            u32x4{L.u.hr.tst[sb][lane], L.u.hr.tst[sb + 1][lane], L.u.hr.tst[sb + 2][lane],
+                  L.u.hr.tst[sb + 3][lane]};
+    }
+    // marked extent: the whole segment, or up to where the lane stopped
+    {
+        const u32 ext = !active ? 0u : nxt == S_NONE ? seg : (q - p) + (nxt == S_MARKER ? 1u : 0u);
+        L.u.hr.mlim[lane] = ext < 32 * IW_MARKW ? ext : 32 * IW_MARKW;
+    }
+    __syncthreads();  // every lane's marks and list are stored
+    IW_T(IWT_P1);
+    // pass 2: follow my path until it meets a token start a later lane marked
+    u32 ks = lane + 1, pk = pend, it2 = 0;
+    u32 lim = ks < 64 ? L.u.hr.mlim[ks] : 0u;  // (no segment past lane 63)
+    u32 cwi = 0xFFFFFFFFu, cwv = 0;
+    bool run2 = nxt == S_NONE;
+    while (__ballot(run2) != 0) {
+        const u32x4 vC = gr_vec(vbase, nvec, bs.vc), vD = gr_vec(vbase, nvec, bs.vc + 1);
+        IW_ADD(IWD_P2_WIT, 1);
+        for (u32 k = 0; k < IW_K * IW_KH; k++) {
+            if (!run2) continue;
+            if (q >= round_hi) { nxt = S_ROUND_END; run2 = false; continue; }
+            if (q >= pk + seg) { ks++; pk += seg; lim = ks < 64 ? L.u.hr.mlim[ks] : 0u; cwi = 0xFFFFFFFFu; }
+            const u32 off = q - pk;
+            if (off < lim) {
+                const u32 wi = off >> 5;
+                if (wi != cwi) { cwv = wi < IW_EMW ? L.u.hr.em[wi][ks] : marks[(u64)ks * IW_MWORDS + wi]; cwi = wi; }
+                if ((cwv >> (off & 31)) & 1u) {
+                    give = iw_rank(L, ks, marks + (u64)ks * IW_MWORDS, wi, cwv & ((1u << (off & 31)) - 1u));
+                    nxt = ks;
+                    run2 = false;
+                    continue;
+                }
+            }
+            if (!gr_fill(bs)) continue;  // A:B ran dry: wait for the refill
+            u32 tk = iw_decode(L, bs.lo);
+            const u32 adv = w_bits(tk);
+            if (q + adv > total_bits) tk = W_EXH;
+            if (nt == IW_TCAP) { nxt = S_CAP; run2 = false; continue; }
+            gl[iw_ta(lane, nt)] = tk;
+            nt++;
+            it2++;
+            if (w_marker(tk)) {
+                if (tk != (W_EXH)) q += adv;
+                nxt = S_MARKER;
+                run2 = false;
+                continue;
+            }
+            gr_drop(bs, adv);
+            q += adv;
+        }
+        gr_absorb(bs, vC, vD);
+    }
+    if (dbg) {
+        const u32 m1 = iw_wave_sum(it1), m2 = iw_wave_sum(it2);
+        const u32 m3 = iw_wave_sum(nxt == S_CAP ? 1u : 0u);
+        IW_ADD(IWD_P1_IT, m1);
+        IW_ADD(IWD_P2_IT, m2);
+        IW_ADD(IWD_CAPS, m3);
+    }
+    IW_T(IWT_P2);
+    // ---- chain: lane 0 is true; follow the sync targets (wave-uniform walk) ----
+    // chain member m lives in lane m's chL/chS/chE (its lane, first valid
+    // token, list length): a sync target is always a later lane, so a
+    // chain has <= 64 members, and the wave-uniform cursor reads them
+    // with v_readlane instead of dependent LDS reads
+    u32 ncm = 0, cur = 0, sidx = 0;
+    u32 chL = 0, chS = 0, chE = 0;
+    for (;;) {
+        const u32 e = (u32)__builtin_amdgcn_readlane((int)nt, (int)cur);
+        const u32 nx = (u32)__builtin_amdgcn_readlane((int)nxt, (int)cur);
+        if (lane == ncm) { chL = cur; chS = sidx; chE = e; }
+        ncm++;
+        if (nx < 64) {
+            sidx = (u32)__builtin_amdgcn_readlane((int)give, (int)cur);
+            cur = nx;
+            continue;
+        }
+        break;
+    }
+    const u32 endq = (u32)__builtin_amdgcn_readlane((int)q, (int)cur);  // after the last member's list
+    if ((u32)__builtin_amdgcn_readlane((int)nxt, (int)cur) == S_CAP && seg > IW_SEGMIN)
+        seg = (seg / 2 + 31) & ~31u;  // lists overflowed: shorter segments next round (this round's
+                                      // positions come from p, computed with the old seg)
+    IW_ADD(IWD_CHAIN, ncm);
+    // token lists of other lanes are read below: their stores must be done
+    __syncthreads();
+    IW_T(IWT_CHAIN);
+    return IwRound{p, ncm, chL, chS, chE, endq};
+}
 
 __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chunk* __restrict__ chunks, u32 n,
                                                                   u64 D, DType t, u32 vflags,
@@ -675,32 +786,24 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
     const u32 lane = threadIdx.x;
     const bool dbg = ZIW_DBG && (vflags & ZCG_FLAG_DEBUG_COUNTERS) != 0;
     const zcg_chunk ch = chunks[c];
-    if (D == 0) { if (lane == 0) status[c] = ZCG_OK; return; }
-    if (ch.dst_cap < D) { if (lane == 0) status[c] = ZCG_ERR_INVALID_INPUT; return; }
-    const u8* s = (const u8*)ch.src;
-    const u64 n_in = ch.src_len;
-    u64 h = 0;
-    int st = gzip_header(s, n_in, &h);
-    if (st == ZCG_OK && (n_in - h >= (1ull << 28) || D >= (1ull << 32))) st = ZCG_ERR_UNSUPPORTED;  // u32 positions
-    if (st != ZCG_OK) { if (lane == 0) status[c] = st; return; }
+    InfMember m;
+    int st;
+    bool open = inf_open(ch, D, t, m, &st);
+    if (open && (m.n_ds >= (1ull << 28) || D >= (1ull << 32))) { st = ZCG_ERR_UNSUPPORTED; open = false; }  // u32 positions
+    if (!open) { if (lane == 0) status[c] = st; return; }
 
-    u8* dst = (u8*)ch.dst;
-    const u8* ds = s + h;
-    const u64 n_ds = n_in - h;
+    u8* const dst = m.dst;
+    const u8* const ds = m.ds;
+    const u64 n_ds = m.n_ds;
     const u32 total_bits = (u32)(n_ds * 8);
     const u8* vbase = (const u8*)((uintptr_t)ds & ~(uintptr_t)15);
     const u32 a0b = (u32)((uintptr_t)ds & 15) * 8;  // stream bit 0 relative to vbase
     const u32 nvec = (u32)(((uintptr_t)ds & 15) + n_ds + 15) / 16;
-    DType tw = t;
-    tw.isbool = 0;
+    const DType tw = m.tw;
 
     // workspace slot (freed at the end; every path below reaches it)
     u32 slot = 0;
-    if (lane == 0) {
-        u32 sl = c % nslot;
-        while (atomicCAS(&owner[sl], 0u, 1u) != 0u) sl = (sl + 1) % nslot;
-        slot = sl;
-    }
+    if (lane == 0) slot = slot_take(owner, nslot, c);
     slot = __builtin_amdgcn_readfirstlane(slot);
     gu32* const gl = pools + (u64)slot * IW_SLOT_WORDS;                 // token lists (iw_ta layout)
     gu32* const marks = gl + IW_LIST_WORDS;                             // token-start bitmaps [lane][IW_MWORDS]
@@ -725,9 +828,12 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
         u32 type = 0, slen = 0;
         b.cbase = ~0ull;  // the reader's LDS cache shares storage with the stage
         wsync();
-        r = read_block_header_wave<W_LB, W_LCAP, W_DB, W_DCAP>(b, &last, &type, &slen, L.u.h.lens, &L.u.h.lh, L.ltab,
-                                                               &L.u.h.dh, L.dtab, L.u.h.hwin,
-                                                               dbg ? &L.dbgc[IWT_HTAB] : nullptr);
+        r = read_block_header<W_LB, W_LCAP, W_DB, W_DCAP>(
+            b, &last, &type, &slen, L.u.h.lens, &L.u.h.lh, L.ltab, &L.u.h.dh, L.dtab,
+            [&](BitIn& bb) __attribute__((always_inline)) {
+                return read_dynamic_wave<W_LB, W_LCAP, W_DB, W_DCAP>(bb, L.u.h.lens, &L.u.h.lh, L.ltab, &L.u.h.dh, L.dtab,
+                                                                     L.u.h.hwin, dbg ? &L.dbgc[IWT_HTAB] : nullptr);
+            });
         const u32 hdr_end = (u32)b.consumed;
         if (r == R_OK && type != 0) {  // a Huffman block: the tables as the H round reads them
             iw_tab_wave(L);
@@ -738,22 +844,15 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
         wsync();
         if (type == 0) {
             // ---- stored block: byte copies through the stage ------------------------
-            u64 in0 = hdr_end >> 3;  // byte aligned after LEN/NLEN
-            u32 done = 0;
-            while (done < slen && P < D) {
-                u32 k = slen - done;
-                if (k > IW_S - 16) k = IW_S - 16;
-                if ((u64)k > D - P) k = (u32)(D - P);
-                if (in0 + k > n_ds) { r = R_EXHAUSTED; break; }
-                wsync();
-                for (u32 i = lane; i < k; i += 64) L.u.st.ptr[(P & 15) + i] = (u16)(IE_VAL | ds[in0 + i]);
-                iw_commit(L, dst, P, P + k, tw);
-                P += k; in0 += k; done += k;
-            }
+            // (a piece of at most IW_S - 16 bytes never wraps the ring; the fence
+            // after a commit orders its stage reads before the next piece's stores)
+            u64 in_end = 0;
+            r = inf_stored_copy<64>(m, hdr_end >> 3 /* byte aligned after LEN/NLEN */, slen, P, D, IW_S - 16, L.u.st.ptr, lane,
+                                    [](u64 P0, u32 i) -> u32 { return (u32)(P0 & 15) + i; },
+                                    [&](u64 from, u64 to) { iw_commit(L, dst, from, to, tw); wsync(); }, &in_end, &boundary);
             if (r != R_OK) break;
             b.cbase = ~0ull;
-            bi_seek(b, in0 * 8);
-            boundary = (done == slen);
+            bi_seek(b, in_end * 8);
             after_stored = true;
             continue;
         }
@@ -767,275 +866,8 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
         seg = seg < IW_SEGMIN ? IW_SEGMIN : seg > IW_SEGMAX ? IW_SEGMAX : seg;
         while (!block_end && !final_cut && r == R_OK && P < D) {
             // ================= H round: coarse speculative Huffman decode =================
-            IW_ADD(IWD_ROUNDS, 1);
-            const u32 round_hi = R0 + 64 * seg;
-            const u32 p = R0 + lane * seg;
-            const u32 pend = p + seg;
-            u32 q = p, nt = 0, nxt = S_NONE, give = 0;
-            const bool active = p < total_bits;
-            GRd bs;
-            gr_init(bs, vbase, nvec, (active ? p : 0u) + a0b);
-            if (!active) {
-                if (lane == 0) {  // the block body starts at the stream end
-                    gl[iw_ta(0, 0)] = W_MARK | M_EXH;
-                    nt = 1;
-                    nxt = S_MARKER;
-                } else {
-                    nxt = S_ROUND_END;  // (never on the chain: the lane before it ends in EXH)
-                }
-            }
-            // pass 1: my segment; markers other than EXH do not stop it.  Each
-            // step stages its token and sets its start bit in an LDS window of
-            // IW_MWIN mark words; every IW_K steps all lanes flush both to the
-            // workspace with unconditional stores and refill the reader.
-            u32 it1 = 0, w0 = 0, nt0 = nt;
-#pragma unroll
-            for (u32 j = 0; j < IW_MWIN; j++) L.u.hr.mwin[j][lane] = 0;
-            bool run = nxt == S_NONE;
-            // flush of the staged tokens: the aligned block holding token nt0
-            // once it is complete (each block is stored once: its first words
-            // stay in the ring until then, <= 3 + IW_K < 8 entries)
-            auto flush_tokens = [&]() {
-                const u32 a0 = nt0 & ~3u, sb = a0 & 4u;
-                if (nt >= a0 + 4) {
-                    *(gu32x4_a16*)(gl + iw_ta(lane, a0)) =
-                        u32x4{L.u.hr.tst[sb][lane], L.u.hr.tst[sb + 1][lane], L.u.hr.tst[sb + 2][lane],
-                              L.u.hr.tst[sb + 3][lane]};
-                    nt0 = nt;
-                }
-            };
-            while (__ballot(run) != 0) {
-              const u32x4 vC = gr_vec(vbase, nvec, bs.vc), vD = gr_vec(vbase, nvec, bs.vc + 1);
-              IW_ADD(IWD_P1_WIT, 1);
-              // Once per outer step, wave-uniformly: a running lane is on the
-              // edge if its list could fill, its stream could end (8 maximal
-              // tokens of 48 bits), or its mark window is still inside the
-              // IW_MARKW words that are ever read.  With no lane on the edge
-              // the steady body runs: no cap, exhausted or mark work at all.
-              const bool edge = run && (nt + IW_K * IW_KH > IW_TCAP || q + 48 * IW_K * IW_KH > total_bits ||
-                                        w0 < IW_MARKW);
-              if (ZIW_STEADY && __ballot(edge) == 0) {
-                IW_ADD(IWD_P1_STEADY, 1);
-                for (u32 kh = 0; kh < IW_KH; kh++) {
-                    for (u32 k = 0; k < IW_K; k++) {
-                        // one predicated region per step: a lane idles when it is
-                        // done or A:B ran dry (until the absorb below)
-                        if (run && bs.bp <= 208) {
-                            gr_fill(bs);
-                            const u32 tk = iw_decode(L, bs.lo);
-                            const u32 adv = w_bits(tk);
-                            L.u.hr.tst[nt & (2 * IW_K - 1)][lane] = tk;
-                            nt++;
-                            gr_drop(bs, adv);
-                            q += adv;
-                            it1++;
-                            run = q < pend;
-                        }
-                    }
-                    flush_tokens();
-                }
-                // no marks were set and the window was not moved: it holds
-                // nothing that is stored (w0 >= IW_MARKW), so only its position
-                // follows the lane, for an edge step that may come later
-                w0 = (q - p) >> 5;
-              } else {
-              for (u32 kh = 0; kh < IW_KH; kh++) {
-                for (u32 k = 0; k < IW_K; k++) {
-                    if (!run || !gr_fill(bs)) continue;
-                    u32 tk = iw_decode(L, bs.lo);
-                    const u32 adv = w_bits(tk);
-                    if (q + adv > total_bits) tk = W_MARK | M_EXH;
-                    if (nt == IW_TCAP) { nxt = S_CAP; run = false; continue; }
-                    L.u.hr.tst[nt & (2 * IW_K - 1)][lane] = tk;
-                    nt++;
-                    const u32 off = q - p;  // (<= 5 words past w0 within one flush period)
-                    atomicOr(&L.u.hr.mwin[(off >> 5) - w0][lane], 1u << (off & 31));
-                    if (tk == (W_MARK | M_EXH)) { nxt = S_MARKER; run = false; continue; }
-                    gr_drop(bs, adv);
-                    q += adv;
-                    it1++;
-                    if (q >= pend) run = false;
-                }
-                // flush: the staged tokens, then the mark window (words past my
-                // position are still zero)
-                flush_tokens();
-                u32 mv[IW_MWIN];
-#pragma unroll
-                for (u32 j = 0; j < IW_MWIN; j++) mv[j] = L.u.hr.mwin[j][lane];
-                // marks are kept for the first IW_MARKW words of the segment only
-                // (a misaligned decoder syncs within ~450 bits at p99); later
-                // flushes store nothing (stores to a dummy slot instead cost
-                // 14 GB of writes and 11 % of the time per C2 launch: the slot
-                // lines do not stay in L2 under 4 096 chunks' token lists)
-                // Only words w0 .. w1 (the word of my next token start) can hold
-                // marks yet, and w1 - w0 < 4 in almost every period: the second
-                // half of the window is stored only when the lane got that far
-                // (its zero words are stored when the window has slid onto them;
-                // pass 2 and iw_rank read no word past the marked extent)
-                const u32 w1 = (q - p) >> 5;
-                if (w0 < IW_MARKW) {
-                    *(gu32x4_a4*)(mk + w0) = u32x4{mv[0], mv[1], mv[2], mv[3]};
-                    if (w1 >= w0 + 4) *(gu32x4_a4*)(mk + w0 + 4) = u32x4{mv[4], mv[5], mv[6], mv[7]};
-                }
-                // the first IW_EMW words also into LDS (rewritten until the
-                // window has moved past them: then they are final)
-                static_assert(IW_EMW == 2, "early mark words");
-                if (w0 == 0) {
-                    L.u.hr.em[0][lane] = mv[0];
-                    L.u.hr.em[1][lane] = mv[1];
-                } else if (w0 == 1) {
-                    L.u.hr.em[1][lane] = mv[0];
-                }
-                // slide the window to the word of my next token start (< 8 words on)
-                const u32 dw = w1 - w0;
-#pragma unroll
-                for (u32 sb = 1; sb < IW_MWIN; sb <<= 1) {
-                    const bool t = (dw & sb) != 0;
-#pragma unroll
-                    for (u32 j = 0; j < IW_MWIN; j++) mv[j] = t ? (j + sb < IW_MWIN ? mv[j + sb] : 0u) : mv[j];
-                }
-#pragma unroll
-                for (u32 j = 0; j < IW_MWIN; j++) L.u.hr.mwin[j][lane] = mv[j];
-                w0 = w1;
-              }
-              }
-              gr_absorb(bs, vC, vD);
-            }
-            static_assert(IW_K == 4 && IW_MWIN == 8, "flush layout");
-            // the last, incomplete block (an inactive lane's list never went through the ring)
-            if (active && nt > (nt0 & ~3u)) {
-                const u32 a0 = nt0 & ~3u, sb = a0 & 4u;
-                *(gu32x4_a16*)(gl + iw_ta(lane, a0)) =
-                    u32x4{L.u.hr.tst[sb][lane], L.u.hr.tst[sb + 1][lane], L.u.hr.tst[sb + 2][lane],
-                          L.u.hr.tst[sb + 3][lane]};
-            }
-            // marked extent: the whole segment, or up to where the lane stopped
-            {
-                const u32 ext = !active ? 0u : nxt == S_NONE ? seg : (q - p) + (nxt == S_MARKER ? 1u : 0u);
-                L.u.hr.mlim[lane] = ext < 32 * IW_MARKW ? ext : 32 * IW_MARKW;
-            }
-            __syncthreads();  // every lane's marks and list are stored
-            IW_T(IWT_P1);
-            // pass 2: follow my path until it meets a token start a later lane marked
-            u32 ks = lane + 1, pk = pend, it2 = 0;
-            u32 lim = ks < 64 ? L.u.hr.mlim[ks] : 0u;  // (no segment past lane 63)
-            u32 cwi = 0xFFFFFFFFu, cwv = 0;
-            bool run2 = nxt == S_NONE;
-            while (__ballot(run2) != 0) {
-                const u32x4 vC = gr_vec(vbase, nvec, bs.vc), vD = gr_vec(vbase, nvec, bs.vc + 1);
-                IW_ADD(IWD_P2_WIT, 1);
-#if ZIW_P2FLAT
-                // one predicated region per step: the step's outcome is a stop
-                // code (S_NONE: go on), the state follows by selects
-                for (u32 k = 0; k < IW_K * IW_KH; k++) {
-                    if (run2) {
-                        u32 stop = S_NONE;
-                        if (q >= round_hi) {
-                            stop = S_ROUND_END;
-                        } else {
-                            if (q >= pk + seg) { ks++; pk += seg; lim = ks < 64 ? L.u.hr.mlim[ks] : 0u; cwi = 0xFFFFFFFFu; }
-                            const u32 off = q - pk;
-                            if (off < lim) {
-                                const u32 wi = off >> 5;
-                                if (wi != cwi) { cwv = wi < IW_EMW ? L.u.hr.em[wi][ks] : marks[(u64)ks * IW_MWORDS + wi]; cwi = wi; }
-                                if ((cwv >> (off & 31)) & 1u) {
-                                    give = iw_rank(L, ks, marks + (u64)ks * IW_MWORDS, wi, cwv & ((1u << (off & 31)) - 1u));
-                                    stop = ks;
-                                }
-                            }
-                        }
-                        if (stop == S_NONE && bs.bp <= 208) {  // (else A:B ran dry: wait for the refill)
-                            gr_fill(bs);
-                            u32 tk = iw_decode(L, bs.lo);
-                            const u32 adv = w_bits(tk);
-                            if (q + adv > total_bits) tk = W_MARK | M_EXH;
-                            if (nt == IW_TCAP) {
-                                stop = S_CAP;
-                            } else {
-                                gl[iw_ta(lane, nt)] = tk;
-                                nt++;
-                                it2++;
-                                const bool mkr = w_marker(tk);
-                                q += tk == (W_MARK | M_EXH) ? 0u : adv;
-                                bs.bp += mkr ? 0u : adv;
-                                stop = mkr ? S_MARKER : S_NONE;
-                            }
-                        }
-                        nxt = stop;
-                        run2 = stop == S_NONE;
-                    }
-                }
-#else
-                for (u32 k = 0; k < IW_K * IW_KH; k++) {
-                    if (!run2) continue;
-                    if (q >= round_hi) { nxt = S_ROUND_END; run2 = false; continue; }
-                    if (q >= pk + seg) { ks++; pk += seg; lim = ks < 64 ? L.u.hr.mlim[ks] : 0u; cwi = 0xFFFFFFFFu; }
-                    const u32 off = q - pk;
-                    if (off < lim) {
-                        const u32 wi = off >> 5;
-                        if (wi != cwi) { cwv = wi < IW_EMW ? L.u.hr.em[wi][ks] : marks[(u64)ks * IW_MWORDS + wi]; cwi = wi; }
-                        if ((cwv >> (off & 31)) & 1u) {
-                            give = iw_rank(L, ks, marks + (u64)ks * IW_MWORDS, wi, cwv & ((1u << (off & 31)) - 1u));
-                            nxt = ks;
-                            run2 = false;
-                            continue;
-                        }
-                    }
-                    if (!gr_fill(bs)) continue;  // A:B ran dry: wait for the refill
-                    u32 tk = iw_decode(L, bs.lo);
-                    const u32 adv = w_bits(tk);
-                    if (q + adv > total_bits) tk = W_MARK | M_EXH;
-                    if (nt == IW_TCAP) { nxt = S_CAP; run2 = false; continue; }
-                    gl[iw_ta(lane, nt)] = tk;
-                    nt++;
-                    it2++;
-                    if (w_marker(tk)) {
-                        if (tk != (W_MARK | M_EXH)) q += adv;
-                        nxt = S_MARKER;
-                        run2 = false;
-                        continue;
-                    }
-                    gr_drop(bs, adv);
-                    q += adv;
-                }
-#endif
-                gr_absorb(bs, vC, vD);
-            }
-            if (dbg) {
-                const u32 m1 = iw_wave_sum(it1), m2 = iw_wave_sum(it2);
-                const u32 m3 = iw_wave_sum(nxt == S_CAP ? 1u : 0u);
-                IW_ADD(IWD_P1_IT, m1);
-                IW_ADD(IWD_P2_IT, m2);
-                IW_ADD(IWD_CAPS, m3);
-            }
-            IW_T(IWT_P2);
-            // ---- chain: lane 0 is true; follow the sync targets (wave-uniform walk) ----
-            // chain member m lives in lane m's chL/chS/chE (its lane, first valid
-            // token, list length): a sync target is always a later lane, so a
-            // chain has <= 64 members, and the wave-uniform cursor reads them
-            // with v_readlane instead of dependent LDS reads
-            u32 ncm = 0, cur = 0, sidx = 0;
-            u32 chL = 0, chS = 0, chE = 0;
-            for (;;) {
-                const u32 e = (u32)__builtin_amdgcn_readlane((int)nt, (int)cur);
-                const u32 nx = (u32)__builtin_amdgcn_readlane((int)nxt, (int)cur);
-                if (lane == ncm) { chL = cur; chS = sidx; chE = e; }
-                ncm++;
-                if (nx < 64) {
-                    sidx = (u32)__builtin_amdgcn_readlane((int)give, (int)cur);
-                    cur = nx;
-                    continue;
-                }
-                break;
-            }
-            const u32 endq = (u32)__builtin_amdgcn_readlane((int)q, (int)cur);  // after the last member's list
-            if ((u32)__builtin_amdgcn_readlane((int)nxt, (int)cur) == S_CAP && seg > IW_SEGMIN)
-                seg = (seg / 2 + 31) & ~31u;  // lists overflowed: shorter segments next round (this round's
-                                              // positions come from p, computed with the old seg)
-            IW_ADD(IWD_CHAIN, ncm);
-            // token lists of other lanes are read below: their stores must be done
-            __syncthreads();
-            IW_T(IWT_CHAIN);
+            const IwRound hr = iw_h_round(L, R0, seg, total_bits, vbase, nvec, a0b, gl, marks, mk, dbg, t_last);
+            const u32 p = hr.p, ncm = hr.ncm, chL = hr.chL, chS = hr.chS, chE = hr.chE, endq = hr.endq;
 
             // ================= L phase: the chain's tokens, one stage at a time =========
             // Stage: output [S, S + emit) in the ring; lane l owns the 32-entry
@@ -1203,9 +1035,7 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
                     // its part's descriptor.
                     for (u32 n0 = 0; n0 < pn_NB; n0 += 64) {
                         L.u.st.mk[lane] = 0;
-#if ZIW_MKFENCE
                         wsync();
-#endif
                         if (pn_nla && pn_na < n0 + 64 && pn_na + pn_nla > n0) {
                             const u32 sl = pn_na > n0 ? pn_na - n0 : 0u;
                             L.u.st.mk[sl] = (sl << 26) | pn_dsa;
@@ -1462,28 +1292,22 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
             }
         }
     }
-    // zlib's post-N look-ahead (wave-uniform); see zcg_inflate_common.h
+    // zlib's post-N look-ahead (wave-uniform).  The reader's cache shares
+    // storage with the stage; when the output filled inside a Huffman block
+    // (!after_stored) the look-ahead decodes that block's next token, with the
+    // serial reader, so the tables go back to the serial layout (after a
+    // stored block it starts at a header and builds its own).
     if (r == R_OK && P >= D && boundary) {
-        const u64 last_byte = h + (b.consumed ? (b.consumed - 1) / 8 : 0);
-        u64 wend = (last_byte / 32768 + 1) * 32768;
-        if (wend > n_in) wend = n_in;
-        b.limit = (wend - h) * 8;
         b.cbase = ~0ull;
         wsync();
-        if (b.limit >= b.consumed) {
-            // the look-ahead decodes the current block's next token with the
-            // serial reader (after a stored block it starts at a header and
-            // builds its own tables)
-            // (boundary with !after_stored: the output filled inside a Huffman block)
-            if (!after_stored) iw_tab_serial(L);
-            const int la = inf_lookahead<W_LB, W_LCAP, W_DB, W_DCAP>(b, last, after_stored, L.u.h.lens, &L.u.h.lh,
-                                                                     L.ltab, &L.u.h.dh, L.dtab);
-            if (la == R_INVALID) r = R_INVALID;
-        }
+        if (!after_stored) iw_tab_serial(L);
     }
-    if (r == R_INVALID) st = ZCG_ERR_INVALID_DATA;
-    else if (r == R_EXHAUSTED || P < D) st = ZCG_ERR_UNEXPECTED_EOF;
-    if (t.isbool) iw_bool_norm(dst, P < D ? P : D);
+    st = inf_close<W_LB, W_LCAP, W_DB, W_DCAP>(b, m, r, P, D, boundary, last, after_stored, L.u.h.lens, &L.u.h.lh, L.ltab,
+                                               &L.u.h.dh, L.dtab);
+    if (t.isbool) {  // byte != 0 over the whole decoded chunk (the committed bytes were the window)
+        __syncthreads();
+        wave_transform<64>(dst, P < D ? P : D, DType{1, 0, 1}, lane);
+    }
     if (dbg) {
         if (lane == 0) L.dbgc[IWT_TOTAL] = (u32)(__builtin_readcyclecounter() - t_start);
         wsync();
@@ -1492,7 +1316,7 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
     __syncthreads();  // every workspace access of this wave is done
     if (lane == 0) {
         status[c] = st;
-        atomicExch(&owner[slot], 0u);
+        slot_free(owner, slot);
     }
 }
 
@@ -1518,15 +1342,9 @@ static u32 iw_nslot(uint32_t n) {
     return (u32)ns;
 }
 
-// the pass-1 / look-up A/B knobs show in the tag only when they differ from the product build
-#if ZIW_STEADY != 1 || ZIW_SUBSEL != 0 || ZIW_P2FLAT != 0 || ZIW_MKFENCE != 1
-#define IW_AB_TAG ",STEADY=" ZCG_STR(ZIW_STEADY) ",SUBSEL=" ZCG_STR(ZIW_SUBSEL) ",P2FLAT=" ZCG_STR(ZIW_P2FLAT) ",MKFENCE=" ZCG_STR(ZIW_MKFENCE)
-#else
-#define IW_AB_TAG ""
-#endif
 const char* cfg_inflate_wave() {
     return "inflate_wave:S=" ZCG_STR(ZIW_S) ",TCAP=" ZCG_STR(ZIW_TCAP) ",WPE=" ZCG_STR(ZIW_WPE)
-           ",EST_PCT=" ZCG_STR(ZIW_EST_PCT) ",MARKW=" ZCG_STR(ZIW_MARKW) ",G=" ZCG_STR(ZIW_G) ",DBG=" ZCG_STR(ZIW_DBG) IW_AB_TAG;
+           ",EST_PCT=" ZCG_STR(ZIW_EST_PCT) ",MARKW=" ZCG_STR(ZIW_MARKW) ",G=" ZCG_STR(ZIW_G) ",DBG=" ZCG_STR(ZIW_DBG);
 }
 
 uint64_t inflate_wave_ws_bytes(const zcg_array* a, uint32_t n) {

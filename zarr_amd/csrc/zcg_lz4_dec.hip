@@ -1100,7 +1100,7 @@ __global__ __launch_bounds__(64) void lz4_finish_kernel(const zcg_chunk* __restr
     __syncthreads();
     if ((t.swap || t.isbool) && st_s == ZCG_OK) {
         __threadfence_block();
-        wave_transform((u8*)chunks[c].dst, D, t);
+        wave_transform<64>((u8*)chunks[c].dst, D, t, (u32)lane_id());
     }
 }
 

@@ -341,7 +341,7 @@ __global__ __launch_bounds__(64) void xz_decode_kernel(const zcg_chunk* __restri
     io.lane = lane;
     int st = zx::xz_decode(io);
     io.finish();
-    if (st == ZCG_OK && (t.swap || t.isbool)) wave_transform((u8*)ch.dst, D, t);
+    if (st == ZCG_OK && (t.swap || t.isbool)) wave_transform<64>((u8*)ch.dst, D, t, (u32)lane_id());
     if (lane == 0) status[c] = st;
 }
 
