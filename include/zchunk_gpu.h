@@ -74,7 +74,50 @@ enum zcg_status {
  * full-length read, so neither is verified.  LZ4
  * block checksums are verified as LZ4F does, unless this flag skips them
  * (the decoded bytes are the same; only a corrupt checksum word changes the
- * status).  Bits 0x1 and 0x2 are reserved. */
+ * status).
+ *
+ * Opt-in verification (decode only; encode ignores both flags, and a flag for
+ * the other codec is ignored).  Every decode entry point honours them through
+ * zcg_array.compression.flags: zcg_decode_batch, zcg_read_chunk,
+ * zcg_read_chunks_host, zcg_store_read_chunks[_device], zcg_multi_*.
+ *   - A chunk whose status without the flag is not ZCG_OK keeps exactly that
+ *     status: verification runs only on chunks that decode OK.
+ *   - A chunk of D == 0 decoded bytes is OK and nothing is verified (the
+ *     reference reads zero bytes).
+ *   - On a mismatch the decoded bytes stay in dst, untrusted (for bool arrays
+ *     not normalised either); only the status says so.  Bytes after D are
+ *     never touched.
+ * For a chunk that decodes OK the verdict is the first rule that applies.
+ * ZCG_FLAG_VERIFY_GZIP_TRAILER (D = N*elem_size decoded bytes):
+ *   1. the member must end exactly at D bytes: after the output is full the
+ *      rest of the deflate stream is walked with the whole input as its limit
+ *      (not flate2's 32 KiB window): the EOB of the current block, empty
+ *      stored blocks, block headers and tables, up to the final block's end;
+ *   2. the output filled inside a match, the next token would emit a byte, or
+ *      a non-empty stored block follows -> ZCG_ERR_INVALID_DATA (the member
+ *      holds more than the chunk);
+ *   3. an invalid header or code on the way -> ZCG_ERR_INVALID_DATA; input
+ *      that runs out before the final block's end or before 8 trailer bytes
+ *      -> ZCG_ERR_UNEXPECTED_EOF;
+ *   4. the trailer sits at byte h + ceil(end_bit / 8) of the member (h = gzip
+ *      header bytes, end_bit = deflate bits consumed); it is never taken from
+ *      src_len - 8, and bytes after it (a second member) are ignored;
+ *   5. ISIZE != D mod 2^32 -> ZCG_ERR_INVALID_DATA;
+ *   6. CRC32 of the D decoded bytes in stream order (before the byte swap and
+ *      the bool rule) != the trailer's -> ZCG_ERR_INVALID_DATA.
+ * ZCG_FLAG_VERIFY_LZ4_CONTENT:
+ *   1. the frame must end exactly at D bytes: the EndMark follows the block
+ *      that reaches D; a further data block (or a block that decodes past D)
+ *      -> ZCG_ERR_INVALID_DATA; input that ends before the EndMark, or before
+ *      the 4 checksum bytes when FLG.C is set -> ZCG_ERR_UNEXPECTED_EOF;
+ *   2. a content size in the header that differs from D -> ZCG_ERR_INVALID_DATA;
+ *   3. FLG.C set and XXH32 (seed 0) of the D decoded bytes in stream order !=
+ *      the stored word -> ZCG_ERR_INVALID_DATA.  With FLG.C clear there is
+ *      nothing to compare and the chunk stays OK;
+ *   4. linked-block frames and the other serially decoded frames obey the same
+ *      rules. */
+#define ZCG_FLAG_VERIFY_GZIP_TRAILER 0x1u
+#define ZCG_FLAG_VERIFY_LZ4_CONTENT 0x2u
 #define ZCG_FLAG_SKIP_LZ4_BLOCK_CHECKSUM 0x4u
 /* Use the wave-serial inflate kernel instead of the parallel one (the two are
  * bit-identical; the serial one is kept as a differential reference). */

@@ -18,9 +18,16 @@ ABSENT, IO = 6, 7  # store: no chunk file (read_chunk -> None); filesystem error
 NOT_FOUND = 8  # store: key outside the hierarchy (filesystem.rs:180-186)
 RUNTIME = 100
 
+# opt-in verification on decode (include/zchunk_gpu.h): the gzip CRC32/ISIZE
+# trailer, the LZ4 frame's end, content size and content checksum
+FLAG_VERIFY_GZIP_TRAILER = 0x1
+FLAG_VERIFY_LZ4_CONTENT = 0x2
+FLAG_VERIFY = FLAG_VERIFY_GZIP_TRAILER | FLAG_VERIFY_LZ4_CONTENT
 FLAG_SKIP_LZ4_BLOCK_CHECKSUM = 0x4
 FLAG_SERIAL_INFLATE = 0x100
 FLAG_DEBUG_COUNTERS = 0x200
+FLAG_LZ4_WAVE_PER_BLOCK = 0x800
+FLAG_LZ4_LANE_PER_BLOCK = 0x1000
 FLAG_INFLATE_BLOCK_PAR = 0x2000
 FLAG_INFLATE_WAVE = 0x4000
 FLAG_GZIP_SEGMENTED = 0x8000

@@ -151,6 +151,16 @@ __device__ __forceinline__ u32 slot_take(u32* owner, u32 nslot, u32 start) {
 }
 __device__ __forceinline__ void slot_free(u32* owner, u32 slot) { atomicExch(&owner[slot], 0u); }
 
+// Per-chunk record a decoder leaves for the verify kernels (zcg_verify.hip)
+// when a verify flag is set: V_SKIP = the status is final, V_CHECK = compare
+// the checksum of the decoded bytes with `expect`, V_PASS = the stream carries
+// no checksum, only the deferred element transform is owed.  The launchers
+// zero the records (V_SKIP) before the decode.
+enum : u32 { V_SKIP = 0, V_CHECK = 1, V_PASS = 2 };
+struct VerifyRec {
+    u32 mode, expect;
+};
+
 // ---- XXH32 (LZ4 frame header / block / content checksums) --------------
 constexpr u32 XXH_P1 = 2654435761u;
 constexpr u32 XXH_P2 = 2246822519u;
@@ -318,14 +328,36 @@ uint64_t lz4_encode_ws_bytes(const zcg_array* a, uint32_t n);
 uint64_t gzip_decode_ws_bytes(const zcg_array* a, uint32_t n);
 hipError_t launch_gzip_decode(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n,
                               int32_t* d_status, void* ws, uint64_t ws_bytes, hipStream_t s);
+// (ws: the verify records under ZCG_FLAG_VERIFY_GZIP_TRAILER, else unused)
 hipError_t launch_inflate(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n,
-                          int32_t* d_status, hipStream_t s);
+                          int32_t* d_status, void* ws, uint64_t ws_bytes, hipStream_t s);
+// Opt-in checksum verification (zcg_verify.hip), launched on the decode's
+// stream after its last kernel.  The verify area is a part of the decoder's
+// workspace: VerifyRec[n], then the CRC32 partials.  Under a verify flag the
+// decode kernels get a dtype without the part of the element transform that
+// the verify pass applies after it has read the bytes in stream order: bool
+// for gzip (its byte swap is undone on the fly), byte swap and bool for LZ4.
+inline bool gzip_verify(const zcg_array* a) { return (a->compression.flags & ZCG_FLAG_VERIFY_GZIP_TRAILER) != 0; }
+inline bool lz4_verify(const zcg_array* a) { return (a->compression.flags & ZCG_FLAG_VERIFY_LZ4_CONTENT) != 0; }
+inline DType gzip_decode_dtype(const zcg_array* a) {
+    DType t = make_dtype(a->dtype);
+    if (gzip_verify(a)) t.isbool = 0;
+    return t;
+}
+uint64_t verify_ws_bytes(uint32_t n);
+hipError_t verify_reset(void* varea, uint32_t n, hipStream_t s);
+hipError_t launch_crc32_verify(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n,
+                               int32_t* d_status, void* varea, hipStream_t s);
+hipError_t launch_xxh32_verify(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n,
+                               int32_t* d_status, void* varea, hipStream_t s);
 hipError_t launch_inflate_par(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n,
                               int32_t* d_status, void* ws, uint64_t ws_bytes, hipStream_t s);
 uint64_t inflate_par_ws_bytes(const zcg_array* a, uint32_t n);
+void* inflate_par_verify_area(void* ws);
 hipError_t launch_inflate_wave(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n,
                                int32_t* d_status, void* ws, uint64_t ws_bytes, hipStream_t s);
 uint64_t inflate_wave_ws_bytes(const zcg_array* a, uint32_t n);
+void* inflate_wave_verify_area(void* ws);
 // side/fork/join (optional, nullptr: one stream): the lazy parse of each
 // sub-batch runs on the side stream while the next sub-batch's match search
 // runs on s (the workspace's side stream, as the LZ4 decoder uses it)

@@ -25,7 +25,7 @@ namespace zcg {
 
 __global__ __launch_bounds__(64) void inflate_kernel(const zcg_chunk* __restrict__ chunks, u32 n,
                                                      u64 D, DType t, u32 vflags,
-                                                     i32* __restrict__ status) {
+                                                     i32* __restrict__ status, VerifyRec* __restrict__ vrec) {
     __shared__ __attribute__((aligned(16))) u8 ring[INF_RING];
     __shared__ u32 ltab[INF_LTAB];
     __shared__ u32 dtab[INF_DTAB];
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(64) void inflate_kernel(const zcg_chunk* __restrict
             inf_maybe_flush(o);
         }
     }
-    st = inf_close(b, m, r, o.P, D, boundary, last, after_stored, lens, &lh, ltab, &dh, dtab);
+    st = inf_close(b, m, r, o.P, D, boundary, last, after_stored, lens, &lh, ltab, &dh, dtab, vflags, vrec + c);
     if (st == ZCG_OK) {
         while (D - o.F > INF_FLUSH) inf_flush(o, o.F + INF_FLUSH);
         inf_flush(o, D);
@@ -136,12 +136,13 @@ __global__ __launch_bounds__(64) void inflate_kernel(const zcg_chunk* __restrict
 }
 
 hipError_t launch_inflate(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n,
-                          int32_t* d_status, hipStream_t s) {
+                          int32_t* d_status, void* ws, uint64_t ws_bytes, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    const DType t = make_dtype(a->dtype);
+    if (gzip_verify(a) && (!ws || ws_bytes < verify_ws_bytes(n))) return hipErrorInvalidValue;
+    const DType t = gzip_decode_dtype(a);
     const u64 D = a->chunk_num_elements * (u64)t.es;
     hipLaunchKernelGGL(inflate_kernel, dim3(n), dim3(64), 0, s, d_chunks, n, D, t,
-                       a->compression.flags, d_status);
+                       a->compression.flags, d_status, (VerifyRec*)ws);
     return hipGetLastError();
 }
 
@@ -157,16 +158,30 @@ static bool inflate_par_pick(const zcg_array* a, uint32_t n) {
     return n <= 3 * device_cu_count();
 }
 
+// Under ZCG_FLAG_VERIFY_GZIP_TRAILER each kernel's workspace also holds the
+// verify area (per-chunk records, CRC partials): the whole workspace of the
+// serial kernel, after the slot-owner words of the other two.
 uint64_t gzip_decode_ws_bytes(const zcg_array* a, uint32_t n) {
-    if (a->compression.flags & ZCG_FLAG_SERIAL_INFLATE) return 0;
+    if (a->compression.flags & ZCG_FLAG_SERIAL_INFLATE) return gzip_verify(a) && n ? verify_ws_bytes(n) : 0;
     return inflate_par_pick(a, n) ? inflate_par_ws_bytes(a, n) : inflate_wave_ws_bytes(a, n);
 }
 
 hipError_t launch_gzip_decode(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n, int32_t* d_status, void* ws,
                               uint64_t ws_bytes, hipStream_t s) {
-    if (a->compression.flags & ZCG_FLAG_SERIAL_INFLATE) return launch_inflate(a, d_chunks, n, d_status, s);
-    if (inflate_par_pick(a, n)) return launch_inflate_par(a, d_chunks, n, d_status, ws, ws_bytes, s);
-    return launch_inflate_wave(a, d_chunks, n, d_status, ws, ws_bytes, s);
+    if (n == 0) return hipSuccess;
+    const bool verify = gzip_verify(a);
+    const bool serial = (a->compression.flags & ZCG_FLAG_SERIAL_INFLATE) != 0, par = !serial && inflate_par_pick(a, n);
+    void* const varea = serial ? ws : par ? inflate_par_verify_area(ws) : inflate_wave_verify_area(ws);
+    if (verify) {
+        if (!ws || ws_bytes < gzip_decode_ws_bytes(a, n)) return hipErrorInvalidValue;
+        if (hipError_t e = verify_reset(varea, n, s); e != hipSuccess) return e;
+    }
+    hipError_t e;
+    if (serial) e = launch_inflate(a, d_chunks, n, d_status, ws, ws_bytes, s);
+    else if (par) e = launch_inflate_par(a, d_chunks, n, d_status, ws, ws_bytes, s);
+    else e = launch_inflate_wave(a, d_chunks, n, d_status, ws, ws_bytes, s);
+    if (e != hipSuccess || !verify) return e;
+    return launch_crc32_verify(a, d_chunks, n, d_status, varea, s);
 }
 
 }  // namespace zcg

@@ -503,11 +503,14 @@ __device__ __attribute__((always_inline)) int read_block_header(BitIn& b, bool* 
 // given is the rest of flate2's current 32 KiB BufReader window.
 template <int LB = INF_LBITS, u32 LCAP = INF_LTAB, int DB = INF_DBITS, u32 DCAP = INF_DTAB>
 __device__ __attribute__((always_inline)) int inf_lookahead(BitIn& b, bool last, bool at_header, u8* lens, HuffLds* lh,
-                             u32* ltab, HuffLds* dh, u32* dtab) {
+                             u32* ltab, HuffLds* dh, u32* dtab, bool* at_end) {
+    // *at_end: R_OK because the stream ended (the final block's last bit is
+    // consumed), not because the next step would emit a byte
+    *at_end = false;
     for (;;) {
         if (at_header) {  // after a stored block: straight to the next header
             at_header = false;
-            if (last) return R_OK;
+            if (last) { *at_end = true; return R_OK; }
             u32 type = 0, slen = 0;
             int r = read_block_header<LB, LCAP, DB, DCAP>(b, &last, &type, &slen, lens, lh, ltab, dh, dtab);
             if (r != R_OK) return r;
@@ -535,7 +538,7 @@ __device__ __attribute__((always_inline)) int inf_lookahead(BitIn& b, bool last,
         }
         // end of block: the next block header is parsed without output
         for (;;) {
-            if (last) return R_OK;  // stream end
+            if (last) { *at_end = true; return R_OK; }  // stream end
             u32 type = 0, slen = 0;
             r = read_block_header<LB, LCAP, DB, DCAP>(b, &last, &type, &slen, lens, lh, ltab, dh, dtab);
             if (r != R_OK) return r;
@@ -614,19 +617,35 @@ __device__ __forceinline__ bool inf_open(const zcg_chunk& ch, u64 D, DType t, In
 // produced, boundary = the output filled exactly at a token boundary (then
 // zlib looks ahead, inf_lookahead, inside inf_lookahead_limit), last /
 // after_stored = the block the loop stopped in.  Returns the chunk's status.
+// Under ZCG_FLAG_VERIFY_GZIP_TRAILER (rules in zchunk_gpu.h) the look-ahead
+// walks to the member's end with the whole input as its limit, the trailer is
+// read where the stream ended, and `rec` receives the expected CRC32.
 template <int LB = INF_LBITS, u32 LCAP = INF_LTAB, int DB = INF_DBITS, u32 DCAP = INF_DTAB>
 __device__ __attribute__((always_inline)) int inf_close(BitIn& b, const InfMember& m, int r, u64 P, u64 D, bool boundary,
                                                         bool last, bool after_stored, u8* lens, HuffLds* lh, u32* ltab,
-                                                        HuffLds* dh, u32* dtab) {
+                                                        HuffLds* dh, u32* dtab, u32 vflags, VerifyRec* rec) {
+    const bool verify = (vflags & ZCG_FLAG_VERIFY_GZIP_TRAILER) != 0;
+    int la = R_EXHAUSTED;  // (what a look-ahead that cannot start amounts to)
+    bool at_end = false;
     if (r == R_OK && P >= D && boundary) {
-        b.limit = inf_lookahead_limit(m.h, b.consumed, m.n_in);
+        b.limit = verify ? m.n_ds * 8 : inf_lookahead_limit(m.h, b.consumed, m.n_in);
         if (b.limit >= b.consumed) {
-            const int la = inf_lookahead<LB, LCAP, DB, DCAP>(b, last, after_stored, lens, lh, ltab, dh, dtab);
+            la = inf_lookahead<LB, LCAP, DB, DCAP>(b, last, after_stored, lens, lh, ltab, dh, dtab, &at_end);
             if (la == R_INVALID) r = R_INVALID;
         }
     }
     if (r == R_INVALID) return ZCG_ERR_INVALID_DATA;
     if (r == R_EXHAUSTED || P < D) return ZCG_ERR_UNEXPECTED_EOF;
+    if (!verify) return ZCG_OK;
+    // the chunk decodes OK: the member's end and its trailer
+    if (!boundary) return ZCG_ERR_INVALID_DATA;       // full inside a match / a stored block
+    if (la == R_EXHAUSTED) return ZCG_ERR_UNEXPECTED_EOF;
+    if (!at_end) return ZCG_ERR_INVALID_DATA;         // the next step would emit a byte
+    const u64 tr = m.h + (b.consumed + 7) / 8;
+    if (tr + 8 > m.n_in) return ZCG_ERR_UNEXPECTED_EOF;
+    const u8* const tp = m.ds - m.h + tr;
+    if (ld32(tp + 4) != (u32)D) return ZCG_ERR_INVALID_DATA;
+    if (threadIdx.x == 0) *rec = VerifyRec{V_CHECK, ld32(tp)};
     return ZCG_OK;
 }
 

@@ -935,7 +935,9 @@ __global__ __launch_bounds__(PI_NL, ZCG_INF_WPE) void inflate_par_kernel(const z
         }
     }
     // zlib's post-N look-ahead (all waves, identical)
-    st = inf_close(b, m, r, P, D, boundary, last, after_stored, L.lens, &L.lh, L.ltab, &L.dh, L.dtab);
+    // (under the verify flag the records sit between the owner words and the pools)
+    st = inf_close(b, m, r, P, D, boundary, last, after_stored, L.lens, &L.lh, L.ltab, &L.dh, L.dtab, vflags,
+                   (VerifyRec*)((u8*)owner + PI_OWNER_BYTES) + c);
     if (t.isbool) {  // byte != 0 over the whole decoded chunk, after the last round
         __syncthreads();
         wave_transform<PI_NL>(dst, P < D ? P : D, DType{1, 0, 1}, tid);
@@ -963,10 +965,11 @@ extern "C" int zcg__debug_inflate_counters(unsigned long long* out, int reset) {
 }
 
 uint64_t inflate_par_ws_bytes(const zcg_array* a, uint32_t n) {
-    (void)a;
     if (n == 0) return 0;
-    return PI_OWNER_BYTES + (u64)PI_NSLOT * PI_SLOT_WORDS * 4;
+    return PI_OWNER_BYTES + (gzip_verify(a) ? verify_ws_bytes(n) : 0) + (u64)PI_NSLOT * PI_SLOT_WORDS * 4;
 }
+
+void* inflate_par_verify_area(void* ws) { return (u8*)ws + PI_OWNER_BYTES; }
 
 const char* cfg_inflate_par() {
     return "inflate_par:PF=" ZCG_STR(ZCG_INF_PF) ",FU=" ZCG_STR(ZCG_INF_FU) ",WPE=" ZCG_STR(ZCG_INF_WPE);
@@ -976,14 +979,14 @@ hipError_t launch_inflate_par(const zcg_array* a, const zcg_chunk* d_chunks, uin
                               int32_t* d_status, void* ws, uint64_t ws_bytes, hipStream_t s) {
     if (n == 0) return hipSuccess;
     if (!ws || ws_bytes < inflate_par_ws_bytes(a, n)) return hipErrorInvalidValue;
-    const DType t = make_dtype(a->dtype);
+    const DType t = gzip_decode_dtype(a);
     const u64 D = a->chunk_num_elements * (u64)t.es;
     const size_t lds = sizeof(ParLds);
     if (hipError_t e = lds_attr_once((const void*)inflate_par_kernel, (int)lds); e != hipSuccess) return e;
     u32* owner = (u32*)ws;  // the workspace is shared by the stream's codecs: clear the owners
     hipError_t e = hipMemsetAsync(owner, 0, PI_OWNER_BYTES, s);
     if (e != hipSuccess) return e;
-    gu32* pools = (gu32*)((u8*)ws + PI_OWNER_BYTES);
+    gu32* pools = (gu32*)((u8*)ws + PI_OWNER_BYTES + (gzip_verify(a) ? verify_ws_bytes(n) : 0));
     hipLaunchKernelGGL(inflate_par_kernel, dim3(n), dim3(PI_NL), lds, s, d_chunks, n, D, t,
                        a->compression.flags, d_status, owner, pools);
     return hipGetLastError();

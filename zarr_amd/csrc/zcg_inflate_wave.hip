@@ -1302,8 +1302,9 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
         wsync();
         if (!after_stored) iw_tab_serial(L);
     }
+    // (under the verify flag the records sit between the owner words and the pools)
     st = inf_close<W_LB, W_LCAP, W_DB, W_DCAP>(b, m, r, P, D, boundary, last, after_stored, L.u.h.lens, &L.u.h.lh, L.ltab,
-                                               &L.u.h.dh, L.dtab);
+                                               &L.u.h.dh, L.dtab, vflags, (VerifyRec*)((u8*)owner + IW_OWNER_BYTES) + c);
     if (t.isbool) {  // byte != 0 over the whole decoded chunk (the committed bytes were the window)
         __syncthreads();
         wave_transform<64>(dst, P < D ? P : D, DType{1, 0, 1}, lane);
@@ -1348,16 +1349,17 @@ const char* cfg_inflate_wave() {
 }
 
 uint64_t inflate_wave_ws_bytes(const zcg_array* a, uint32_t n) {
-    (void)a;
     if (n == 0) return 0;
-    return IW_OWNER_BYTES + (u64)iw_nslot(n) * IW_SLOT_WORDS * 4;
+    return IW_OWNER_BYTES + (gzip_verify(a) ? verify_ws_bytes(n) : 0) + (u64)iw_nslot(n) * IW_SLOT_WORDS * 4;
 }
+
+void* inflate_wave_verify_area(void* ws) { return (u8*)ws + IW_OWNER_BYTES; }
 
 hipError_t launch_inflate_wave(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n,
                                int32_t* d_status, void* ws, uint64_t ws_bytes, hipStream_t s) {
     if (n == 0) return hipSuccess;
     if (!ws || ws_bytes < inflate_wave_ws_bytes(a, n)) return hipErrorInvalidValue;
-    const DType t = make_dtype(a->dtype);
+    const DType t = gzip_decode_dtype(a);
     const u64 D = a->chunk_num_elements * (u64)t.es;
     const size_t lds = sizeof(IwLds);
     if (hipError_t e = lds_attr_once((const void*)inflate_wave_kernel, (int)lds); e != hipSuccess) return e;
@@ -1365,7 +1367,7 @@ hipError_t launch_inflate_wave(const zcg_array* a, const zcg_chunk* d_chunks, ui
     u32* owner = (u32*)ws;
     hipError_t e = hipMemsetAsync(owner, 0, (size_t)nslot * 4, s);
     if (e != hipSuccess) return e;
-    gu32* pools = (gu32*)((u8*)ws + IW_OWNER_BYTES);
+    gu32* pools = (gu32*)((u8*)ws + IW_OWNER_BYTES + (gzip_verify(a) ? verify_ws_bytes(n) : 0));
     hipLaunchKernelGGL(inflate_wave_kernel, dim3(n), dim3(64), lds, s, d_chunks, n, D, t,
                        a->compression.flags, d_status, owner, nslot, pools);
     return hipGetLastError();

@@ -243,9 +243,30 @@ __device__ __forceinline__ int lz4_next_header_check(const u8* s, u64 n, u64 pos
     return ZCG_OK;
 }
 
+// ZCG_FLAG_VERIFY_LZ4_CONTENT on a chunk that decoded OK (rules in
+// zchunk_gpu.h): `end` = the stream position after the block that reached D,
+// LZ_END_OVER when a block decoded past D.  Returns the status; *rc = what the
+// verify kernel still has to do (XXH32 against the stored word, or only the
+// deferred element transform when the frame carries no content checksum).
+constexpr u64 LZ_END_OVER = ~0ull;
+__device__ inline int lz4_verify_tail(const u8* s, u64 n, u64 end, u32 flags, u64 D, VerifyRec* rc) {
+    if (end == LZ_END_OVER) return ZCG_ERR_INVALID_DATA;
+    if (end + 4 > n) return ZCG_ERR_UNEXPECTED_EOF;
+    if (ld32(s + end) != 0) return ZCG_ERR_INVALID_DATA;  // a further block
+    if ((flags & F_CONTENT_CKSUM) && end + 8 > n) return ZCG_ERR_UNEXPECTED_EOF;
+    if (flags & F_CONTENT_SIZE) {
+        const u64 declared = (u64)ld32(s + 6) | ((u64)ld32(s + 10) << 32);
+        if (declared != D) return ZCG_ERR_INVALID_DATA;
+    }
+    *rc = (flags & F_CONTENT_CKSUM) ? VerifyRec{V_CHECK, ld32(s + end + 4)} : VerifyRec{V_PASS, 0u};
+    return ZCG_OK;
+}
+
 // Serial decode of a whole frame by one lane, exact output offsets.  Used for
 // linked-block frames and whenever the per-block placement guess failed.
-__device__ int lz4_frame_serial(const u8* s, u64 n, u8* dst, u64 D, u32 vflags) {
+// *end (when the result is ZCG_OK): see lz4_verify_tail.
+__device__ int lz4_frame_serial(const u8* s, u64 n, u8* dst, u64 D, u32 vflags, u64* end) {
+    *end = LZ_END_OVER;
     Lz4Hdr h = lz4_parse_header(s, n);
     if (h.st != ZCG_OK) return h.st;
     u64 pos = h.hdr_len, out = 0;
@@ -284,7 +305,10 @@ __device__ int lz4_frame_serial(const u8* s, u64 n, u8* dst, u64 D, u32 vflags) 
         }
         out += got;
         pos += need;
-        if (out == D) return lz4_next_header_check(s, n, pos, h.bmax);
+        if (out == D) {
+            *end = pos;
+            return lz4_next_header_check(s, n, pos, h.bmax);
+        }
     }
     return ZCG_OK;
 }
@@ -1057,7 +1081,7 @@ __global__ __launch_bounds__(64) void lz4_finish_kernel(const zcg_chunk* __restr
                                                         DType t, u32 vflags, u32 S,
                                                         const Lz4ChunkInfo* __restrict__ info,
                                                         const Lz4Slot* __restrict__ slots,
-                                                        i32* __restrict__ status) {
+                                                        i32* __restrict__ status, VerifyRec* __restrict__ vrec) {
     const u32 c = blockIdx.x;
     if (c >= n) return;
     const int lane = lane_id();
@@ -1066,6 +1090,7 @@ __global__ __launch_bounds__(64) void lz4_finish_kernel(const zcg_chunk* __restr
         const Lz4ChunkInfo ci = info[c];
         const Lz4Slot* sl = slots + (u64)c * S;
         int st = ci.st;
+        u64 end = LZ_END_OVER;  // (verify) where the block that reached D ended
         if (st == ZCG_OK && D > 0) {
             const u32 ns = ci.nslot, bmax = ci.bmax;
             u64 total = 0;
@@ -1080,6 +1105,7 @@ __global__ __launch_bounds__(64) void lz4_finish_kernel(const zcg_chunk* __restr
                 const u64 pos = (u64)sl[ns - 1].src_off + (sl[ns - 1].bs & 0x7FFFFFFFu) +
                                 ((ci.flags & F_BLOCK_CKSUM) ? 4 : 0);
                 st = lz4_next_header_check((const u8*)ch.src, ch.src_len, pos, bmax);
+                end = pos;
             }
             if (st == ZCG_OK && total < D) {
                 // frame ended / input ran out before N bytes; a short last
@@ -1092,7 +1118,15 @@ __global__ __launch_bounds__(64) void lz4_finish_kernel(const zcg_chunk* __restr
         }
         if (st == -1) {
             const zcg_chunk ch = chunks[c];
-            st = lz4_frame_serial((const u8*)ch.src, ch.src_len, (u8*)ch.dst, D, vflags);
+            st = lz4_frame_serial((const u8*)ch.src, ch.src_len, (u8*)ch.dst, D, vflags, &end);
+        }
+        if (vrec) {  // ZCG_FLAG_VERIFY_LZ4_CONTENT
+            VerifyRec rc{V_SKIP, 0u};
+            if (st == ZCG_OK && D > 0) {
+                const zcg_chunk ch = chunks[c];
+                st = lz4_verify_tail((const u8*)ch.src, ch.src_len, end, ci.flags, D, &rc);
+            }
+            vrec[c] = rc;
         }
         status[c] = st;
         st_s = st;
@@ -1104,23 +1138,36 @@ __global__ __launch_bounds__(64) void lz4_finish_kernel(const zcg_chunk* __restr
     }
 }
 
+// The decoder's own workspace; under ZCG_FLAG_VERIFY_LZ4_CONTENT the verify
+// area (per-chunk records) follows it.
+static uint64_t lz4_decoder_ws_bytes(uint32_t n, u64 S) {
+    return ((u64)n * sizeof(Lz4ChunkInfo) + 255) / 256 * 256 + (u64)n * S * sizeof(Lz4Slot);
+}
+
 uint64_t lz4_decode_ws_bytes(const zcg_array* a, uint32_t n) {
     const DType t = make_dtype(a->dtype);
     const u64 D = a->chunk_num_elements * (u64)t.es;
     u64 S = (D + LZ4_MIN_BMAX - 1) / LZ4_MIN_BMAX;
     if (S < 1) S = 1;
-    return ((u64)n * sizeof(Lz4ChunkInfo) + 255) / 256 * 256 + (u64)n * S * sizeof(Lz4Slot);
+    return lz4_decoder_ws_bytes(n, S) + (lz4_verify(a) && n ? verify_ws_bytes(n) : 0);
 }
 
 hipError_t launch_lz4_decode(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n, int32_t* d_status,
                              void* ws, uint64_t ws_bytes, hipStream_t s, hipStream_t side, hipEvent_t fork,
                              hipEvent_t join) {
     if (n == 0) return hipSuccess;
-    const DType t = make_dtype(a->dtype);
+    DType t = make_dtype(a->dtype);
     const u64 D = a->chunk_num_elements * (u64)t.es;
     u64 S = (D + LZ4_MIN_BMAX - 1) / LZ4_MIN_BMAX;
     if (S < 1) S = 1;
     if (S > 65536 || ws_bytes < lz4_decode_ws_bytes(a, n)) return hipErrorInvalidValue;
+    const bool verify = lz4_verify(a);
+    void* const varea = (u8*)ws + lz4_decoder_ws_bytes(n, S);
+    if (verify) {  // the verify kernel applies the element transform after it has read the bytes
+        t.swap = 0;
+        t.isbool = 0;
+        if (hipError_t e = verify_reset(varea, n, s); e != hipSuccess) return e;
+    }
     Lz4ChunkInfo* info = (Lz4ChunkInfo*)ws;
     Lz4Slot* slots = (Lz4Slot*)((u8*)ws + ((u64)n * sizeof(Lz4ChunkInfo) + 255) / 256 * 256);
     hipLaunchKernelGGL(lz4_frames_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d_chunks, n, D, (u32)S, info,
@@ -1162,8 +1209,10 @@ hipError_t launch_lz4_decode(const zcg_array* a, const zcg_chunk* d_chunks, uint
         }
     }
     hipLaunchKernelGGL(lz4_finish_kernel, dim3(n), dim3(64), 0, s, d_chunks, n, D, t, a->compression.flags,
-                       (u32)S, (const Lz4ChunkInfo*)info, (const Lz4Slot*)slots, d_status);
-    return hipGetLastError();
+                       (u32)S, (const Lz4ChunkInfo*)info, (const Lz4Slot*)slots, d_status,
+                       verify ? (VerifyRec*)varea : (VerifyRec*)nullptr);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess || !verify) return e;
+    return launch_xxh32_verify(a, d_chunks, n, d_status, varea, s);
 }
 
 const char* cfg_lz4_dec() {

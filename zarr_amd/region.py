@@ -138,7 +138,7 @@ def scatter_region(meta: ArrayMetadata, bbox: BoundingBox, es: int, table, box, 
 WRITE_BATCH_BYTES = 1 << 30
 
 
-def _decode_visited(hier, path_name: str, meta: ArrayMetadata, bbox: BoundingBox, device: int):
+def _decode_visited(hier, path_name: str, meta: ArrayMetadata, bbox: BoundingBox, device: int, flags: int = 0):
     """Read + batch-decode the chunks bounded_coord_iter visits, through the
     store's get() semantics (shared flock, filesystem.rs:201-210) straight
     into device slots (zcg_store_read_chunks_device); returns (table tensor,
@@ -157,7 +157,8 @@ def _decode_visited(hier, path_name: str, meta: ArrayMetadata, bbox: BoundingBox
         D = meta.get_chunk_num_elements() * es
         slots = torch.empty(max(len(coords) * D, 1), dtype=torch.uint8, device=dev)
         ptrs = [slots.data_ptr() + i * D for i in range(len(coords))]
-        st = store_read_device(meta, [hier.chunk_path(path_name, meta, c) for c in coords], ptrs, device)
+        st = store_read_device(meta, [hier.chunk_path(path_name, meta, c) for c in coords], ptrs, device,
+                               flags=flags)
         for i, c in enumerate(coords):
             if st[i] == _native.ABSENT:
                 continue  # read_chunk -> Ok(None)
@@ -169,9 +170,11 @@ def _decode_visited(hier, path_name: str, meta: ArrayMetadata, bbox: BoundingBox
 
 
 def read_ndarray(hier, path_name: str, meta: ArrayMetadata, bbox: BoundingBox, t, device: int = 0,
-                 as_tensor: bool = False):
+                 as_tensor: bool = False, flags: int = 0):
     """ZarrNdarrayReader::read_ndarray (ndarray.rs:153-174): an array of the
-    box's shape in the chunk memory order, fill value where no chunk is."""
+    box's shape in the chunk memory order, fill value where no chunk is.
+    `flags`: decode flags; under _native.FLAG_VERIFY* a chunk that fails its
+    checksum raises InvalidData."""
     import torch
     check_array_type(t, meta)
     if len(bbox.offset) != meta.get_ndim():
@@ -182,7 +185,7 @@ def read_ndarray(hier, path_name: str, meta: ArrayMetadata, bbox: BoundingBox, t
     st = _strides(bbox.shape, order)
     total = int(np.prod(bbox.shape)) if bbox.shape else 1
     out = torch.empty(max(total * es, 1), dtype=torch.uint8, device=torch.device("cuda", device))
-    table, keep = _decode_visited(hier, path_name, meta, bbox, device)
+    table, keep = _decode_visited(hier, path_name, meta, bbox, device, flags)
     assemble_region(meta, bbox, es, table, out, st, True, effective_fill_value(meta, dt), device)
     torch.cuda.synchronize(device)
     if as_tensor:
@@ -192,7 +195,7 @@ def read_ndarray(hier, path_name: str, meta: ArrayMetadata, bbox: BoundingBox, t
 
 
 def read_ndarray_into(hier, path_name: str, meta: ArrayMetadata, bbox: BoundingBox, arr: np.ndarray, t,
-                      device: int = 0) -> None:
+                      device: int = 0, flags: int = 0) -> None:
     """ZarrNdarrayReader::read_ndarray_into (ndarray.rs:176-268): elements
     that no present chunk covers keep their values; `arr` may be any
     writable view of the box's shape."""
@@ -208,7 +211,7 @@ def read_ndarray_into(hier, path_name: str, meta: ArrayMetadata, bbox: BoundingB
     st = _strides(bbox.shape, "C")
     dev = torch.device("cuda", device)
     out = torch.from_numpy(staged.reshape(-1).view(np.uint8).copy() if staged.size else np.zeros(1, np.uint8)).to(dev)
-    table, keep = _decode_visited(hier, path_name, meta, bbox, device)
+    table, keep = _decode_visited(hier, path_name, meta, bbox, device, flags)
     assemble_region(meta, bbox, es, table, out, st, False, 0, device)
     torch.cuda.synchronize(device)
     if staged.size:

@@ -108,15 +108,17 @@ class FilesystemHierarchy:
 
     # ---- chunks (the path) ---------------------------------------------------------
     def read_chunk(self, path_name: str, array_meta: ArrayMetadata, grid_position, t,
-                   device: int = 0) -> Optional[SliceDataChunk]:
-        """storage.rs:206-235: get() under a shared flock; None if absent."""
-        return self.read_chunks(path_name, array_meta, [grid_position], t, device=device, io_threads=1)[0]
+                   device: int = 0, flags: int = 0) -> Optional[SliceDataChunk]:
+        """storage.rs:206-235: get() under a shared flock; None if absent.
+        `flags`: decode flags (_native.FLAG_VERIFY* check the stream's checksum)."""
+        return self.read_chunks(path_name, array_meta, [grid_position], t, device=device, io_threads=1,
+                                flags=flags)[0]
 
     def read_chunk_into(self, path_name: str, array_meta: ArrayMetadata, grid_position,
-                        chunk: SliceDataChunk, t, device: int = 0) -> Optional[bool]:
+                        chunk: SliceDataChunk, t, device: int = 0, flags: int = 0) -> Optional[bool]:
         """storage.rs:237-267: None if absent, else the chunk reinitialised
         (ReinitDataChunk::reinitialize, chunk.rs:91-94) with the decoded data."""
-        got = self.read_chunk(path_name, array_meta, grid_position, t, device=device)
+        got = self.read_chunk(path_name, array_meta, grid_position, t, device=device, flags=flags)
         if got is None:
             return None
         chunk.grid_position = list(grid_position)
@@ -130,15 +132,17 @@ class FilesystemHierarchy:
         return True
 
     def read_chunks(self, path_name: str, array_meta: ArrayMetadata, grid_positions, t,
-                    device: int = 0, io_threads: int = 16) -> List[Optional[SliceDataChunk]]:
+                    device: int = 0, io_threads: int = 16, flags: int = 0) -> List[Optional[SliceDataChunk]]:
         """Batched read_chunk through the native store path
         (zcg_store_read_chunks): files read under a shared flock into pinned
         staging by `io_threads` host threads, pipelined with H2D, the batch
-        decode and D2H on two streams.  A missing chunk is None."""
+        decode and D2H on two streams.  A missing chunk is None.  With
+        _native.FLAG_VERIFY* in `flags` a chunk whose checksum does not match
+        raises InvalidData like any other corrupt chunk."""
         for g in grid_positions:
             assert array_meta.in_bounds(g)  # storage.rs:217 (a panic there)
         paths = [self.chunk_path(path_name, array_meta, g) for g in grid_positions]
-        arrs, status = store_read(array_meta, paths, t, device=device, io_threads=io_threads)
+        arrs, status = store_read(array_meta, paths, t, device=device, io_threads=io_threads, flags=flags)
         out: List[Optional[SliceDataChunk]] = []
         for g, a, st in zip(grid_positions, arrs, status):
             if st == _native.ABSENT:
@@ -205,7 +209,7 @@ def _host_buffer(nbytes: int, pinned: bool) -> np.ndarray:
 
 
 def store_read(array_meta: ArrayMetadata, paths: Sequence[str], t, device: int = 0, io_threads: int = 16,
-               pinned=None):
+               pinned=None, flags: int = 0):
     """zcg_store_read_chunks: (list of element arrays, status array).  The
     arrays are views of one host allocation, page-locked for large batches."""
     check_array_type(t, array_meta)
@@ -221,7 +225,7 @@ def store_read(array_meta: ArrayMetadata, paths: Sequence[str], t, device: int =
     dp = (ctypes.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
     cp, keep = _cstrs(paths)
     st = np.zeros(max(n, 1), np.int32)
-    arr = abi_array(array_meta)
+    arr = abi_array(array_meta, flags)
     r = ctx.lib.zcg_store_read_chunks(ctx.handle, ctypes.byref(arr), n, ctypes.addressof(cp),
                                       ctypes.addressof(dp), st.ctypes.data, io_threads)
     if r != _native.OK:
@@ -255,7 +259,7 @@ def store_write(array_meta: ArrayMetadata, paths: Sequence[str], datas, device: 
 
 
 def store_read_device(array_meta: ArrayMetadata, paths: Sequence[str], d_ptrs: Sequence[int], device: int = 0,
-                      io_threads: int = 16):
+                      io_threads: int = 16, flags: int = 0):
     """zcg_store_read_chunks_device: chunk files (shared flock, reader pool,
     pinned staging) decoded straight into the device slots `d_ptrs`
     (N*elem_size bytes each); returns the status array."""
@@ -264,7 +268,7 @@ def store_read_device(array_meta: ArrayMetadata, paths: Sequence[str], d_ptrs: S
     dp = (ctypes.c_void_p * max(n, 1))(*[int(p) for p in d_ptrs])
     cp, keep = _cstrs(paths)
     st = np.zeros(max(n, 1), np.int32)
-    arr = abi_array(array_meta)
+    arr = abi_array(array_meta, flags)
     r = ctx.lib.zcg_store_read_chunks_device(ctx.handle, ctypes.byref(arr), n, ctypes.addressof(cp),
                                              ctypes.addressof(dp), st.ctypes.data, io_threads)
     if r != _native.OK:
