@@ -301,6 +301,53 @@ int zcg_read_region(zcg_ctx* ctx, const zcg_region* r, const void* const* d_chun
 int zcg_write_region(zcg_ctx* ctx, const zcg_region* r, void* const* d_chunk_table,
                      const void* d_in, void* stream);
 
+/* ---- many bounding boxes in one call ----------------------------------
+ * The reference's users read many small boxes from one array (tiles, patches,
+ * random crops), one read_ndarray each.  zcg_read_regions assembles n_boxes
+ * boxes of one common shape in one launch: each box has its own offset and its
+ * own output view, all read one shared chunk table. */
+typedef struct zcg_box {
+    uint64_t offset[ZCG_MAX_DIMS]; /* bbox_offset of this box, per array dim   */
+    void* out;                     /* DEVICE base (element (0,..,0)) of its view */
+} zcg_box;
+
+/* Union of the boxes' zcg_region_grid ranges: the smallest grid range
+ * lo[d] .. lo[d]+n[d] that holds every chunk some box visits (r->bbox_offset
+ * is ignored; `offsets` is a host array of n_boxes*ndim, box-major; lo and n
+ * are host arrays of ndim).  Returns the number of table entries (product of
+ * n); 0, with lo = n = 0, if no box visits a chunk. */
+uint64_t zcg_regions_grid(const zcg_region* r, const uint64_t* offsets, uint32_t n_boxes,
+                          uint64_t* lo, uint64_t* n);
+
+/* `r` gives ndim, elem_size, chunk_order, fill_missing, array_shape,
+ * chunk_shape, bbox_shape, out_strides and fill_value for every box;
+ * r->bbox_offset is ignored.  d_chunk_table covers the grid range
+ * table_lo[d] .. table_lo[d]+table_n[d] (host arrays of ndim), C order with
+ * dim 0 slowest, NULL = chunk absent: zcg_read_region's convention.  d_boxes
+ * and d_status are DEVICE arrays of n_boxes entries.
+ *  - Per-box equivalence: for every box whose status is ZCG_OK the bytes
+ *    written to its view are exactly those zcg_read_region writes for a
+ *    zcg_region with that bbox_offset and a table holding the same pointers
+ *    over that box's own zcg_region_grid range: clipping to array_shape,
+ *    overhanging edge chunks, fill versus untouched.  A chunk inside the table
+ *    but outside the box's own grid range is never read.
+ *  - A box whose own grid range is not inside the table's range gets
+ *    ZCG_ERR_INVALID_INPUT; nothing of it is written, and the other boxes are
+ *    unaffected.
+ *  - A box that visits no chunk is ZCG_OK, and filled when fill_missing is set.
+ *  - n_boxes == 0, or a zero extent in bbox_shape, returns ZCG_OK and launches
+ *    nothing (d_status is not written).
+ *  - bbox_shape[d] + chunk_shape[d] - 1 >= 2^32 returns ZCG_ERR_UNSUPPORTED
+ *    (the single-box limit, for any offset).
+ *  - Asynchronous on `stream`; the number of launches does not depend on
+ *    n_boxes; the call allocates nothing and does not synchronize with the
+ *    host.  d_boxes is read when the kernel runs, so the call can be captured
+ *    in a graph and a replay sees new offsets and outputs.
+ *  - Output views of different boxes that overlap are the caller's business. */
+int zcg_read_regions(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+                     const void* const* d_chunk_table, const zcg_box* d_boxes, uint32_t n_boxes,
+                     int32_t* d_status, void* stream);
+
 /* ---- FilesystemHierarchy chunk files ---------------
  * The e2e path's two ends: chunk files read into pinned staging by a pool of
  * `io_threads` host threads (open + shared flock + read, as ReadableStore::get,
@@ -405,6 +452,44 @@ uint64_t zcg_chunk_key(const char* path, const char* separator, const uint64_t* 
  * `out` (cap bytes, NUL-terminated) may be NULL to query the length, and a cap
  * below path_len + 1 gives ZCG_ERR_OUTPUT_TOO_SMALL.  Returns ZCG_OK. */
 int zcg_store_path(const char* root, const char* key, char* out, uint64_t cap, uint64_t* path_len);
+
+/* ---- read_ndarray for many boxes, from the store to the boxes ------------
+ * ZarrNdarrayReader::read_ndarray (ndarray.rs:153-268) for n_boxes boxes of one
+ * shape `box_shape` (ndim) at `offsets` (n_boxes*ndim, box-major) of the array
+ * `path` under the FilesystemHierarchy `root`, in one blocking call: the
+ * chunks the boxes visit (the union of bounded_coord_iter's coordinates,
+ * deduplicated) are each read (zcg_chunk_key + zcg_store_path, shared flock)
+ * and decoded once, and one zcg_read_regions launch assembles every box.
+ *  - decode flags come from meta->array.compression.flags (the verify flags
+ *    work), element type and chunk order from `meta`, the fill value is
+ *    meta->fill_value when has_fill_value, else 0;
+ *  - an absent chunk is a NULL table entry; the first chunk whose status is
+ *    neither ZCG_OK nor ZCG_ABSENT makes the call return that status,
+ *    zcg_last_error names its grid position, and no box is guaranteed written;
+ *  - a visited chunk outside the array's chunk grid (read_chunk panics there,
+ *    storage.rs:217; the grid extent is the reference's u64_ceil_div,
+ *    lib.rs:340-342, over-count included) -> ZCG_ERR_INVALID_INPUT before any
+ *    file is read;
+ *  - ndim != chunk_ndim -> ZCG_ERR_INVALID_DATA; a raw (rN) element type ->
+ *    ZCG_ERR_INVALID_INPUT; a union chunk table above 2^24 entries ->
+ *    ZCG_ERR_UNSUPPORTED (zcg_last_error says so);
+ *  - device memory: boxes are taken in consecutive groups whose unique chunks
+ *    need at most slot_budget_bytes of decoded slots (0 = 4 GiB); a single box
+ *    that alone exceeds the budget runs as its own group; a chunk two groups
+ *    share is decoded in each.
+ * zcg_store_read_boxes_device writes box i to the DEVICE view d_outs[i]
+ * (out_strides per array dim, in elements; fill_missing as in zcg_region).
+ * zcg_store_read_boxes writes box i to the HOST buffer outs[i], dense in the
+ * chunk memory order and filled where no chunk is (read_ndarray's array), by
+ * way of a device staging buffer and one D2H per group; n_boxes = 1 is the
+ * reference's read_ndarray. */
+int zcg_store_read_boxes_device(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                                const uint64_t* box_shape, const int64_t* out_strides, uint32_t fill_missing,
+                                const uint64_t* offsets, void* const* d_outs, uint32_t n_boxes,
+                                uint64_t slot_budget_bytes, uint32_t io_threads);
+int zcg_store_read_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                         const uint64_t* box_shape, const uint64_t* offsets, void* const* outs, uint32_t n_boxes,
+                         uint64_t slot_budget_bytes, uint32_t io_threads);
 
 #ifdef __cplusplus
 }

@@ -13,12 +13,13 @@ from .metadata import ArrayMetadata, u64_ceil_div
 from .chunk import (DefaultChunk, SliceDataChunk, VecDataChunk, ZarrIOError, check_array_type,
                     read_chunks_host)
 from .storage import FilesystemHierarchy, get_chunk_key
+from .region import BoundingBox, read_ndarray, read_ndarrays
 from ._native import NativeUnavailable
 
 __all__ = [
-    "ArrayMetadata", "Bzip2", "CompressionType", "DataType", "DefaultChunk", "Endian",
+    "ArrayMetadata", "BoundingBox", "Bzip2", "CompressionType", "DataType", "DefaultChunk", "Endian",
     "ExtendedDataType", "FilesystemHierarchy", "GZIP_CODEC_ID", "Gzip", "Lz4", "MetadataError",
     "NATIVE_ENDIAN", "NativeUnavailable", "REFLECTED_TYPES", "Raw", "SliceDataChunk",
     "VecDataChunk", "Xz", "ZarrIOError", "check_array_type", "effective_type", "get_chunk_key",
-    "read_chunks_host", "u64_ceil_div", "zarr_type",
+    "read_chunks_host", "read_ndarray", "read_ndarrays", "u64_ceil_div", "zarr_type",
 ]

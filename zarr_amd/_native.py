@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = (
     "zcg_multi_read_chunks_host", "zcg_multi_store_read_chunks", "zcg_multi_store_write_chunks",
     "zcg_array_meta_from_json", "zcg_chunk_key", "zcg_store_path",
     "zcg_store_read_chunks_device", "zcg_store_write_chunks_device",
+    "zcg_regions_grid", "zcg_read_regions", "zcg_store_read_boxes_device", "zcg_store_read_boxes",
 )
 
 
@@ -88,6 +89,11 @@ class Region(ctypes.Structure):
                 ("out_strides", ctypes.c_int64 * MAX_DIMS), ("fill_value", ctypes.c_uint64)]
 
 
+class Box(ctypes.Structure):
+    """zcg_box: one bounding box of a batched read (offset per array dim, DEVICE output base)."""
+    _fields_ = [("offset", ctypes.c_uint64 * MAX_DIMS), ("out", ctypes.c_void_p)]
+
+
 class ArrayMeta(ctypes.Structure):
     _fields_ = [("array", Array), ("ndim", ctypes.c_uint32), ("chunk_ndim", ctypes.c_uint32),
                 ("chunk_order", ctypes.c_uint32), ("dtype_kind", ctypes.c_uint32),
@@ -100,6 +106,7 @@ class ArrayMeta(ctypes.Structure):
 assert ctypes.sizeof(Region) == 16 + 5 * 8 * MAX_DIMS + 8
 assert ctypes.sizeof(Compression) == 24 and ctypes.sizeof(Array) == 40
 assert ctypes.sizeof(Chunk) == 32
+assert ctypes.sizeof(Box) == 8 * MAX_DIMS + 8
 
 _lib = None
 _lock = threading.Lock()
@@ -183,6 +190,16 @@ def load_library(path: str = LIB_PATH):
         L.zcg_store_read_chunks_device.restype = ctypes.c_int
         L.zcg_store_write_chunks_device.argtypes = [vp, ctypes.POINTER(Array), u32, vp, vp, vp, u32]
         L.zcg_store_write_chunks_device.restype = ctypes.c_int
+        L.zcg_regions_grid.argtypes = [ctypes.POINTER(Region), vp, u32, vp, vp]
+        L.zcg_regions_grid.restype = u64
+        L.zcg_read_regions.argtypes = [vp, ctypes.POINTER(Region), vp, vp, vp, vp, u32, vp, vp]
+        L.zcg_read_regions.restype = ctypes.c_int
+        L.zcg_store_read_boxes_device.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
+                                                  vp, vp, u32, vp, vp, u32, u64, u32]
+        L.zcg_store_read_boxes_device.restype = ctypes.c_int
+        L.zcg_store_read_boxes.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
+                                           vp, vp, vp, u32, u64, u32]
+        L.zcg_store_read_boxes.restype = ctypes.c_int
         _lib = L
         return L
 

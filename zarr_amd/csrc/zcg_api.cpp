@@ -570,4 +570,84 @@ static int region_call(zcg_ctx* ctx, const zcg_region* r, const void* const* d_c
     return ZCG_OK;
 }
 
+uint64_t zcg_regions_grid(const zcg_region* r, const uint64_t* offsets, uint32_t n_boxes, uint64_t* lo,
+                          uint64_t* n) {
+    if (!r || r->ndim < 1 || r->ndim > ZCG_MAX_DIMS) return 0;
+    const uint32_t nd = r->ndim;
+    uint64_t ulo[ZCG_MAX_DIMS] = {0}, uhi[ZCG_MAX_DIMS] = {0};
+    bool any = false;
+    zcg_region one = *r;
+    for (uint32_t b = 0; b < n_boxes && offsets; b++) {
+        uint64_t blo[ZCG_MAX_DIMS], bn[ZCG_MAX_DIMS];
+        for (uint32_t d = 0; d < nd; d++) one.bbox_offset[d] = offsets[(size_t)b * nd + d];
+        if (zcg_region_grid(&one, blo, bn) == 0) continue;  // visits no chunk
+        for (uint32_t d = 0; d < nd; d++) {
+            ulo[d] = any ? std::min(ulo[d], blo[d]) : blo[d];
+            uhi[d] = any ? std::max(uhi[d], blo[d] + bn[d]) : blo[d] + bn[d];
+        }
+        any = true;
+    }
+    uint64_t cnt = any ? 1 : 0;
+    for (uint32_t d = 0; d < nd; d++) {
+        if (lo) lo[d] = ulo[d];
+        if (n) n[d] = uhi[d] - ulo[d];
+        cnt *= uhi[d] - ulo[d];
+    }
+    return cnt;
+}
+
+int zcg_read_regions(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+                     const void* const* d_chunk_table, const zcg_box* d_boxes, uint32_t n_boxes,
+                     int32_t* d_status, void* stream) {
+    if (!ctx || !r || r->ndim < 1 || r->ndim > ZCG_MAX_DIMS) return ZCG_ERR_INVALID_INPUT;
+    const uint32_t es = r->elem_size;
+    if (es != 1 && es != 2 && es != 4 && es != 8) return ZCG_ERR_INVALID_INPUT;
+    if (n_boxes == 0) return ZCG_OK;
+    const uint32_t nd = r->ndim;
+    RegionsArgs a{};
+    a.nd = nd;
+    a.es = es;
+    a.fill = r->fill_missing ? 1u : 0u;
+    a.V = 16 / es;
+    a.nboxes = n_boxes;
+    a.fillv = r->fill_value;
+    uint64_t tstr_arr[ZCG_MAX_DIMS], entries = 1;
+    for (int d = (int)nd - 1; d >= 0; d--) {
+        tstr_arr[d] = entries;
+        entries *= table_n ? table_n[d] : 0;
+    }
+    uint64_t total = 1, cst = 1;
+    for (uint32_t k = 0; k < nd; k++) {
+        const uint32_t d = r->chunk_order == 1 ? k : nd - 1 - k;  // fast-first
+        const uint64_t cs = r->chunk_shape[d], bs = r->bbox_shape[d];
+        if (cs == 0 || cs >= (1ull << 32)) return ZCG_ERR_INVALID_INPUT;
+        if (bs + cs - 1 >= (1ull << 32)) {
+            ctx->err = "regions: box extent + chunk extent along a dimension must stay below 2^32 elements";
+            return ZCG_ERR_UNSUPPORTED;
+        }
+        a.dim[k] = d;
+        a.bs[k] = (uint32_t)bs;
+        a.cs[k] = (uint32_t)cs;
+        a.as[k] = r->array_shape[d];
+        a.tlo[k] = table_lo ? table_lo[d] : 0;
+        a.tn[k] = table_n ? table_n[d] : 0;
+        a.tstr[k] = tstr_arr[d];
+        a.cstr[k] = cst;
+        a.ostr[k] = r->out_strides[d];
+        cst *= cs;
+        total *= bs;
+    }
+    a.total = total;
+    if (total == 0) return ZCG_OK;
+    if (!d_boxes || !d_status || (entries && !d_chunk_table)) return ZCG_ERR_INVALID_INPUT;
+    if (total > (1ull << 62) / n_boxes) {
+        ctx->err = "regions: n_boxes x box elements must stay below 2^62";
+        return ZCG_ERR_UNSUPPORTED;
+    }
+    (void)hipSetDevice(ctx->device);
+    const hipError_t e = launch_regions(a, d_chunk_table, d_boxes, d_status, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, e, "regions launch");
+    return ZCG_OK;
+}
+
 }  // extern "C"

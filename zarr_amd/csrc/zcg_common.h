@@ -267,6 +267,29 @@ struct RegionArgs {
     i64 ostr[ZCG_MAX_DIMS];    // element stride of the output view
 };
 
+// Batched region assembly arguments (zcg_regions.hip), built by
+// zcg_read_regions: what every box of the call shares.  The per-box terms
+// (offset mod chunk extent, the box's own grid range, its base in the shared
+// table) are computed on the device from zcg_box.offset.
+struct RegionsArgs {
+    u32 nd, es, fill, V;       // dims, element bytes, fill flag, elements per thread (16/es)
+    u32 nboxes, pad;
+    u64 total;                 // elements in one box
+    u64 nrows;                 // box rows (total / bs[0]); the row kernel's
+    u64 upb;                   // work units per box (tiles, or rows x row pieces)
+    u64 fillv;                 // fill element
+    // per dim, fast-first order (the chunks' memory order)
+    u32 dim[ZCG_MAX_DIMS];     // the array dimension (index into zcg_box.offset)
+    u32 bs[ZCG_MAX_DIMS];      // box extent
+    u32 cs[ZCG_MAX_DIMS];      // chunk extent
+    u64 as[ZCG_MAX_DIMS];      // array extent
+    u64 tlo[ZCG_MAX_DIMS];     // first grid position of the shared table
+    u64 tn[ZCG_MAX_DIMS];      // table extent
+    u64 tstr[ZCG_MAX_DIMS];    // table stride
+    u64 cstr[ZCG_MAX_DIMS];    // element stride inside a chunk
+    i64 ostr[ZCG_MAX_DIMS];    // element stride of every output view
+};
+
 }  // namespace zcg
 
 // Internal launchers (zcg_*.hip) used by zcg_api.cpp.
@@ -378,6 +401,9 @@ hipError_t launch_xz_decode(const zcg_array* a, const zcg_chunk* d_chunks, uint3
 uint64_t xz_decode_ws_bytes(const zcg_array* a, uint32_t n);
 struct RegionArgs;
 hipError_t launch_region(const RegionArgs& a, const void* const* d_table, void* d_out, hipStream_t s);
+struct RegionsArgs;
+hipError_t launch_regions(const RegionsArgs& a, const void* const* d_table, const zcg_box* d_boxes,
+                          int32_t* d_status, hipStream_t s);
 hipError_t launch_xz_encode(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n,
                             uint64_t* d_out_len, int32_t* d_status, void* ws, uint64_t ws_bytes,
                             hipStream_t s);

@@ -21,22 +21,12 @@
 #include <hip/hip_runtime.h>
 
 #include "zcg_common.h"
+#include "zcg_region_walk.h"
 
 namespace zcg {
 
 
 namespace {
-
-constexpr u32 RG_T = 256;
-// pieces per lane in flight per work unit (A/B: 1 / 2 / 4 / 8 / 16 -> 1 753 /
-// 2 249 / 2 385 / 1 852 / 1 254 GiB/s of box on the bench leg)
-#ifndef ZCG_RG_U
-#define ZCG_RG_U 4
-#endif
-
-struct Pos {
-    u32 x[ZCG_MAX_DIMS];
-};
 
 // where element x is read from (nullptr: no visited chunk), and how many
 // elements from it stay in one chunk row and one box row
@@ -76,23 +66,6 @@ __device__ __forceinline__ void region_advance(const RegionArgs& a, Pos& p, u32 
         const u64 q = v / a.bs[k];
         p.x[k] = (u32)(v - q * a.bs[k]);
         c = (u32)q;
-    }
-}
-
-__device__ __forceinline__ void copy_elem(u8* dst, const u8* src, u32 es) {
-    switch (es) {
-    case 1: *dst = *src; break;
-    case 2: *(u16*)dst = *(const u16*)src; break;
-    case 4: *(u32*)dst = *(const u32*)src; break;
-    default: *(u64*)dst = *(const u64*)src; break;
-    }
-}
-__device__ __forceinline__ void fill_elem(u8* dst, u64 v, u32 es) {
-    switch (es) {
-    case 1: *dst = (u8)v; break;
-    case 2: *(u16*)dst = (u16)v; break;
-    case 4: *(u32*)dst = (u32)v; break;
-    default: *(u64*)dst = v; break;
     }
 }
 

@@ -194,6 +194,81 @@ def read_ndarray(hier, path_name: str, meta: ArrayMetadata, bbox: BoundingBox, t
     return np.ndarray(tuple(bbox.shape), dtype=dt, buffer=host, strides=tuple(s * es for s in st)).copy(order=order)
 
 
+def assemble_regions(meta: ArrayMetadata, shape: Sequence[int], es: int, table, table_lo, table_n, boxes, status,
+                     out_strides, fill: bool, fill_value: int, device: int = 0, stream=None) -> None:
+    """Device-level call for many boxes of one `shape` (zcg_read_regions):
+    `table` = device int64 tensor of chunk pointers over the grid range
+    table_lo .. table_lo + table_n (C order, 0 = absent), `boxes` = device
+    tensor holding one _native.Box per box (offset per dim, output base),
+    `status` = device int32 tensor, one word per box.  Asynchronous."""
+    import torch
+    ctx = _native.context(device)
+    nd = meta.get_ndim()
+    r = _region(meta, BoundingBox([0] * nd, shape), es, fill, fill_value, out_strides)
+    lo = (ctypes.c_uint64 * _native.MAX_DIMS)(*[int(x) for x in table_lo])
+    n = (ctypes.c_uint64 * _native.MAX_DIMS)(*[int(x) for x in table_n])
+    n_boxes = boxes.numel() * boxes.element_size() // ctypes.sizeof(_native.Box) if boxes is not None else 0
+    s = stream if stream is not None else torch.cuda.current_stream(device)
+    h = s.cuda_stream if hasattr(s, "cuda_stream") else int(s)
+    st = ctx.lib.zcg_read_regions(ctx.handle, ctypes.byref(r), ctypes.addressof(lo), ctypes.addressof(n),
+                                  table.data_ptr() if table is not None else None,
+                                  boxes.data_ptr() if n_boxes else None, n_boxes,
+                                  status.data_ptr() if status is not None else None, h)
+    _raise_status(st, ctx, "read_regions")
+
+
+def read_ndarrays(hier, path_name: str, meta: ArrayMetadata, offsets, shape: Sequence[int], t, device: int = 0,
+                  as_tensor: bool = False, flags: int = 0, slot_budget_bytes: int = 0):
+    """read_ndarray for many boxes of one `shape` in one native call
+    (zcg_store_read_boxes[_device]): an array of shape (B, *shape) whose [b]
+    equals read_ndarray(..., BoundingBox(offsets[b], shape), t).  The chunks
+    the boxes share are read and decoded once; `slot_budget_bytes` bounds the
+    decoded chunks held on the device at a time (0: 4 GiB).  With as_tensor the
+    result is (uint8 device tensor of B boxes back to back, element strides of
+    one box), as read_ndarray gives for one."""
+    import torch
+    check_array_type(t, meta)
+    shape = [int(x) for x in shape]
+    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64).reshape(-1, len(shape)))
+    if len(shape) != meta.get_ndim():
+        raise ZarrIOError("InvalidData", "Wrong number of dimensions")
+    B = offs.shape[0]
+    dt = np.dtype(t).newbyteorder("=")
+    es = dt.itemsize
+    order = "F" if meta.chunk_memory_layout == "F" else "C"
+    strides = _strides(shape, order)
+    total = int(np.prod(shape)) if shape else 1
+    st, am, msg = _native.array_meta_from_json(meta.to_json())
+    if st != _native.OK:
+        raise ZarrIOError(_native.STATUS_NAMES.get(st, str(st)), f"array metadata: {msg}")
+    am.array.compression.flags = flags
+    ctx = _native.context(device)
+    bshape = (ctypes.c_uint64 * _native.MAX_DIMS)(*shape)
+    root, path = os.fsencode(hier.base_path), path_name.encode()
+    if as_tensor:
+        out = torch.empty(max(B * total * es, 1), dtype=torch.uint8, device=torch.device("cuda", device))
+        outs = (ctypes.c_void_p * max(B, 1))(*[out.data_ptr() + b * total * es for b in range(B)])
+        ostr = (ctypes.c_int64 * _native.MAX_DIMS)(*strides)
+        r = ctx.lib.zcg_store_read_boxes_device(ctx.handle, ctypes.byref(am), root, path, ctypes.addressof(bshape),
+                                                ctypes.addressof(ostr), 1, offs.ctypes.data, ctypes.addressof(outs),
+                                                B, slot_budget_bytes, 16)
+    else:
+        host = np.empty(max(B * total * es, 1), np.uint8)
+        outs = (ctypes.c_void_p * max(B, 1))(*[host.ctypes.data + b * total * es for b in range(B)])
+        r = ctx.lib.zcg_store_read_boxes(ctx.handle, ctypes.byref(am), root, path, ctypes.addressof(bshape),
+                                         offs.ctypes.data, ctypes.addressof(outs), B, slot_budget_bytes, 16)
+    if r != _native.OK:
+        raise ZarrIOError(_native.STATUS_NAMES.get(r, str(r)), f"read_boxes: {ctx.last_error()}")
+    if as_tensor:
+        return out[: B * total * es], strides
+    res = np.empty((B, *shape), dtype=dt, order="C")
+    for b in range(B):
+        box = np.ndarray(tuple(shape), dtype=dt, buffer=host, offset=b * total * es,
+                         strides=tuple(s * es for s in strides))
+        res[b] = box
+    return res
+
+
 def read_ndarray_into(hier, path_name: str, meta: ArrayMetadata, bbox: BoundingBox, arr: np.ndarray, t,
                       device: int = 0, flags: int = 0) -> None:
     """ZarrNdarrayReader::read_ndarray_into (ndarray.rs:176-268): elements
