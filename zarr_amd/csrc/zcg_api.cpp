@@ -507,8 +507,85 @@ uint64_t zcg_region_grid(const zcg_region* r, uint64_t* grid_lo, uint64_t* grid_
     return cnt;
 }
 
+// The array dimension at position k of the fast-first order (the chunks'
+// memory order).
+static uint32_t region_dim(const zcg_region* r, uint32_t k) { return r->chunk_order == 1 ? k : r->ndim - 1 - k; }
+
+static int region_head(const zcg_ctx* ctx, const zcg_region* r) {
+    if (!ctx || !r || r->ndim < 1 || r->ndim > ZCG_MAX_DIMS) return ZCG_ERR_INVALID_INPUT;
+    const uint32_t es = r->elem_size;
+    return es == 1 || es == 2 || es == 4 || es == 8 ? ZCG_OK : ZCG_ERR_INVALID_INPUT;
+}
+
+// What the region calls share: `r` validated and the walk filled in fast-first
+// order, for a chunk table of extents tn (per array dim; NULL: no table) whose
+// number of entries is returned in *entries.  The kernels hold a position
+// along a dimension plus a box's offset into its first chunk in 32 bits:
+// `off` is the one box's offset, or NULL for boxes at any offset (the offset
+// into the chunk is then taken as chunk extent - 1); `too_far` is the error
+// text of that limit.
+static int region_walk(zcg_ctx* ctx, const zcg_region* r, const uint64_t* off, const uint64_t* tn,
+                       const char* too_far, RegionWalk* w, uint64_t* entries) {
+    const int head = region_head(ctx, r);
+    if (head != ZCG_OK) return head;
+    const uint32_t nd = r->ndim;
+    *w = RegionWalk{};
+    w->nd = nd;
+    w->es = r->elem_size;
+    w->fill = r->fill_missing ? 1u : 0u;
+    w->V = 16 / r->elem_size;
+    w->fillv = r->fill_value;
+    uint64_t tstr[ZCG_MAX_DIMS];
+    *entries = 1;
+    for (int d = (int)nd - 1; d >= 0; d--) {
+        tstr[d] = *entries;
+        *entries *= tn ? tn[d] : 0;
+    }
+    uint64_t total = 1, cst = 1;
+    for (uint32_t k = 0; k < nd; k++) {
+        const uint32_t d = region_dim(r, k);
+        const uint64_t cs = r->chunk_shape[d], bs = r->bbox_shape[d];
+        if (cs == 0 || cs >= (1ull << 32)) return ZCG_ERR_INVALID_INPUT;
+        if (bs + (off ? off[d] % cs : cs - 1) >= (1ull << 32)) {
+            ctx->err = too_far;
+            return ZCG_ERR_UNSUPPORTED;
+        }
+        w->bs[k] = (uint32_t)bs;
+        w->cs[k] = (uint32_t)cs;
+        w->tstr[k] = tstr[d];
+        w->cstr[k] = cst;
+        w->ostr[k] = r->out_strides[d];
+        cst *= cs;
+        total *= bs;
+    }
+    w->total = total;
+    return ZCG_OK;
+}
+
 static int region_call(zcg_ctx* ctx, const zcg_region* r, const void* const* d_chunk_table, void* d_box,
-                       void* stream, uint32_t dir);
+                       void* stream, uint32_t dir) {
+    uint64_t gn[ZCG_MAX_DIMS], nchunks;
+    zcg_region_grid(r, nullptr, gn);
+    RegionWalk w;
+    const int rc = region_walk(ctx, r, r ? r->bbox_offset : nullptr, gn,
+                               "region: box extent along a dimension must stay below 2^32 elements", &w, &nchunks);
+    if (rc != ZCG_OK) return rc;
+    if (dir) w.fill = 0;
+    BoxTerms t{};
+    for (uint32_t k = 0; k < w.nd; k++) {
+        const uint32_t d = region_dim(r, k);
+        t.orr[k] = (uint32_t)(r->bbox_offset[d] % w.cs[k]);
+        t.gn[k] = (uint32_t)gn[d];  // <= offset into the chunk + box extent < 2^32
+    }
+    t.table = (const u8* const*)d_chunk_table;
+    t.out = (u8*)d_box;
+    if (w.total == 0) return ZCG_OK;
+    if (!d_box || (nchunks && !d_chunk_table)) return ZCG_ERR_INVALID_INPUT;
+    (void)hipSetDevice(ctx->device);
+    const hipError_t e = launch_region(w, t, dir, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, e, "region launch");
+    return ZCG_OK;
+}
 
 int zcg_read_region(zcg_ctx* ctx, const zcg_region* r, const void* const* d_chunk_table, void* d_out,
                     void* stream) {
@@ -518,56 +595,6 @@ int zcg_read_region(zcg_ctx* ctx, const zcg_region* r, const void* const* d_chun
 int zcg_write_region(zcg_ctx* ctx, const zcg_region* r, void* const* d_chunk_table, const void* d_in,
                      void* stream) {
     return region_call(ctx, r, (const void* const*)d_chunk_table, (void*)d_in, stream, 1);
-}
-
-static int region_call(zcg_ctx* ctx, const zcg_region* r, const void* const* d_chunk_table, void* d_out,
-                       void* stream, uint32_t dir) {
-    if (!ctx || !r || r->ndim < 1 || r->ndim > ZCG_MAX_DIMS) return ZCG_ERR_INVALID_INPUT;
-    const uint32_t es = r->elem_size;
-    if (es != 1 && es != 2 && es != 4 && es != 8) return ZCG_ERR_INVALID_INPUT;
-    const uint32_t nd = r->ndim;
-    uint64_t lo[ZCG_MAX_DIMS], gn[ZCG_MAX_DIMS];
-    const uint64_t nchunks = zcg_region_grid(r, lo, gn);
-    RegionArgs a{};
-    a.nd = nd;
-    a.es = es;
-    a.fill = (r->fill_missing && !dir) ? 1u : 0u;
-    a.dir = dir;
-    a.V = 16 / es;
-    a.fillv = r->fill_value;
-    uint64_t tstr_arr[ZCG_MAX_DIMS];
-    {
-        uint64_t st = 1;
-        for (int d = (int)nd - 1; d >= 0; d--) { tstr_arr[d] = st; st *= gn[d]; }
-    }
-    uint64_t total = 1, cst = 1;
-    for (uint32_t k = 0; k < nd; k++) {
-        const uint32_t d = r->chunk_order == 1 ? k : nd - 1 - k;  // fast-first
-        const uint64_t cs = r->chunk_shape[d], bs = r->bbox_shape[d];
-        if (cs == 0 || cs >= (1ull << 32)) return ZCG_ERR_INVALID_INPUT;
-        const uint64_t orr = r->bbox_offset[d] % cs;
-        if (bs + orr >= (1ull << 32)) {
-            ctx->err = "region: box extent along a dimension must stay below 2^32 elements";
-            return ZCG_ERR_UNSUPPORTED;
-        }
-        a.bs[k] = (uint32_t)bs;
-        a.orr[k] = (uint32_t)orr;
-        a.cs[k] = (uint32_t)cs;
-        a.ob[k] = lo[d];
-        a.gn[k] = gn[d];
-        a.tstr[k] = tstr_arr[d];
-        a.cstr[k] = cst;
-        a.ostr[k] = r->out_strides[d];
-        cst *= cs;
-        total *= bs;
-    }
-    a.total = total;
-    if (total == 0) return ZCG_OK;
-    if (!d_out || (nchunks && !d_chunk_table)) return ZCG_ERR_INVALID_INPUT;
-    (void)hipSetDevice(ctx->device);
-    const hipError_t e = launch_region(a, d_chunk_table, d_out, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, e, "region launch");
-    return ZCG_OK;
 }
 
 uint64_t zcg_regions_grid(const zcg_region* r, const uint64_t* offsets, uint32_t n_boxes, uint64_t* lo,
@@ -599,53 +626,30 @@ uint64_t zcg_regions_grid(const zcg_region* r, const uint64_t* offsets, uint32_t
 int zcg_read_regions(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
                      const void* const* d_chunk_table, const zcg_box* d_boxes, uint32_t n_boxes,
                      int32_t* d_status, void* stream) {
-    if (!ctx || !r || r->ndim < 1 || r->ndim > ZCG_MAX_DIMS) return ZCG_ERR_INVALID_INPUT;
-    const uint32_t es = r->elem_size;
-    if (es != 1 && es != 2 && es != 4 && es != 8) return ZCG_ERR_INVALID_INPUT;
-    if (n_boxes == 0) return ZCG_OK;
-    const uint32_t nd = r->ndim;
-    RegionsArgs a{};
-    a.nd = nd;
-    a.es = es;
-    a.fill = r->fill_missing ? 1u : 0u;
-    a.V = 16 / es;
-    a.nboxes = n_boxes;
-    a.fillv = r->fill_value;
-    uint64_t tstr_arr[ZCG_MAX_DIMS], entries = 1;
-    for (int d = (int)nd - 1; d >= 0; d--) {
-        tstr_arr[d] = entries;
-        entries *= table_n ? table_n[d] : 0;
+    if (n_boxes == 0) return region_head(ctx, r);
+    RegionWalk w;
+    uint64_t entries;
+    const int rc = region_walk(ctx, r, nullptr, table_n,
+                               "regions: box extent + chunk extent along a dimension must stay below 2^32 elements",
+                               &w, &entries);
+    if (rc != ZCG_OK) return rc;
+    BoxTable bt{};
+    bt.nboxes = n_boxes;
+    for (uint32_t k = 0; k < w.nd; k++) {
+        const uint32_t d = region_dim(r, k);
+        bt.dim[k] = d;
+        bt.as[k] = r->array_shape[d];
+        bt.tlo[k] = table_lo ? table_lo[d] : 0;
+        bt.tn[k] = table_n ? table_n[d] : 0;
     }
-    uint64_t total = 1, cst = 1;
-    for (uint32_t k = 0; k < nd; k++) {
-        const uint32_t d = r->chunk_order == 1 ? k : nd - 1 - k;  // fast-first
-        const uint64_t cs = r->chunk_shape[d], bs = r->bbox_shape[d];
-        if (cs == 0 || cs >= (1ull << 32)) return ZCG_ERR_INVALID_INPUT;
-        if (bs + cs - 1 >= (1ull << 32)) {
-            ctx->err = "regions: box extent + chunk extent along a dimension must stay below 2^32 elements";
-            return ZCG_ERR_UNSUPPORTED;
-        }
-        a.dim[k] = d;
-        a.bs[k] = (uint32_t)bs;
-        a.cs[k] = (uint32_t)cs;
-        a.as[k] = r->array_shape[d];
-        a.tlo[k] = table_lo ? table_lo[d] : 0;
-        a.tn[k] = table_n ? table_n[d] : 0;
-        a.tstr[k] = tstr_arr[d];
-        a.cstr[k] = cst;
-        a.ostr[k] = r->out_strides[d];
-        cst *= cs;
-        total *= bs;
-    }
-    a.total = total;
-    if (total == 0) return ZCG_OK;
+    if (w.total == 0) return ZCG_OK;
     if (!d_boxes || !d_status || (entries && !d_chunk_table)) return ZCG_ERR_INVALID_INPUT;
-    if (total > (1ull << 62) / n_boxes) {
+    if (w.total > (1ull << 62) / n_boxes) {
         ctx->err = "regions: n_boxes x box elements must stay below 2^62";
         return ZCG_ERR_UNSUPPORTED;
     }
     (void)hipSetDevice(ctx->device);
-    const hipError_t e = launch_regions(a, d_chunk_table, d_boxes, d_status, (hipStream_t)stream);
+    const hipError_t e = launch_regions(w, bt, d_chunk_table, d_boxes, d_status, (hipStream_t)stream);
     if (e != hipSuccess) return fail(ctx, e, "regions launch");
     return ZCG_OK;
 }

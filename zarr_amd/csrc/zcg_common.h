@@ -250,44 +250,38 @@ static __constant__ u32 g_crc32_table[256] = {
     0x54de5729u, 0x23d967bfu, 0xb3667a2eu, 0xc4614ab8u, 0x5d681b02u, 0x2a6f2b94u,
     0xb40bbe37u, 0xc30c8ea1u, 0x5a05df1bu, 0x2d02ef8du};
 
-// Region assembly arguments (zcg_region.hip), built by zcg_read_region.
-struct RegionArgs {
+// Region assembly arguments (zcg_region.hip, zcg_region_walk.h), built by
+// zcg_api.cpp.  RegionWalk: what every box of a launch shares.
+struct RegionWalk {
     u32 nd, es, fill, V;       // dims, element bytes, fill flag, elements per thread (16/es)
-    u32 dir, pad;              // 0: chunks -> box (read_ndarray), 1: box -> chunks (write_ndarray)
-    u64 total;                 // elements in the box
-    u64 fillv;                 // fill element, replicated to 16 bytes below
-    // per dim, fast-first order (the chunks' memory order)
-    u32 bs[ZCG_MAX_DIMS];      // box extent
-    u32 orr[ZCG_MAX_DIMS];     // box offset mod chunk extent
-    u32 cs[ZCG_MAX_DIMS];      // chunk extent
-    u64 ob[ZCG_MAX_DIMS];      // box offset / chunk extent  (= grid_lo)
-    u64 gn[ZCG_MAX_DIMS];      // visited chunks along the dim
-    u64 tstr[ZCG_MAX_DIMS];    // chunk-table stride
-    u64 cstr[ZCG_MAX_DIMS];    // element stride inside a chunk
-    i64 ostr[ZCG_MAX_DIMS];    // element stride of the output view
-};
-
-// Batched region assembly arguments (zcg_regions.hip), built by
-// zcg_read_regions: what every box of the call shares.  The per-box terms
-// (offset mod chunk extent, the box's own grid range, its base in the shared
-// table) are computed on the device from zcg_box.offset.
-struct RegionsArgs {
-    u32 nd, es, fill, V;       // dims, element bytes, fill flag, elements per thread (16/es)
-    u32 nboxes, pad;
     u64 total;                 // elements in one box
-    u64 nrows;                 // box rows (total / bs[0]); the row kernel's
-    u64 upb;                   // work units per box (tiles, or rows x row pieces)
     u64 fillv;                 // fill element
     // per dim, fast-first order (the chunks' memory order)
-    u32 dim[ZCG_MAX_DIMS];     // the array dimension (index into zcg_box.offset)
     u32 bs[ZCG_MAX_DIMS];      // box extent
     u32 cs[ZCG_MAX_DIMS];      // chunk extent
-    u64 as[ZCG_MAX_DIMS];      // array extent
-    u64 tlo[ZCG_MAX_DIMS];     // first grid position of the shared table
-    u64 tn[ZCG_MAX_DIMS];      // table extent
-    u64 tstr[ZCG_MAX_DIMS];    // table stride
+    u64 tstr[ZCG_MAX_DIMS];    // chunk-table stride
     u64 cstr[ZCG_MAX_DIMS];    // element stride inside a chunk
     i64 ostr[ZCG_MAX_DIMS];    // element stride of every output view
+};
+
+// What one box adds (wave-uniform): filled by the host for zcg_read_region and
+// zcg_write_region, computed on the device from zcg_box for zcg_read_regions.
+struct BoxTerms {
+    u32 orr[ZCG_MAX_DIMS];     // box offset mod chunk extent
+    u32 gn[ZCG_MAX_DIMS];      // chunks the box visits along the dim (its own grid range)
+    const u8* const* table;    // the chunk table at the box's first chunk
+    u8* out;                   // element (0, ..., 0) of the box's view
+};
+
+// The shared table of a zcg_read_regions call and its boxes.
+struct BoxTable {
+    u32 nboxes, pad;
+    u64 upb;                   // work units per box (tiles, or rows x row pieces)
+    // per dim, fast-first order
+    u32 dim[ZCG_MAX_DIMS];     // the array dimension (index into zcg_box.offset)
+    u64 as[ZCG_MAX_DIMS];      // array extent
+    u64 tlo[ZCG_MAX_DIMS];     // first grid position of the table
+    u64 tn[ZCG_MAX_DIMS];      // table extent
 };
 
 }  // namespace zcg
@@ -399,11 +393,10 @@ uint64_t bzip2_encode_ws_bytes(const zcg_array* a, uint32_t n);
 hipError_t launch_xz_decode(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n,
                             int32_t* d_status, void* ws, uint64_t ws_bytes, hipStream_t s);
 uint64_t xz_decode_ws_bytes(const zcg_array* a, uint32_t n);
-struct RegionArgs;
-hipError_t launch_region(const RegionArgs& a, const void* const* d_table, void* d_out, hipStream_t s);
-struct RegionsArgs;
-hipError_t launch_regions(const RegionsArgs& a, const void* const* d_table, const zcg_box* d_boxes,
-                          int32_t* d_status, hipStream_t s);
+// dir 0: chunks -> box (read_ndarray), 1: box -> chunks (write_ndarray)
+hipError_t launch_region(const RegionWalk& w, const BoxTerms& t, uint32_t dir, hipStream_t s);
+hipError_t launch_regions(const RegionWalk& w, const BoxTable& bt, const void* const* d_table,
+                          const zcg_box* d_boxes, int32_t* d_status, hipStream_t s);
 hipError_t launch_xz_encode(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n,
                             uint64_t* d_out_len, int32_t* d_status, void* ws, uint64_t ws_bytes,
                             hipStream_t s);

@@ -1,7 +1,9 @@
 // zcg_region.hip — region assembly on the device:
 // ZarrNdarrayReader::read_ndarray / read_ndarray_into_with_buffer
 // (src/ndarray.rs:153-268) for chunks that the batch decoders already left in
-// HBM.
+// HBM, for one bounding box per launch (zcg_read_region, zcg_write_region) or
+// many boxes of one common shape, each at its own offset and into its own
+// output view, from one shared chunk table (zcg_read_regions).
 //
 // Reference semantics kept: the chunks visited are bounded_coord_iter's grid
 // range (ndarray.rs:410-432); each visited chunk covers its full nominal
@@ -12,12 +14,19 @@
 // visited chunk covers keep Array::from_elem's fill value in read_ndarray
 // (ndarray.rs:164-171) and are left untouched by read_ndarray_into.
 //
-// The kernel is HBM-bound byte movement (2 bytes of traffic per output byte):
-// the box is walked in the chunks' memory order, 16 bytes per thread, so
-// reads from a chunk row and writes to an output row with unit stride are
-// both coalesced 16-byte accesses; a 16-byte piece that crosses a row or a
-// chunk boundary is copied in per-element runs.  Tile starts are decomposed
-// once per workgroup (scalar), threads add their offset with carries.
+// The kernels are HBM-bound byte movement (2 bytes of traffic per output
+// byte).  The walk itself is zcg_region_walk.h's; the four entry points differ
+// only in how they obtain a box's terms.  The single-box ones get them from
+// the host as kernel arguments (scalar).  The many-box ones work on the
+// flattened (box, tile) or (box, row piece) space: the box of a work unit is
+// wave-uniform, so everything that depends on the box alone — offset mod chunk
+// extent, the box's grid range, its base index in the shared table, whether
+// that range lies in the table — is computed once per work unit from
+// d_boxes[b].offset on the scalar side.  Per box the semantics are the single
+// call's: a box behaves exactly as a zcg_read_region call with its offset and
+// a table over its own grid range would.  The shared table only supplies the
+// pointers; a chunk of the table outside the box's own grid range is never
+// read.
 #include <hip/hip_runtime.h>
 
 #include "zcg_common.h"
@@ -25,209 +34,143 @@
 
 namespace zcg {
 
-
 namespace {
 
-// where element x is read from (nullptr: no visited chunk), and how many
-// elements from it stay in one chunk row and one box row
-__device__ __forceinline__ const u8* region_src(const RegionArgs& a, const Pos& p,
-                                                const u8* const* __restrict__ table, u32* run) {
-    u64 ti = 0, wi = 0;
-    bool ok = true;
-    u32 w0 = 0;
-    for (u32 k = 0; k < a.nd; k++) {
-        const u32 r = a.orr[k] + p.x[k];
-        const u32 q = r / a.cs[k];
-        const u32 w = r - q * a.cs[k];
-        if (k == 0) w0 = w;
-        ok &= (u64)q < a.gn[k];
-        ti += (u64)q * a.tstr[k];
-        wi += (u64)w * a.cstr[k];
+// the terms of box b of a many-box call; false: the box's grid range does not
+// lie inside the table's
+__device__ __forceinline__ bool box_terms(const RegionWalk& w, const BoxTable& bt,
+                                          const u8* const* __restrict__ table,
+                                          const zcg_box* __restrict__ boxes, u64 b, BoxTerms& t) {
+    const zcg_box* bx = boxes + b;
+    u64 base = 0;
+    bool inside = true, visits = true;
+#pragma unroll
+    for (u32 k = 0; k < ZCG_MAX_DIMS; k++) {
+        t.orr[k] = 0;
+        t.gn[k] = 0;
+        if (k >= w.nd) continue;
+        // bounded_coord_iter (ndarray.rs:410-432), as zcg_region_grid states it:
+        // the box clipped to the array, floor / ceil by the chunk extent
+        const u64 off = ru64(bx->offset[bt.dim[k]]);
+        const u64 cs = w.cs[k];
+        const u64 lo = off / cs;
+        const u64 orr = off - lo * cs;
+        const u64 end = off + w.bs[k] < bt.as[k] ? off + w.bs[k] : bt.as[k];
+        const u64 s = end > off ? end - off : 0;
+        // ceil((off + s) / cs) - lo, in 32 bits: orr + s <= chunk extent - 1 +
+        // box extent < 2^32 (checked by the host)
+        const u32 span = (u32)orr + (u32)s, nq = span / w.cs[k];
+        const u32 n = nq + (span != nq * w.cs[k] ? 1u : 0u);
+        t.orr[k] = (u32)orr;
+        t.gn[k] = n;
+        visits &= n != 0;
+        inside &= lo >= bt.tlo[k] && lo - bt.tlo[k] + n <= bt.tn[k];
+        base += (lo - bt.tlo[k]) * w.tstr[k];
     }
-    const u32 r1 = a.bs[0] - p.x[0], r2 = a.cs[0] - w0;
-    *run = r1 < r2 ? r1 : r2;
-    if (!ok) return nullptr;
-    const u8* base = table[ti];
-    return base ? base + wi * a.es : nullptr;
+    t.table = table + (visits && inside ? base : 0);
+    t.out = (u8*)(uintptr_t)ru64((u64)(uintptr_t)bx->out);
+    // a box that visits no chunk reads no table entry: it is filled (or left
+    // untouched) wherever the table is
+    return inside || !visits;
 }
 
-__device__ __forceinline__ i64 region_dst(const RegionArgs& a, const Pos& p) {
-    i64 o = 0;
-    for (u32 k = 0; k < a.nd; k++) o += (i64)p.x[k] * a.ostr[k];
-    return o;
+// one lane says how the box fared
+__device__ __forceinline__ void box_status(i32* status, u64 b, bool in_table, bool first_lane) {
+    if (first_lane) status[b] = in_table ? ZCG_OK : ZCG_ERR_INVALID_INPUT;
 }
 
-// advance p by d elements along the fast-first order (carries)
-__device__ __forceinline__ void region_advance(const RegionArgs& a, Pos& p, u32 d) {
-    u32 c = d;
-    for (u32 k = 0; k < a.nd && c; k++) {
-        const u64 v = (u64)p.x[k] + c;
-        if (v < a.bs[k]) { p.x[k] = (u32)v; c = 0; break; }
-        const u64 q = v / a.bs[k];
-        p.x[k] = (u32)(v - q * a.bs[k]);
-        c = (u32)q;
-    }
+// Short box rows: a workgroup per tile (walk_tile).
+__global__ __launch_bounds__(RG_T) void region_kernel(RegionWalk w, BoxTerms t, u64 ntiles, u32 dir) {
+    for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) walk_tile(w, t, tile, dir);
 }
 
-__global__ __launch_bounds__(RG_T) void region_kernel(RegionArgs a, const u8* const* __restrict__ table,
-                                                      u8* __restrict__ out) {
-    const u64 tile_elems = (u64)RG_T * a.V;
-    const u64 ntiles = (a.total + tile_elems - 1) / tile_elems;
-    u64 fv = a.fillv;
-    if (a.es == 1) fv = (fv & 0xFF) * 0x0101010101010101ull;
-    else if (a.es == 2) fv = (fv & 0xFFFF) * 0x0001000100010001ull;
-    else if (a.es == 4) fv = (fv & 0xFFFFFFFFull) * 0x0000000100000001ull;
-    const u32x4 fill16 = {(u32)fv, (u32)(fv >> 32), (u32)fv, (u32)(fv >> 32)};
-    for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        // decompose the tile start (wave-uniform, scalar)
-        Pos p;
-        u64 e = tile * tile_elems;
-        for (u32 k = 0; k < ZCG_MAX_DIMS; k++) {
-            if (k < a.nd) {
-                const u64 q = e / a.bs[k];
-                p.x[k] = (u32)(e - q * a.bs[k]);
-                e = q;
-            } else {
-                p.x[k] = 0;
-            }
-        }
-        const u64 e0 = tile * tile_elems + (u64)threadIdx.x * a.V;
-        if (e0 >= a.total) continue;
-        region_advance(a, p, threadIdx.x * a.V);
-        u32 rem = (u32)((a.total - e0) < a.V ? (a.total - e0) : a.V);
-        u32 run;
-        const u8* src = region_src(a, p, table, &run);
-        if (rem == a.V && run >= a.V && a.ostr[0] == 1) {  // one 16-byte piece, both sides contiguous
-            u8* d = out + region_dst(a, p) * (i64)a.es;
-            if (a.dir) { if (src) st16((u8*)src, ld16(d)); }
-            else if (src) st16(d, ld16(src));
-            else if (a.fill) st16(d, fill16);
-            continue;
-        }
-        while (rem) {  // runs inside one chunk row and one box row
-            const u32 k = run < rem ? run : rem;
-            u8* d = out + region_dst(a, p) * (i64)a.es;
-            const i64 ds = a.ostr[0] * (i64)a.es;
-            for (u32 j = 0; j < k; j++) {
-                if (a.dir) { if (src) copy_elem((u8*)src + (u64)j * a.es, d + j * ds, a.es); }
-                else if (src) copy_elem(d + j * ds, src + (u64)j * a.es, a.es);
-                else if (a.fill) fill_elem(d + j * ds, fv, a.es);
-            }
-            rem -= k;
-            if (!rem) break;
-            region_advance(a, p, k);
-            src = region_src(a, p, table, &run);
-        }
-    }
-}
-
-// Long box rows (the common case: the fast dimension spans many 16-byte
-// pieces): one wave per box row.  The row's coordinates, chunk-table and
-// chunk-offset contributions of the slow dimensions are scalar, computed once
-// per row; lanes stream the row 16 bytes each.
-__global__ __launch_bounds__(RG_T) void region_rows_kernel(RegionArgs a, u64 nrows,
-                                                           const u8* const* __restrict__ table,
-                                                           u8* __restrict__ out) {
-    const u32 lane = threadIdx.x & 63;
+// Long box rows: a wave per (row, row piece) (walk_row_piece).
+__global__ __launch_bounds__(RG_T) void region_rows_kernel(RegionWalk w, BoxTerms t, u64 nunits, u32 dir) {
     const u64 wid = ((u64)blockIdx.x * RG_T + threadIdx.x) >> 6;
     const u64 nwaves = ((u64)gridDim.x * RG_T) >> 6;
-    u64 fv = a.fillv;
-    if (a.es == 1) fv = (fv & 0xFF) * 0x0101010101010101ull;
-    else if (a.es == 2) fv = (fv & 0xFFFF) * 0x0001000100010001ull;
-    else if (a.es == 4) fv = (fv & 0xFFFFFFFFull) * 0x0000000100000001ull;
-    const u32x4 fill16 = {(u32)fv, (u32)(fv >> 32), (u32)fv, (u32)(fv >> 32)};
-    const u32 V = a.V, bs0 = a.bs[0], cs0 = a.cs[0], orr0 = a.orr[0];
-    const i64 es = a.es;
-    // work unit = (row, piece of U*64*V elements of it): many short units
-    // keep more loads in flight per CU than one long walk per row
-    constexpr u32 U = ZCG_RG_U;
-    const u32 span = U * 64 * V;
-    const u32 ppr = (bs0 + span - 1) / span;
-    const u64 nunits = nrows * ppr;
+    const u32 ppr = row_pieces(w);
     for (u64 unit = ru64(wid); unit < nunits; unit += nwaves) {
         const u64 row = unit / ppr;
-        const u32 piece = (u32)(unit - row * ppr);
-        // slow-dimension coordinates of this row (scalar)
-        u64 e = row, ti = 0, wi = 0;
-        i64 drow = 0;
-        bool ok = true;
-        for (u32 k = 1; k < ZCG_MAX_DIMS; k++) {
-            if (k >= a.nd) break;
-            const u64 qd = e / a.bs[k];
-            const u32 x = (u32)(e - qd * a.bs[k]);
-            e = qd;
-            const u32 r = a.orr[k] + x;
-            const u32 q = r / a.cs[k];
-            ok &= (u64)q < a.gn[k];
-            ti += (u64)q * a.tstr[k];
-            wi += (u64)(r - q * a.cs[k]) * a.cstr[k];
-            drow += (i64)x * a.ostr[k];
-        }
-        u8* drow_p = out + drow * es;
-        // U pieces per lane in flight: loads first, then stores
-        const u32 xend = (piece + 1) * span;
-        for (u32 xb = piece * span + lane * V; xb < bs0 && xb < xend; xb += span) {
-            u32x4 v[U];
-            u8* dp[U];
-            u32 mode[U];  // 0 skip, 1 load+store, 2 fill, 3 element runs
-#pragma unroll
-            for (u32 u = 0; u < U; u++) {
-                const u32 x0 = xb + u * 64 * V;
-                mode[u] = 0;
-                dp[u] = drow_p + (i64)x0 * a.ostr[0] * es;
-                if (x0 >= bs0) continue;
-                const u32 r = orr0 + x0;
-                const u32 q = r / cs0;
-                const u32 w0 = r - q * cs0;
-                const bool here = ok && (u64)q < a.gn[0];
-                const u8* base = here ? table[ti + (u64)q * a.tstr[0]] : nullptr;
-                if (!(bs0 - x0 >= V && w0 + V <= cs0 && a.ostr[0] == 1)) { mode[u] = 3; continue; }
-                if (a.dir) {  // write_ndarray: box -> chunk
-                    if (base) { v[u] = ld16(dp[u]); dp[u] = (u8*)base + (wi + w0) * (u64)es; mode[u] = 1; }
-                } else if (base) { v[u] = ld16(base + (wi + w0) * (u64)es); mode[u] = 1; }
-                else if (a.fill) { v[u] = fill16; mode[u] = 2; }
-            }
-#pragma unroll
-            for (u32 u = 0; u < U; u++)
-                if (mode[u] == 1 || mode[u] == 2) st16(dp[u], v[u]);
-#pragma unroll
-            for (u32 u = 0; u < U; u++) {
-                if (mode[u] != 3) continue;
-                const u32 x0 = xb + u * 64 * V;
-                const u32 rem = bs0 - x0 < V ? bs0 - x0 : V;
-                // the piece crosses a chunk boundary or ends the row: per element
-                for (u32 j = 0; j < rem; j++) {
-                    const u32 rj = orr0 + x0 + j;
-                    const u32 qj = rj / cs0;
-                    const bool hj = ok && (u64)qj < a.gn[0];
-                    const u8* bj = hj ? table[ti + (u64)qj * a.tstr[0]] : nullptr;
-                    u8* dj = drow_p + (i64)(x0 + j) * a.ostr[0] * es;
-                    if (a.dir) { if (bj) copy_elem((u8*)bj + (wi + (rj - qj * cs0)) * (u64)es, dj, a.es); }
-                    else if (bj) copy_elem(dj, bj + (wi + (rj - qj * cs0)) * (u64)es, a.es);
-                    else if (a.fill) fill_elem(dj, fv, a.es);
-                }
-            }
-        }
+        walk_row_piece<1>(w, t, row, (u32)(unit - row * ppr), dir);
     }
+}
+
+// Many boxes, short rows: a workgroup per (box, tile).
+__global__ __launch_bounds__(RG_T) void regions_kernel(RegionWalk w, BoxTable bt, const u8* const* __restrict__ table,
+                                                       const zcg_box* __restrict__ boxes,
+                                                       i32* __restrict__ status) {
+    const u64 nunits = (u64)bt.nboxes * bt.upb;
+    for (u64 unit = blockIdx.x; unit < nunits; unit += gridDim.x) {
+        const u64 b = unit / bt.upb;
+        const u64 tile = unit - b * bt.upb;
+        BoxTerms t;
+        const bool in_table = box_terms(w, bt, table, boxes, b, t);
+        box_status(status, b, in_table, tile == 0 && threadIdx.x == 0);
+        if (in_table) walk_tile(w, t, tile, 0);
+    }
+}
+
+// Many boxes, long rows: a wave per (box, row, row piece).
+__global__ __launch_bounds__(RG_T) void regions_rows_kernel(RegionWalk w, BoxTable bt,
+                                                            const u8* const* __restrict__ table,
+                                                            const zcg_box* __restrict__ boxes,
+                                                            i32* __restrict__ status) {
+    const u64 wid = ((u64)blockIdx.x * RG_T + threadIdx.x) >> 6;
+    const u64 nwaves = ((u64)gridDim.x * RG_T) >> 6;
+    const u32 ppr = row_pieces(w);
+    const u64 nunits = (u64)bt.nboxes * bt.upb;
+    for (u64 unit = ru64(wid); unit < nunits; unit += nwaves) {
+        const u64 b = unit / bt.upb;
+        const u64 ub = unit - b * bt.upb;
+        BoxTerms t;
+        const bool in_table = box_terms(w, bt, table, boxes, b, t);
+        box_status(status, b, in_table, ub == 0 && (threadIdx.x & 63) == 0);
+        if (!in_table) continue;
+        const u64 row = ub / ppr;
+        walk_row_piece<ZCG_MAX_DIMS>(w, t, row, (u32)(ub - row * ppr), 0);
+    }
+}
+
+// The launch rule: rows of at least 32 16-byte pieces go a wave per row piece,
+// shorter ones a workgroup per tile.  One launch whatever the number of boxes
+// (the grid is capped; workgroups stride over the units).
+struct LaunchShape {
+    bool rows;
+    u64 upb;   // work units per box
+    u32 grid;
+};
+LaunchShape launch_shape(const RegionWalk& w, u64 nboxes) {
+    LaunchShape g;
+    g.rows = w.bs[0] >= 32u * w.V;
+    if (g.rows) {
+        g.upb = w.total / w.bs[0] * row_pieces(w);
+        const u64 wgs = (g.upb * nboxes + 3) / 4;
+        g.grid = (u32)(wgs < (1u << 20) ? wgs : (1u << 20));
+    } else {
+        g.upb = (w.total + (u64)RG_T * w.V - 1) / ((u64)RG_T * w.V);
+        const u64 units = g.upb * nboxes;
+        g.grid = (u32)(units < 262144 ? units : 262144);
+    }
+    return g;
 }
 
 }  // namespace
 
-hipError_t launch_region(const RegionArgs& a, const void* const* d_table, void* d_out, hipStream_t s) {
-    if (a.total == 0) return hipSuccess;
-    if (a.bs[0] >= 32u * a.V) {  // long rows: a wave per row
-        const u64 nrows = a.total / a.bs[0];
-        const u64 span = (u64)ZCG_RG_U * 64 * a.V;
-        const u64 units = nrows * ((a.bs[0] + span - 1) / span);
-        const u64 wgs = (units + 3) / 4;
-        const u32 grid = (u32)(wgs < (1u << 20) ? wgs : (1u << 20));
-        hipLaunchKernelGGL(region_rows_kernel, dim3(grid), dim3(RG_T), 0, s, a, nrows, (const u8* const*)d_table,
-                           (u8*)d_out);
-        return hipGetLastError();
-    }
-    const u64 tiles = (a.total + (u64)RG_T * a.V - 1) / ((u64)RG_T * a.V);
-    const u32 grid = (u32)(tiles < 262144 ? tiles : 262144);
-    hipLaunchKernelGGL(region_kernel, dim3(grid), dim3(RG_T), 0, s, a, (const u8* const*)d_table, (u8*)d_out);
+hipError_t launch_region(const RegionWalk& w, const BoxTerms& t, uint32_t dir, hipStream_t s) {
+    if (w.total == 0) return hipSuccess;
+    const LaunchShape g = launch_shape(w, 1);
+    hipLaunchKernelGGL(g.rows ? region_rows_kernel : region_kernel, dim3(g.grid), dim3(RG_T), 0, s, w, t, g.upb, dir);
+    return hipGetLastError();
+}
+
+hipError_t launch_regions(const RegionWalk& w, const BoxTable& bt0, const void* const* d_table,
+                          const zcg_box* d_boxes, int32_t* d_status, hipStream_t s) {
+    if (w.total == 0 || bt0.nboxes == 0) return hipSuccess;
+    const LaunchShape g = launch_shape(w, bt0.nboxes);
+    BoxTable bt = bt0;
+    bt.upb = g.upb;
+    hipLaunchKernelGGL(g.rows ? regions_rows_kernel : regions_kernel, dim3(g.grid), dim3(RG_T), 0, s, w, bt,
+                       (const u8* const*)d_table, d_boxes, d_status);
     return hipGetLastError();
 }
 

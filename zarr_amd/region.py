@@ -103,18 +103,23 @@ def _strides(shape: Sequence[int], order: str) -> List[int]:
     return st
 
 
+def _stream_handle(stream, device: int) -> int:
+    """The native handle of `stream` (a torch stream or a raw handle); None:
+    the device's current stream."""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream(device)
+    return s.cuda_stream if hasattr(s, "cuda_stream") else int(s)
+
+
 def assemble_region(meta: ArrayMetadata, bbox: BoundingBox, es: int, table, out, out_strides,
                     fill: bool, fill_value: int, device: int = 0, stream=None) -> None:
     """Device-level call: `table` = device int64 tensor of chunk pointers
     (C order over region_grid's range, 0 = absent), `out` = device tensor
     whose data_ptr() is element (0, ..., 0) of the output view."""
-    import torch
     ctx = _native.context(device)
     r = _region(meta, bbox, es, fill, fill_value, out_strides)
-    s = stream if stream is not None else torch.cuda.current_stream(device)
-    h = s.cuda_stream if hasattr(s, "cuda_stream") else int(s)
     st = ctx.lib.zcg_read_region(ctx.handle, ctypes.byref(r), table.data_ptr() if table is not None else None,
-                                 out.data_ptr(), h)
+                                 out.data_ptr(), _stream_handle(stream, device))
     _raise_status(st, ctx, "read_region")
 
 
@@ -123,13 +128,10 @@ def scatter_region(meta: ArrayMetadata, bbox: BoundingBox, es: int, table, box, 
     """Device-level inverse of assemble_region (zcg_write_region): the box
     (`box` = device tensor whose data_ptr() is element (0, ..., 0) of a view
     with `box_strides`) is written into the chunk slots of `table`."""
-    import torch
     ctx = _native.context(device)
     r = _region(meta, bbox, es, False, 0, box_strides)
-    s = stream if stream is not None else torch.cuda.current_stream(device)
-    h = s.cuda_stream if hasattr(s, "cuda_stream") else int(s)
     st = ctx.lib.zcg_write_region(ctx.handle, ctypes.byref(r), table.data_ptr() if table is not None else None,
-                                  box.data_ptr(), h)
+                                  box.data_ptr(), _stream_handle(stream, device))
     _raise_status(st, ctx, "write_region")
 
 
@@ -201,19 +203,17 @@ def assemble_regions(meta: ArrayMetadata, shape: Sequence[int], es: int, table, 
     table_lo .. table_lo + table_n (C order, 0 = absent), `boxes` = device
     tensor holding one _native.Box per box (offset per dim, output base),
     `status` = device int32 tensor, one word per box.  Asynchronous."""
-    import torch
     ctx = _native.context(device)
     nd = meta.get_ndim()
     r = _region(meta, BoundingBox([0] * nd, shape), es, fill, fill_value, out_strides)
     lo = (ctypes.c_uint64 * _native.MAX_DIMS)(*[int(x) for x in table_lo])
     n = (ctypes.c_uint64 * _native.MAX_DIMS)(*[int(x) for x in table_n])
     n_boxes = boxes.numel() * boxes.element_size() // ctypes.sizeof(_native.Box) if boxes is not None else 0
-    s = stream if stream is not None else torch.cuda.current_stream(device)
-    h = s.cuda_stream if hasattr(s, "cuda_stream") else int(s)
     st = ctx.lib.zcg_read_regions(ctx.handle, ctypes.byref(r), ctypes.addressof(lo), ctypes.addressof(n),
                                   table.data_ptr() if table is not None else None,
                                   boxes.data_ptr() if n_boxes else None, n_boxes,
-                                  status.data_ptr() if status is not None else None, h)
+                                  status.data_ptr() if status is not None else None,
+                                  _stream_handle(stream, device))
     _raise_status(st, ctx, "read_regions")
 
 
@@ -318,16 +318,13 @@ def write_ndarray(hier, path_name: str, meta: ArrayMetadata, offset: Sequence[in
     codec = BatchCodec(device)
     cap = codec.encode_bound(meta, D)
     box = torch.from_numpy(np.ascontiguousarray(array, dtype=dt).reshape(-1).view(np.uint8).copy()).to(dev)
-    ctx = _native.context(device)
-    r = _region(meta, bbox, es, False, 0, _strides(bbox.shape, "C"))
-    h = torch.cuda.current_stream(device).cuda_stream
     per = max(1, WRITE_BATCH_BYTES // max(D + cap, 1))
     for b0 in range(0, len(coords), per):
         _write_sub_batch(hier, path_name, meta, bbox, coords, b0, min(len(coords), b0 + per), dt, D, N, cap,
-                         box, ctx, r, h, codec, dev)
+                         box, device, dev)
 
 
-def _write_sub_batch(hier, path_name, meta, bbox, coords, b0, b1, dt, D, N, cap, box, ctx, r, h, codec, dev):
+def _write_sub_batch(hier, path_name, meta, bbox, coords, b0, b1, dt, D, N, cap, box, device, dev):
     """write_ndarray for coords[b0:b1]: read/decode the partly covered chunks
     into their slots (store get(): shared flock), scatter the box into all of
     them, encode and write every chunk file through the store's set()
@@ -350,7 +347,7 @@ def _write_sub_batch(hier, path_name, meta, bbox, coords, b0, b1, dt, D, N, cap,
             partial.append(i)  # fully overwritten chunks are not read (ndarray.rs:328-337)
     absent = []
     if partial:
-        st = store_read_device(meta, [paths[i] for i in partial], [ptrs[i] for i in partial], ctx.device)
+        st = store_read_device(meta, [paths[i] for i in partial], [ptrs[i] for i in partial], device)
         for k, i in enumerate(partial):
             if st[k] == _native.ABSENT:
                 absent.append(i)  # starts as fill value (ndarray.rs:357-368)
@@ -366,10 +363,9 @@ def _write_sub_batch(hier, path_name, meta, bbox, coords, b0, b1, dt, D, N, cap,
     table_h = np.zeros(len(coords), np.int64)
     table_h[b0:b1] = ptrs
     table = torch.from_numpy(table_h).to(dev)
-    _raise_status(ctx.lib.zcg_write_region(ctx.handle, ctypes.byref(r), table.data_ptr(), box.data_ptr(), h),
-                  ctx, "write_region")
+    scatter_region(meta, bbox, dt.itemsize, table, box, _strides(bbox.shape, "C"), device)
     torch.cuda.synchronize(dev)  # the store's streams read the slots next
-    st = store_write_device(meta, paths, ptrs, ctx.device)
+    st = store_write_device(meta, paths, ptrs, device)
     bad = np.nonzero(st != 0)[0]
     if len(bad):
         i = int(bad[0])
