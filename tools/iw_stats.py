@@ -72,6 +72,10 @@ names = {0: "rounds", 1: "blocks", 2: "stages", 3: "groups", 4: "p1_lane_it", 5:
          31: "far_batches_after_first"}
 d = {v: int(out[k]) for k, v in names.items()}
 res["per_chunk"] = {k: round(v / packed.n, 1) for k, v in d.items()}
+# lane efficiency of a pass: lane-steps used / (64 lanes x 8 steps x outer steps issued)
+res["lane_efficiency"] = {"pass1": round(d["p1_lane_it"] / max(1, 512 * d["p1_wave_it"]), 3),
+                          "pass2": round(d["p2_lane_it"] / max(1, 512 * d["p2_wave_it"]), 3)}
+res["decode_steps_per_chunk"] = round((d["p1_lane_it"] + d["p2_lane_it"]) / packed.n, 1)
 cyc = {k: v for k, v in d.items() if k.startswith("cyc_") and k not in ("cyc_total", "cyc_hdr_tables", "cyc_hdr_walk")}
 tot = max(1, sum(cyc.values()))
 res["cycle_share"] = {k: round(v / tot, 3) for k, v in cyc.items()}

@@ -16,8 +16,10 @@
 //    lane runs past its segment end it soon lands on a token start the next
 //    lane marked: from there that lane's list is the true path.  Lane 0 starts
 //    at the true position; the chain of sync points gives every lane the
-//    first valid token of its list.  Segments are long, so the resync tail
-//    costs ~15 % of the decode instead of the ~60 % that 256-bit segments cost.
+//    first valid token of its list (its rank among that lane's marks, counted
+//    for all synced lanes at once after the loop).  Segments are long, so the
+//    resync tail costs ~15 % of the decode instead of the ~60 % that 256-bit
+//    segments cost.
 //    A lane that hits an invalid code or an end-of-block in its own segment
 //    records it and keeps decoding after it (the record is real only if the
 //    lane's valid range reaches it), so a garbage path never ends a segment
@@ -320,15 +322,6 @@ __device__ __forceinline__ void iw_put(u16* pe, u32 n, u32 x, u32 y, u32 z, u32 
 // two source bytes (0-1 / 2-3 of w) as two final stage entries
 __device__ __forceinline__ u32 ie_lo(u32 w) { return __builtin_amdgcn_perm(0xFFFFFFFFu, w, 0x04010400u); }
 __device__ __forceinline__ u32 ie_hi(u32 w) { return __builtin_amdgcn_perm(0xFFFFFFFFu, w, 0x04030402u); }
-
-// tokens of a lane's list that start before word wi of its bitmap, plus the
-// marks in `part` (the bits of word wi below the position)
-__device__ __forceinline__ u32 iw_rank(const IwLds& L, u32 ks, const gu32* mw, u32 wi, u32 part) {
-    u32 c = __popc(part);
-#pragma unroll 8
-    for (u32 w = 0; w < wi; w++) c += __popc(w < IW_EMW ? L.u.hr.em[w][ks] : mw[w]);
-    return c;
-}
 
 // stream bit of token j of the list of `lm` (segment start + bits before it)
 __device__ __forceinline__ u32 iw_pos(const gu32* gl, u32 lm, u32 j, u32 seg0) {
@@ -649,7 +642,7 @@ __device__ __attribute__((always_inline)) IwRound iw_h_round(IwLds& L, u32 R0, u
         // marks yet, and w1 - w0 < 4 in almost every period: the second
         // half of the window is stored only when the lane got that far
         // (its zero words are stored when the window has slid onto them;
-        // pass 2 and iw_rank read no word past the marked extent)
+        // pass 2 and the rank count read no word past the marked extent)
         const u32 w1 = (q - p) >> 5;
         if (w0 < IW_MARKW) {
             *(gu32x4_a4*)(mk + w0) = u32x4{mv[0], mv[1], mv[2], mv[3]};
@@ -710,8 +703,7 @@ __device__ __attribute__((always_inline)) IwRound iw_h_round(IwLds& L, u32 R0, u
             if (off < lim) {
                 const u32 wi = off >> 5;
                 if (wi != cwi) { cwv = wi < IW_EMW ? L.u.hr.em[wi][ks] : marks[(u64)ks * IW_MWORDS + wi]; cwi = wi; }
-                if ((cwv >> (off & 31)) & 1u) {
-                    give = iw_rank(L, ks, marks + (u64)ks * IW_MWORDS, wi, cwv & ((1u << (off & 31)) - 1u));
+                if ((cwv >> (off & 31)) & 1u) {  // (its rank in that list: after the loop)
                     nxt = ks;
                     run2 = false;
                     continue;
@@ -735,6 +727,28 @@ __device__ __attribute__((always_inline)) IwRound iw_h_round(IwLds& L, u32 R0, u
             q += adv;
         }
         gr_absorb(bs, vC, vD);
+    }
+    // The sync tokens' ranks, for every synced lane at once: q is the synced
+    // start, in segment nxt; the rank is the number of that lane's token
+    // starts before it, counted from its mark words one word per trip over
+    // the wave's longest distance (<= IW_MARKW words).  Inside the loop the
+    // count was up to 32 dependent loads for one lane while 63 waited.
+    {
+        const bool syn = nxt < 64;
+        const u32 kn = syn ? nxt : 0u;
+        const u32 off = syn ? q - (R0 + kn * seg) : 0u;
+        const u32 wi = off >> 5;
+        const gu32* mw = marks + (u64)kn * IW_MWORDS;
+        const u32 wmax = (u32)__builtin_amdgcn_readlane((int)iw_incl_umax(wi), 63);
+        u32 c = 0;
+#pragma unroll 4
+        for (u32 w = 0; w <= wmax; w++) {
+            if (syn && w <= wi) {
+                const u32 v = w < IW_EMW ? L.u.hr.em[w][kn] : mw[w];
+                c += __popc(w < wi ? v : v & ((1u << (off & 31)) - 1u));
+            }
+        }
+        give = c;
     }
     if (dbg) {
         const u32 m1 = iw_wave_sum(it1), m2 = iw_wave_sum(it2);
