@@ -173,7 +173,13 @@ struct BzHostIO {
             // unRLE_obuf_to_output_FAST, randomised branch
             for (;;) {
                 for (;;) {
-                    if (pos == D) return zb::OUT_FULL;
+                    if (pos == D) {
+                        // BZ2_bzDecompress looks for the block's end whatever
+                        // the output loop returned: a block finished exactly
+                        // at D still has its CRC checked
+                        if (out_len == 0 && used == savePP) break;
+                        return zb::OUT_FULL;
+                    }
                     if (out_len == 0) break;
                     EMIT(out_ch);
                     out_len--;

@@ -280,8 +280,12 @@ def same_bz2(s, D):
 def test_bzip2_core_fuzz_vs_libbz2(seed):
     """Block parsing, selectors, code lengths, libbz2's limit/base/perm
     Huffman decoding, RUNA/RUNB + MTF, origPtr checks, the tPos walk,
-    unRLE_obuf_to_output_FAST, block/combined CRCs, randomised blocks and
-    the 32 KiB-window post-N behaviour, against libbz2 1.0.8."""
+    unRLE_obuf_to_output_FAST's plain branch, block/combined CRCs and the
+    32 KiB-window post-N behaviour, against libbz2 1.0.8.  Every stream here
+    comes from libbz2's encoder (whole, cut or with bytes flipped), which
+    never sets the randomised bit, never leaves a run of four without its
+    count and always writes a one-cycle L / origPtr pair: randomised blocks,
+    such runs and other chains are covered by tests/test_bz2_craft_host.py."""
     import bz2
     rng = np.random.default_rng(seed)
     for _ in range(80):

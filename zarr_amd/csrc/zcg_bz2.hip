@@ -332,6 +332,7 @@ struct BzShared {
     u32 nblock, orig, stored_crc, randomised, single, done_status;
     u64 out_pos;
     u32 p0;
+    u32 wrap;  // the chain's byte at position nblock, as libbz2 would fetch it
 };
 
 // LDS of the stage B/C workgroup
@@ -553,19 +554,24 @@ __device__ __forceinline__ int bz_block_bc(BzBcLds& X, const gu8* L, gu8* KB, u3
             T[k] = (u8)(w & 0xFF);
             p = w >> 8;
         }
+        sh.wrap = W[p] & 0xFF;  // p's cycle need not close at nblock
     }
 #undef BZ_IS_SAMPLE
 #undef BZ_SID
     __syncthreads();
     BZ_TSTAMP(4);
-    if (sh.randomised && tid == 0) {
-        // BZ_RAND_UPD_MASK: fetch F_{m+1} - 2 is XORed with 1
-        u32 f = 0, rt = 0;
-        for (;;) {
-            f += zb::kRNums[rt];
-            rt = (rt + 1) & 511;
-            if (f - 2 >= nblock) break;
-            T[f - 2] ^= 1;
+    if (tid == 0) {
+        if (sh.single) sh.wrap = T[0];  // one cycle: position nblock is the start again
+        if (sh.randomised) {
+            // BZ_RAND_UPD_MASK: fetch F_{m+1} - 2 is XORed with 1
+            u32 f = 0, rt = 0;
+            for (;;) {
+                f += zb::kRNums[rt];
+                rt = (rt + 1) & 511;
+                if (f - 2 >= nblock) break;
+                T[f - 2] ^= 1;
+            }
+            if (f - 2 == nblock) sh.wrap ^= 1;
         }
     }
     __syncthreads();
@@ -644,13 +650,18 @@ __device__ __forceinline__ int bz_block_bc(BzBcLds& X, const gu8* L, gu8* KB, u3
     if (tid == 0) {
         int fs = -1;
         if (tail4) {
-            // libbz2 reads the next chain byte (the cycle start) as the count,
-            // emits those copies, then reports the stream corrupt
-            const u32 g = (u32)T[0] ^ 0u;
+            // libbz2 fetches chain position nblock (masked by the schedule
+            // when randomised) as the count, emits those copies, then finds
+            // the block overrun.  Its randomised loop looks at the output
+            // space first, so a run that ends exactly at D is still OK; the
+            // plain loop looks at the overrun first, so there it is not.
+            const u32 g = sh.wrap;
             const u32 val = nblock ? (u32)T[nblock - 1] : 0u;
             u64 op = ob + blk_total;
             for (u32 r2 = 0; r2 < g && op < D; r2++, op++) dst[swap_pos(op, t)] = norm_byte((u8)val, t);
-            fs = (op >= D) ? ZCG_OK : ((vflags & ZCG_FLAG_DEBUG_COUNTERS) ? 20000 : ZCG_ERR_INVALID_DATA);
+            const u64 end = ob + blk_total + g;
+            const bool full = sh.randomised ? end >= D : end > D;
+            fs = full ? ZCG_OK : ((vflags & ZCG_FLAG_DEBUG_COUNTERS) ? 20000 : ZCG_ERR_INVALID_DATA);
         } else if (!complete) {
             fs = ZCG_OK;  // D reached inside the block
         } else if (tcrc[0] != sh.stored_crc && !(vflags & ZCG_FLAG_DEBUG_COUNTERS)) {
