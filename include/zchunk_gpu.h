@@ -348,6 +348,56 @@ int zcg_read_regions(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo
                      const void* const* d_chunk_table, const zcg_box* d_boxes, uint32_t n_boxes,
                      int32_t* d_status, void* stream);
 
+/* The inverse of zcg_read_regions, ZarrNdarrayWriter::write_ndarray's scatter
+ * (ndarray.rs:276-385) for n_boxes boxes of one shape in one launch.  The
+ * arguments are zcg_read_regions', except that zcg_box.out is the DEVICE base
+ * of the box's INPUT view (r->out_strides: its strides per array dim, in
+ * elements), which is only read, and that fill_missing and fill_value are
+ * ignored.
+ *  - Per-box equivalence: for every box whose status is ZCG_OK the bytes
+ *    written to the chunk slots are exactly those zcg_write_region writes for
+ *    a zcg_region with that bbox_offset and a table holding the same pointers
+ *    over that box's own zcg_region_grid range: every element of the box that
+ *    falls in a visited, non-NULL chunk is written, the overhang of edge
+ *    chunks beyond array_shape included; elements in chunks the box does not
+ *    visit are dropped; NULL entries are skipped.  A chunk inside the table
+ *    but outside the box's own grid range is never touched.
+ *  - A box whose own grid range is not inside the table's range gets
+ *    ZCG_ERR_INVALID_INPUT; nothing of it is written, and the other boxes are
+ *    unaffected.
+ *  - A box that visits no chunk is ZCG_OK and writes nothing.
+ *  - n_boxes == 0, or a zero extent in bbox_shape, returns ZCG_OK and launches
+ *    nothing (d_status is not written).
+ *  - bbox_shape[d] + chunk_shape[d] - 1 >= 2^32 returns ZCG_ERR_UNSUPPORTED.
+ *  - Overlapping boxes: two boxes of one call may write the same chunk
+ *    element.  It ends up with one of their values, whole (elements are at
+ *    most 8 bytes and naturally aligned); which box wins is unspecified.
+ *    Callers who need "the later box wins" split the call with
+ *    zcg_regions_waves and launch the waves in order on one stream.
+ *  - Asynchronous on `stream`; the number of launches does not depend on
+ *    n_boxes; the call allocates nothing and does not synchronize with the
+ *    host.  d_boxes is read when the kernel runs, so the call can be captured
+ *    in a graph and a replay sees new offsets and inputs. */
+int zcg_write_regions(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+                      void* const* d_chunk_table, const zcg_box* d_boxes, uint32_t n_boxes,
+                      int32_t* d_status, void* stream);
+
+/* A greedy split of a box list into consecutive runs ("waves") of pairwise
+ * disjoint boxes; host code, no GPU and no context.  `r` gives ndim,
+ * bbox_shape and chunk_shape; `offsets` is a host array of n_boxes*ndim,
+ * box-major; wave_of (n_boxes entries) receives each box's wave.  Box 0 is in
+ * wave 0; box b opens a new wave if and only if its extent intersects the
+ * extent of a box already in the current wave.  The extent is offsets[b] ..
+ * offsets[b] + bbox_shape, not clipped to the array, ends saturating at
+ * 2^64-1; two extents intersect when they share at least one element in every
+ * dimension.  wave_of is non-decreasing; the return value is the number of
+ * waves, 0 for n_boxes == 0.  With a zero extent in bbox_shape nothing
+ * intersects: one wave.  zcg_write_regions calls for the waves, in order on
+ * one stream, leave every shared element with the later box's value.  The
+ * cost is linear in n_boxes for disjoint boxes (a box is compared only with
+ * boxes that share a chunk-aligned cell with it). */
+uint32_t zcg_regions_waves(const zcg_region* r, const uint64_t* offsets, uint32_t n_boxes, uint32_t* wave_of);
+
 /* ---- FilesystemHierarchy chunk files ---------------
  * The e2e path's two ends: chunk files read into pinned staging by a pool of
  * `io_threads` host threads (open + shared flock + read, as ReadableStore::get,
@@ -490,6 +540,55 @@ int zcg_store_read_boxes_device(zcg_ctx* ctx, const zcg_array_meta* meta, const 
 int zcg_store_read_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
                          const uint64_t* box_shape, const uint64_t* offsets, void* const* outs, uint32_t n_boxes,
                          uint64_t slot_budget_bytes, uint32_t io_threads);
+
+/* ---- write_ndarray for many boxes, from the boxes to the store -----------
+ * ZarrNdarrayWriter::write_ndarray (ndarray.rs:276-385) for n_boxes boxes of
+ * one shape in one blocking call.  THE STORE ENDS UP AS IF write_ndarray HAD
+ * RUN FOR BOX 0, 1, ..., n_boxes-1 IN THAT ORDER, but a chunk that k boxes
+ * touch is read, encoded and written once, not k times.
+ *  - Chunks written: the union of the chunks the boxes visit
+ *    (bounded_coord_iter per box), each once per group, through
+ *    zcg_store_write_chunks_device (set(): exclusive flock, then truncate).
+ *    No other file is created or touched.
+ *  - Chunks read first: take the lowest-numbered box that visits the chunk.
+ *    If it does not cover the chunk's nominal bounds completely, the existing
+ *    file is read and decoded (zcg_store_read_chunks_device, shared flock;
+ *    decode flags, verify flags included, from meta->array.compression.flags),
+ *    and an absent file makes the slot start as fill value (meta->fill_value
+ *    when has_fill_value, else 0).  If it covers them completely the file is
+ *    not read (ndarray.rs:327-335): a corrupt old file is then harmless.
+ *  - Order: inside a group the boxes are scattered in the waves of
+ *    zcg_regions_waves, in order on one stream: a later box wins every element
+ *    it shares with an earlier one.
+ *  - Groups: consecutive boxes whose unique chunks need at most
+ *    slot_budget_bytes of decoded slots (0 = 4 GiB); a single box that alone
+ *    exceeds the budget runs as its own group; a chunk two groups share is
+ *    written by the first and read back by the second (zcg_store_read_boxes'
+ *    grouping).
+ *  - Before any file is read or written: a visited chunk outside the array's
+ *    chunk grid (zcg_store_read_boxes' rule) -> ZCG_ERR_INVALID_INPUT;
+ *    ndim != chunk_ndim -> ZCG_ERR_INVALID_DATA; a raw (rN) element type ->
+ *    ZCG_ERR_INVALID_INPUT; a union chunk table above 2^24 entries ->
+ *    ZCG_ERR_UNSUPPORTED (zcg_last_error says so).
+ *  - While running: the first chunk whose read status is neither ZCG_OK nor
+ *    ZCG_ABSENT makes the call return that status, and zcg_last_error names
+ *    its grid position; reads precede writes within a group, so nothing of
+ *    that group has been written, and earlier groups stay written.  The first
+ *    chunk that fails to write is returned and named in the same way.
+ *  - n_boxes == 0, or a zero extent in box_shape, returns ZCG_OK and writes
+ *    nothing.
+ * zcg_store_write_boxes_device takes box i from the DEVICE view d_ins[i]
+ * (in_strides per array dim, in elements).  zcg_store_write_boxes takes box i
+ * from the HOST buffer ins[i], dense in the chunk memory order (the layout
+ * zcg_store_read_boxes produces), staged with one H2D per group; n_boxes = 1
+ * is the reference's write_ndarray. */
+int zcg_store_write_boxes_device(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                                 const uint64_t* box_shape, const int64_t* in_strides, const uint64_t* offsets,
+                                 const void* const* d_ins, uint32_t n_boxes, uint64_t slot_budget_bytes,
+                                 uint32_t io_threads);
+int zcg_store_write_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                          const uint64_t* box_shape, const uint64_t* offsets, const void* const* ins,
+                          uint32_t n_boxes, uint64_t slot_budget_bytes, uint32_t io_threads);
 
 #ifdef __cplusplus
 }

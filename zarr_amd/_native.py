@@ -50,6 +50,7 @@ EXPORTED_SYMBOLS = (
     "zcg_array_meta_from_json", "zcg_chunk_key", "zcg_store_path",
     "zcg_store_read_chunks_device", "zcg_store_write_chunks_device",
     "zcg_regions_grid", "zcg_read_regions", "zcg_store_read_boxes_device", "zcg_store_read_boxes",
+    "zcg_write_regions", "zcg_regions_waves", "zcg_store_write_boxes_device", "zcg_store_write_boxes",
 )
 
 
@@ -200,6 +201,16 @@ def load_library(path: str = LIB_PATH):
         L.zcg_store_read_boxes.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
                                            vp, vp, vp, u32, u64, u32]
         L.zcg_store_read_boxes.restype = ctypes.c_int
+        L.zcg_write_regions.argtypes = [vp, ctypes.POINTER(Region), vp, vp, vp, vp, u32, vp, vp]
+        L.zcg_write_regions.restype = ctypes.c_int
+        L.zcg_regions_waves.argtypes = [ctypes.POINTER(Region), vp, u32, vp]
+        L.zcg_regions_waves.restype = u32
+        L.zcg_store_write_boxes_device.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
+                                                   vp, vp, vp, vp, u32, u64, u32]
+        L.zcg_store_write_boxes_device.restype = ctypes.c_int
+        L.zcg_store_write_boxes.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
+                                            vp, vp, vp, u32, u64, u32]
+        L.zcg_store_write_boxes.restype = ctypes.c_int
         _lib = L
         return L
 

@@ -623,9 +623,9 @@ uint64_t zcg_regions_grid(const zcg_region* r, const uint64_t* offsets, uint32_t
     return cnt;
 }
 
-int zcg_read_regions(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
-                     const void* const* d_chunk_table, const zcg_box* d_boxes, uint32_t n_boxes,
-                     int32_t* d_status, void* stream) {
+static int regions_call(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+                        const void* const* d_chunk_table, const zcg_box* d_boxes, uint32_t n_boxes,
+                        int32_t* d_status, void* stream, uint32_t dir) {
     if (n_boxes == 0) return region_head(ctx, r);
     RegionWalk w;
     uint64_t entries;
@@ -633,6 +633,7 @@ int zcg_read_regions(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo
                                "regions: box extent + chunk extent along a dimension must stay below 2^32 elements",
                                &w, &entries);
     if (rc != ZCG_OK) return rc;
+    if (dir) w.fill = 0;
     BoxTable bt{};
     bt.nboxes = n_boxes;
     for (uint32_t k = 0; k < w.nd; k++) {
@@ -649,9 +650,22 @@ int zcg_read_regions(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo
         return ZCG_ERR_UNSUPPORTED;
     }
     (void)hipSetDevice(ctx->device);
-    const hipError_t e = launch_regions(w, bt, d_chunk_table, d_boxes, d_status, (hipStream_t)stream);
+    const hipError_t e = launch_regions(w, bt, d_chunk_table, d_boxes, d_status, dir, (hipStream_t)stream);
     if (e != hipSuccess) return fail(ctx, e, "regions launch");
     return ZCG_OK;
+}
+
+int zcg_read_regions(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+                     const void* const* d_chunk_table, const zcg_box* d_boxes, uint32_t n_boxes,
+                     int32_t* d_status, void* stream) {
+    return regions_call(ctx, r, table_lo, table_n, d_chunk_table, d_boxes, n_boxes, d_status, stream, 0);
+}
+
+int zcg_write_regions(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+                      void* const* d_chunk_table, const zcg_box* d_boxes, uint32_t n_boxes, int32_t* d_status,
+                      void* stream) {
+    return regions_call(ctx, r, table_lo, table_n, (const void* const*)d_chunk_table, d_boxes, n_boxes, d_status,
+                        stream, 1);
 }
 
 }  // extern "C"

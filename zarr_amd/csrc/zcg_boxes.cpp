@@ -6,12 +6,18 @@
 //
 // Boxes are taken in consecutive groups whose unique chunks fit a budget of
 // decoded device slots; a chunk two groups share is decoded in each.
+//
+// write_ndarray for many boxes (ndarray.rs:276-385) is the same plan the other
+// way round: per group the chunks under a partial first box are read (absent
+// ones prefilled), the boxes are scattered in the waves of zcg_regions_waves
+// (zcg_write_regions per wave, so a later box wins), and every chunk of the
+// group is encoded and written once (zcg_store_write_chunks_device).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
 #include <string>
-#include <unordered_set>
+#include <unordered_map>
 #include <vector>
 
 #include "zcg_common.h"
@@ -43,7 +49,8 @@ struct Stream {
 
 struct Group {
     uint32_t b0, b1;
-    std::vector<uint64_t> keys;  // unique visited chunks, as linear indices over the array's grid
+    std::vector<uint64_t> keys;  // unique visited chunks, as linear indices over the array's grid, ascending
+    std::vector<uint8_t> read_first;  // write: per key, 1 = the chunk's file is read before the scatter
 };
 
 std::string pos_text(const uint64_t* pos, uint32_t nd) {
@@ -57,36 +64,64 @@ int fail_hip(zcg_ctx* ctx, hipError_t e, const char* what) {
     return ZCG_ERR_RUNTIME;
 }
 
-// host == true: outs are host buffers, each box dense in the chunk memory
-// order with fill (read_ndarray); else device views with the caller's strides
-int read_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
-               const uint64_t* box_shape, const int64_t* out_strides, uint32_t fill_missing,
-               const uint64_t* offsets, void* const* outs, uint32_t n_boxes, uint64_t slot_budget_bytes,
-               uint32_t io_threads, bool host) {
-    if (!ctx || !meta || !root || !path || !box_shape || (!host && !out_strides)) return ZCG_ERR_INVALID_INPUT;
-    if (n_boxes && (!offsets || !outs)) return ZCG_ERR_INVALID_INPUT;
+// What the box calls plan before any file is read or written: the region
+// descriptor every box shares, and the boxes in consecutive groups with each
+// group's unique chunks and union table range.
+struct Plan {
+    zcg_region r;
+    uint32_t nd = 0, es = 0;
+    uint64_t D = 0, box_elems = 1;      // bytes of a decoded chunk; elements of a box
+    uint64_t gstr[ZCG_MAX_DIMS];        // linear chunk keys over the array's grid
+    bool nothing = false;               // n_boxes == 0: the call is done
+    std::vector<Group> groups;
+    std::vector<uint64_t> glo, gn, gentries;  // per group: table range (ZCG_MAX_DIMS each), entries
+
+    void key_pos(uint64_t key, uint64_t* pos) const {
+        for (uint32_t d = 0; d < nd; d++) { pos[d] = key / gstr[d]; key -= pos[d] * gstr[d]; }
+    }
+};
+
+// Argument checks, the in-bounds check of every visited chunk (the reference
+// panics at storage.rs:217) and the grouping under the slot budget.  `what`
+// prefixes the messages.  host == true: boxes are host buffers, each dense in
+// the chunk memory order; else device views with the caller's strides.
+// cover == true (write): Group::read_first is filled in.
+int plan_boxes(zcg_ctx* ctx, const std::string& what, const zcg_array_meta* meta, const char* root, const char* path,
+               const uint64_t* box_shape, const int64_t* strides, uint32_t fill_missing, const uint64_t* offsets,
+               const void* const* bufs, uint32_t n_boxes, uint64_t slot_budget_bytes, bool host, bool cover,
+               Plan& P) {
+    if (!ctx || !meta || !root || !path || !box_shape || (!host && !strides)) return ZCG_ERR_INVALID_INPUT;
+    if (n_boxes && (!offsets || !bufs)) return ZCG_ERR_INVALID_INPUT;
     if (meta->ndim != meta->chunk_ndim) {
-        ctx_set_error(ctx, "read_boxes: shape and chunk_shape differ in their number of dimensions");
+        ctx_set_error(ctx, what + ": shape and chunk_shape differ in their number of dimensions");
         return ZCG_ERR_INVALID_DATA;
     }
     const uint32_t nd = meta->ndim;
     if (nd < 1 || nd > ZCG_MAX_DIMS) return ZCG_ERR_INVALID_INPUT;
     if (meta->dtype_kind == ZCG_DT_RAW) {
-        ctx_set_error(ctx, "read_boxes: raw (rN) element types have no ndarray form");
+        ctx_set_error(ctx, what + ": raw (rN) element types have no ndarray form");
         return ZCG_ERR_INVALID_INPUT;
     }
     const uint32_t es = meta->array.dtype.elem_size;
     if (es != 1 && es != 2 && es != 4 && es != 8) return ZCG_ERR_INVALID_INPUT;
-    if (n_boxes == 0) return ZCG_OK;
+    P.nd = nd;
+    P.es = es;
+    if (n_boxes == 0) {
+        P.nothing = true;
+        return ZCG_OK;
+    }
 
-    zcg_region r;
+    zcg_region& r = P.r;
+    uint64_t* gstr = P.gstr;
+    uint64_t& box_elems = P.box_elems;
     memset(&r, 0, sizeof r);
     r.ndim = nd;
     r.elem_size = es;
     r.chunk_order = meta->chunk_order;
     r.fill_missing = host ? 1u : (fill_missing ? 1u : 0u);
     r.fill_value = meta->has_fill_value ? meta->fill_value : 0;
-    uint64_t extent[ZCG_MAX_DIMS], gstr[ZCG_MAX_DIMS], box_elems = 1;
+    uint64_t extent[ZCG_MAX_DIMS];
+    box_elems = 1;
     for (uint32_t d = 0; d < nd; d++) {
         if (meta->chunk_shape[d] == 0) return ZCG_ERR_INVALID_INPUT;
         r.array_shape[d] = meta->shape[d];
@@ -100,28 +135,40 @@ int read_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const
         uint64_t g = 1;
         for (uint32_t k = 0; k < nd; k++) {
             const uint32_t d = meta->chunk_order == 1 ? k : nd - 1 - k;
-            r.out_strides[d] = host ? acc : out_strides[d];
+            r.out_strides[d] = host ? acc : strides[d];
             acc *= (int64_t)std::max<uint64_t>(box_shape[d], 1);
         }
         for (int d = (int)nd - 1; d >= 0; d--) {
             gstr[d] = g;
             if (extent[d] && g > (~0ull) / extent[d]) {
-                ctx_set_error(ctx, "read_boxes: the array's chunk grid exceeds 2^64 chunks");
+                ctx_set_error(ctx, what + ": the array's chunk grid exceeds 2^64 chunks");
                 return ZCG_ERR_UNSUPPORTED;
             }
             g *= extent[d];
         }
     }
-    const uint64_t D = meta->array.chunk_num_elements * (uint64_t)es;
+    const uint64_t D = P.D = meta->array.chunk_num_elements * (uint64_t)es;
     const uint64_t budget = slot_budget_bytes ? slot_budget_bytes : BOXES_DEFAULT_BUDGET;
 
-    // 1. every box's visited chunks: in bounds (the reference panics at
-    //    storage.rs:217), grouped under the slot budget — before any file is read
-    std::vector<Group> groups;
+    // every box's visited chunks: in bounds, grouped under the slot budget.
+    // seen: chunk key -> does the group's first box to visit it leave part of
+    // its nominal bounds uncovered (write: the chunk is read first)
+    std::vector<Group>& groups = P.groups;
     {
-        std::unordered_set<uint64_t> seen;
+        std::unordered_map<uint64_t, uint8_t> seen;
         std::vector<uint64_t> fresh;
-        Group cur{0, 0, {}};
+        Group cur{0, 0, {}, {}};
+        auto close = [&](uint32_t b1) {
+            cur.b1 = b1;
+            cur.keys.reserve(seen.size());
+            for (const auto& kv : seen) cur.keys.push_back(kv.first);
+            std::sort(cur.keys.begin(), cur.keys.end());
+            if (cover) {
+                cur.read_first.reserve(seen.size());
+                for (uint64_t k : cur.keys) cur.read_first.push_back(seen[k]);
+            }
+            groups.push_back(std::move(cur));
+        };
         for (uint32_t b = 0; b < n_boxes; b++) {
             uint64_t lo[ZCG_MAX_DIMS], n[ZCG_MAX_DIMS], pos[ZCG_MAX_DIMS];
             for (uint32_t d = 0; d < nd; d++) r.bbox_offset[d] = offsets[(size_t)b * nd + d];
@@ -129,110 +176,155 @@ int read_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const
             for (uint32_t d = 0; cnt && d < nd; d++)
                 if (lo[d] + n[d] > extent[d]) {
                     for (uint32_t k = 0; k < nd; k++) pos[k] = lo[k] + n[k] - 1;
-                    ctx_set_error(ctx, "read_boxes: box " + std::to_string(b) + " visits chunk " + pos_text(pos, nd) +
+                    ctx_set_error(ctx, what + ": box " + std::to_string(b) + " visits chunk " + pos_text(pos, nd) +
                                            " outside the array's chunk grid");
                     return ZCG_ERR_INVALID_INPUT;
                 }
             if (cnt > BOXES_MAX_TABLE) {
-                ctx_set_error(ctx, "read_boxes: a chunk table above 2^24 entries is not supported");
+                ctx_set_error(ctx, what + ": a chunk table above 2^24 entries is not supported");
                 return ZCG_ERR_UNSUPPORTED;
             }
-            auto visit = [&](std::unordered_set<uint64_t>& set, std::vector<uint64_t>& added) {
-                added.clear();
+            auto visit = [&]() {
+                fresh.clear();
                 for (uint64_t i = 0; i < cnt; i++) {
                     uint64_t rem = i, key = 0;
+                    bool part = false;
                     for (int d = (int)nd - 1; d >= 0; d--) {
-                        key += (lo[d] + rem % n[d]) * gstr[d];
+                        const uint64_t c = lo[d] + rem % n[d];
+                        key += c * gstr[d];
                         rem /= n[d];
+                        if (cover) {  // write_bb == nom_chunk_bb (ndarray.rs:327), per dimension
+                            const uint64_t cs = r.chunk_shape[d], o = r.bbox_offset[d], o1 = o + r.bbox_shape[d];
+                            part |= c * cs < o || c * cs + cs > (o1 < o ? ~0ull : o1);
+                        }
                     }
-                    if (set.insert(key).second) added.push_back(key);
+                    if (seen.emplace(key, part ? 1 : 0).second) fresh.push_back(key);
                 }
             };
-            visit(seen, fresh);
+            visit();
             if (b > cur.b0 && (uint64_t)seen.size() > budget / std::max<uint64_t>(D, 1)) {
                 // this box does not fit beside the others: it starts the next group
                 for (uint64_t k : fresh) seen.erase(k);
-                cur.b1 = b;
-                cur.keys.assign(seen.begin(), seen.end());
-                groups.push_back(std::move(cur));
-                cur = Group{b, b, {}};
+                close(b);
+                cur = Group{b, b, {}, {}};
                 seen.clear();
-                visit(seen, fresh);
+                visit();
             }
         }
-        cur.b1 = n_boxes;
-        cur.keys.assign(seen.begin(), seen.end());
-        groups.push_back(std::move(cur));
+        close(n_boxes);
     }
-    std::vector<uint64_t> glo(groups.size() * ZCG_MAX_DIMS), gn(groups.size() * ZCG_MAX_DIMS), gentries(groups.size());
+    P.glo.resize(groups.size() * ZCG_MAX_DIMS);
+    P.gn.resize(groups.size() * ZCG_MAX_DIMS);
+    P.gentries.resize(groups.size());
     for (size_t g = 0; g < groups.size(); g++) {
-        Group& G = groups[g];
-        std::sort(G.keys.begin(), G.keys.end());
-        gentries[g] = zcg_regions_grid(&r, offsets + (size_t)G.b0 * nd, G.b1 - G.b0, &glo[g * ZCG_MAX_DIMS],
-                                       &gn[g * ZCG_MAX_DIMS]);
-        if (gentries[g] > BOXES_MAX_TABLE) {
-            ctx_set_error(ctx, "read_boxes: the boxes' union chunk table (" + std::to_string(gentries[g]) +
-                                   " entries) exceeds 2^24; read the boxes in several calls");
+        const Group& G = groups[g];
+        P.gentries[g] = zcg_regions_grid(&r, offsets + (size_t)G.b0 * nd, G.b1 - G.b0, &P.glo[g * ZCG_MAX_DIMS],
+                                         &P.gn[g * ZCG_MAX_DIMS]);
+        if (P.gentries[g] > BOXES_MAX_TABLE) {
+            ctx_set_error(ctx, what + ": the boxes' union chunk table (" + std::to_string(P.gentries[g]) +
+                                   " entries) exceeds 2^24; split the boxes over several calls");
             return ZCG_ERR_UNSUPPORTED;
         }
     }
-    if (box_elems == 0) return ZCG_OK;
+    return ZCG_OK;
+}
+
+// The chunk files and device slots of a group: slot i (D bytes, packed) and
+// file i belong to chunk G.keys[i], table index tidx[i].
+struct GroupSlots {
+    DevMem slots;
+    std::vector<std::string> paths;
+    std::vector<const char*> cpaths;
+    std::vector<void*> ptrs;
+    std::vector<uint64_t> tidx;
+};
+
+int group_slots(zcg_ctx* ctx, const std::string& what, const zcg_array_meta* meta, const char* root,
+                const char* path, const Plan& P, size_t g, GroupSlots& S) {
+    const Group& G = P.groups[g];
+    const uint32_t nd = P.nd, m = (uint32_t)G.keys.size();
+    const uint64_t* lo = &P.glo[g * ZCG_MAX_DIMS];
+    const uint64_t* n = &P.gn[g * ZCG_MAX_DIMS];
+    const hipError_t e = S.slots.alloc((size_t)m * P.D);
+    if (e != hipSuccess) return fail_hip(ctx, e, (what + " slots").c_str());
+    S.paths.resize(m);
+    S.cpaths.resize(m);
+    S.ptrs.resize(m);
+    S.tidx.resize(m);
+    std::string key;
+    for (uint32_t i = 0; i < m; i++) {
+        uint64_t pos[ZCG_MAX_DIMS], ti = 0, tstr = 1;
+        P.key_pos(G.keys[i], pos);
+        for (int d = (int)nd - 1; d >= 0; d--) { ti += (pos[d] - lo[d]) * tstr; tstr *= n[d]; }
+        S.tidx[i] = ti;
+        key.resize(zcg_chunk_key(path, meta->separator, pos, nd, nullptr, 0) + 1);
+        zcg_chunk_key(path, meta->separator, pos, nd, &key[0], key.size());
+        uint64_t plen = 0;
+        int rc = zcg_store_path(root, key.c_str(), nullptr, 0, &plen);
+        if (rc == ZCG_OK) {
+            S.paths[i].resize(plen + 1);
+            rc = zcg_store_path(root, key.c_str(), &S.paths[i][0], plen + 1, nullptr);
+        }
+        if (rc != ZCG_OK) {
+            ctx_set_error(ctx, what + ": chunk " + pos_text(pos, nd) + ": key outside the hierarchy");
+            return rc;
+        }
+        S.cpaths[i] = S.paths[i].c_str();
+        S.ptrs[i] = (uint8_t*)S.slots.p + (size_t)i * P.D;
+    }
+    return ZCG_OK;
+}
+
+int chunk_failed(zcg_ctx* ctx, const std::string& what, const Plan& P, uint64_t key, int32_t status) {
+    uint64_t pos[ZCG_MAX_DIMS];
+    P.key_pos(key, pos);
+    ctx_set_error(ctx, what + ": chunk " + pos_text(pos, P.nd) + ": status " + std::to_string(status));
+    return status;
+}
+
+// host == true: outs are host buffers, each box dense in the chunk memory
+// order with fill (read_ndarray); else device views with the caller's strides
+int read_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+               const uint64_t* box_shape, const int64_t* out_strides, uint32_t fill_missing,
+               const uint64_t* offsets, void* const* outs, uint32_t n_boxes, uint64_t slot_budget_bytes,
+               uint32_t io_threads, bool host) {
+    const std::string what = "read_boxes";
+    Plan P;
+    // 1. before any file is read
+    const int prc = plan_boxes(ctx, what, meta, root, path, box_shape, out_strides, fill_missing, offsets, outs,
+                               n_boxes, slot_budget_bytes, host, false, P);
+    if (prc != ZCG_OK) return prc;
+    if (P.nothing || P.box_elems == 0) return ZCG_OK;
+    const zcg_region& r = P.r;
+    const uint32_t nd = P.nd, es = P.es;
 
     (void)hipSetDevice(ctx_device(ctx));
     Stream st;
     hipError_t e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
     if (e != hipSuccess) return fail_hip(ctx, e, "read_boxes stream");
-    const uint64_t box_bytes = box_elems * es;
+    const uint64_t box_bytes = P.box_elems * es;
 
     // 2. per group: read + decode its chunks once, build the table, one launch
-    for (size_t g = 0; g < groups.size(); g++) {
-        const Group& G = groups[g];
+    for (size_t g = 0; g < P.groups.size(); g++) {
+        const Group& G = P.groups[g];
         const uint32_t nb = G.b1 - G.b0, m = (uint32_t)G.keys.size();
-        const uint64_t* lo = &glo[g * ZCG_MAX_DIMS];
-        const uint64_t* n = &gn[g * ZCG_MAX_DIMS];
-        const uint64_t entries = gentries[g];
-        DevMem slots, meta_dev, staging;
+        const uint64_t* lo = &P.glo[g * ZCG_MAX_DIMS];
+        const uint64_t* n = &P.gn[g * ZCG_MAX_DIMS];
+        const uint64_t entries = P.gentries[g];
+        GroupSlots S;
+        DevMem meta_dev, staging;
         std::vector<const void*> table(std::max<uint64_t>(entries, 1), nullptr);
         if (m) {
-            if ((e = slots.alloc((size_t)m * D)) != hipSuccess) return fail_hip(ctx, e, "read_boxes slots");
-            std::vector<std::string> paths(m);
-            std::vector<const char*> cpaths(m);
-            std::vector<void*> dsts(m);
+            int rc = group_slots(ctx, what, meta, root, path, P, g, S);
+            if (rc != ZCG_OK) return rc;
             std::vector<int32_t> status(m, ZCG_OK);
-            std::vector<uint64_t> tidx(m);
-            std::string key;
-            for (uint32_t i = 0; i < m; i++) {
-                uint64_t pos[ZCG_MAX_DIMS], rem = G.keys[i], ti = 0, tstr = 1;
-                for (uint32_t d = 0; d < nd; d++) { pos[d] = rem / gstr[d]; rem -= pos[d] * gstr[d]; }
-                for (int d = (int)nd - 1; d >= 0; d--) { ti += (pos[d] - lo[d]) * tstr; tstr *= n[d]; }
-                tidx[i] = ti;
-                key.resize(zcg_chunk_key(path, meta->separator, pos, nd, nullptr, 0) + 1);
-                zcg_chunk_key(path, meta->separator, pos, nd, &key[0], key.size());
-                uint64_t plen = 0;
-                int rc = zcg_store_path(root, key.c_str(), nullptr, 0, &plen);
-                if (rc == ZCG_OK) {
-                    paths[i].resize(plen + 1);
-                    rc = zcg_store_path(root, key.c_str(), &paths[i][0], plen + 1, nullptr);
-                }
-                if (rc != ZCG_OK) {
-                    ctx_set_error(ctx, "read_boxes: chunk " + pos_text(pos, nd) + ": key outside the hierarchy");
-                    return rc;
-                }
-                cpaths[i] = paths[i].c_str();
-                dsts[i] = (uint8_t*)slots.p + (size_t)i * D;
-            }
-            const int rc = zcg_store_read_chunks_device(ctx, &meta->array, m, cpaths.data(), dsts.data(),
-                                                        status.data(), io_threads ? io_threads : 1);
+            rc = zcg_store_read_chunks_device(ctx, &meta->array, m, S.cpaths.data(), S.ptrs.data(), status.data(),
+                                              io_threads ? io_threads : 1);
             if (rc != ZCG_OK) return rc;
             for (uint32_t i = 0; i < m; i++) {
                 if (status[i] == ZCG_ABSENT) continue;  // read_chunk -> Ok(None): a NULL entry
-                if (status[i] != ZCG_OK) {
-                    uint64_t pos[ZCG_MAX_DIMS], rem = G.keys[i];
-                    for (uint32_t d = 0; d < nd; d++) { pos[d] = rem / gstr[d]; rem -= pos[d] * gstr[d]; }
-                    ctx_set_error(ctx, "read_boxes: chunk " + pos_text(pos, nd) + ": status " + std::to_string(status[i]));
-                    return status[i];
-                }
-                table[tidx[i]] = dsts[i];
+                if (status[i] != ZCG_OK) return chunk_failed(ctx, what, P, G.keys[i], status[i]);
+                table[S.tidx[i]] = S.ptrs[i];
             }
         }
         // device: [table entries][boxes nb][status nb]
@@ -292,7 +384,246 @@ int read_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const
     return ZCG_OK;
 }
 
+// write_ndarray for the boxes in order (ndarray.rs:276-385).  Per group: the
+// slots of chunks whose first visiting box is partial are read (or, absent,
+// prefilled); the boxes are scattered wave by wave; every slot is encoded and
+// written.  host == true: ins are host buffers, dense in the chunk memory order.
+int write_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                const uint64_t* box_shape, const int64_t* in_strides, const uint64_t* offsets,
+                const void* const* ins, uint32_t n_boxes, uint64_t slot_budget_bytes, uint32_t io_threads,
+                bool host) {
+    const std::string what = "write_boxes";
+    Plan P;
+    // 1. before any file is read or written
+    const int prc = plan_boxes(ctx, what, meta, root, path, box_shape, in_strides, 0, offsets, ins, n_boxes,
+                               slot_budget_bytes, host, true, P);
+    if (prc != ZCG_OK) return prc;
+    if (P.nothing || P.box_elems == 0) return ZCG_OK;
+    const zcg_region& r = P.r;
+    const uint32_t nd = P.nd, es = P.es;
+    const uint64_t fillv = meta->has_fill_value ? meta->fill_value : 0;
+    const uint32_t threads = io_threads ? io_threads : 1;
+
+    (void)hipSetDevice(ctx_device(ctx));
+    Stream st;
+    hipError_t e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
+    if (e != hipSuccess) return fail_hip(ctx, e, "write_boxes stream");
+    const uint64_t box_bytes = P.box_elems * es;
+    std::vector<uint32_t> wave_of;
+
+    for (size_t g = 0; g < P.groups.size(); g++) {
+        const Group& G = P.groups[g];
+        const uint32_t nb = G.b1 - G.b0, m = (uint32_t)G.keys.size();
+        if (m == 0) continue;  // no box of the group visits a chunk: nothing to write
+        const uint64_t* lo = &P.glo[g * ZCG_MAX_DIMS];
+        const uint64_t* n = &P.gn[g * ZCG_MAX_DIMS];
+        const uint64_t entries = P.gentries[g];
+        GroupSlots S;
+        DevMem meta_dev, staging;
+        int rc = group_slots(ctx, what, meta, root, path, P, g, S);
+        if (rc != ZCG_OK) return rc;
+
+        // 2. the existing chunks under a partial first box; absent ones start as fill value
+        std::vector<void*> absent;
+        {
+            std::vector<uint32_t> idx;
+            std::vector<const char*> rpaths;
+            std::vector<void*> rptrs;
+            for (uint32_t i = 0; i < m; i++)
+                if (G.read_first[i]) {
+                    idx.push_back(i);
+                    rpaths.push_back(S.cpaths[i]);
+                    rptrs.push_back(S.ptrs[i]);
+                }
+            if (!idx.empty()) {
+                std::vector<int32_t> status(idx.size(), ZCG_OK);
+                rc = zcg_store_read_chunks_device(ctx, &meta->array, (uint32_t)idx.size(), rpaths.data(), rptrs.data(),
+                                                  status.data(), threads);
+                if (rc != ZCG_OK) return rc;
+                for (size_t k = 0; k < idx.size(); k++) {
+                    if (status[k] == ZCG_ABSENT) absent.push_back(rptrs[k]);  // ndarray.rs:351-364
+                    else if (status[k] != ZCG_OK) return chunk_failed(ctx, what, P, G.keys[idx[k]], status[k]);
+                }
+            }
+        }
+
+        // 3. device: [table entries][boxes nb][status nb][absent slots]; every visited chunk has a slot
+        std::vector<void*> table(entries, nullptr);
+        for (uint32_t i = 0; i < m; i++) table[S.tidx[i]] = S.ptrs[i];
+        const size_t o_box = (entries * sizeof(void*) + 255) & ~(size_t)255;
+        const size_t o_st = (o_box + (size_t)nb * sizeof(zcg_box) + 255) & ~(size_t)255;
+        const size_t o_abs = (o_st + (size_t)nb * sizeof(int32_t) + 255) & ~(size_t)255;
+        if ((e = meta_dev.alloc(o_abs + absent.size() * sizeof(void*))) != hipSuccess)
+            return fail_hip(ctx, e, "write_boxes table");
+        if (host && (e = staging.alloc((size_t)nb * box_bytes)) != hipSuccess)
+            return fail_hip(ctx, e, "write_boxes staging");
+        std::vector<zcg_box> boxes(nb);
+        for (uint32_t i = 0; i < nb; i++) {
+            memset(&boxes[i], 0, sizeof(zcg_box));
+            for (uint32_t d = 0; d < nd; d++) boxes[i].offset[d] = offsets[(size_t)(G.b0 + i) * nd + d];
+            boxes[i].out = host ? (void*)((uint8_t*)staging.p + (size_t)i * box_bytes) : (void*)ins[G.b0 + i];
+        }
+        uint8_t* db = (uint8_t*)meta_dev.p;
+        std::vector<uint8_t> bounce;
+        e = hipMemcpyAsync(db, table.data(), entries * sizeof(void*), hipMemcpyHostToDevice, st.s);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(db + o_box, boxes.data(), (size_t)nb * sizeof(zcg_box), hipMemcpyHostToDevice, st.s);
+        if (e == hipSuccess && !absent.empty())
+            e = hipMemcpyAsync(db + o_abs, absent.data(), absent.size() * sizeof(void*), hipMemcpyHostToDevice, st.s);
+        if (e == hipSuccess && host) {
+            // one H2D per group: straight from the caller's boxes when they are
+            // consecutive in memory, else through a bounce buffer
+            bool dense = true;
+            for (uint32_t i = 1; i < nb && dense; i++)
+                dense = (const uint8_t*)ins[G.b0 + i] == (const uint8_t*)ins[G.b0] + (size_t)i * box_bytes;
+            const uint8_t* src = (const uint8_t*)ins[G.b0];
+            if (!dense) {
+                bounce.resize((size_t)nb * box_bytes);
+                for (uint32_t i = 0; i < nb; i++) memcpy(bounce.data() + (size_t)i * box_bytes, ins[G.b0 + i], box_bytes);
+                src = bounce.data();
+            }
+            e = hipMemcpyAsync(staging.p, src, (size_t)nb * box_bytes, hipMemcpyHostToDevice, st.s);
+        }
+        if (e == hipSuccess)
+            e = launch_slot_fill((void* const*)(db + o_abs), (uint32_t)absent.size(), P.D, es, fillv, st.s);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(st.s);  // the host vectors of an enqueued copy end with this scope
+            return fail_hip(ctx, e, "write_boxes H2D");
+        }
+
+        // 4. the scatter, wave by wave: a later box wins what it shares with an earlier one
+        wave_of.resize(nb);
+        zcg_regions_waves(&r, offsets + (size_t)G.b0 * nd, nb, wave_of.data());
+        for (uint32_t b0 = 0; b0 < nb;) {
+            uint32_t b1 = b0 + 1;
+            while (b1 < nb && wave_of[b1] == wave_of[b0]) b1++;
+            rc = zcg_write_regions(ctx, &r, lo, n, (void* const*)db, (const zcg_box*)(db + o_box) + b0, b1 - b0,
+                                   (int32_t*)(db + o_st) + b0, (void*)st.s);
+            if (rc != ZCG_OK) {
+                (void)hipStreamSynchronize(st.s);
+                return rc;
+            }
+            b0 = b1;
+        }
+        std::vector<int32_t> bst(nb, ZCG_OK);
+        e = hipMemcpyAsync(bst.data(), db + o_st, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, st.s);
+        if (e == hipSuccess) e = hipStreamSynchronize(st.s);
+        else (void)hipStreamSynchronize(st.s);
+        if (e != hipSuccess) return fail_hip(ctx, e, "write_boxes scatter");
+        for (uint32_t i = 0; i < nb; i++)
+            if (bst[i] != ZCG_OK) {
+                ctx_set_error(ctx, "write_boxes: box " + std::to_string(G.b0 + i) + ": status " + std::to_string(bst[i]));
+                return bst[i];
+            }
+
+        // 5. encode and write every chunk of the group, once
+        std::vector<int32_t> wst(m, ZCG_OK);
+        rc = zcg_store_write_chunks_device(ctx, &meta->array, m, S.cpaths.data(), (const void* const*)S.ptrs.data(),
+                                           wst.data(), threads);
+        if (rc != ZCG_OK) return rc;
+        for (uint32_t i = 0; i < m; i++)
+            if (wst[i] != ZCG_OK) return chunk_failed(ctx, what, P, G.keys[i], wst[i]);
+    }
+    return ZCG_OK;
+}
+
+// a box's cells along one dimension: first and last cell index
+struct CellRange {
+    uint64_t lo, hi;
+};
+
 }  // namespace
+
+extern "C" uint32_t zcg_regions_waves(const zcg_region* r, const uint64_t* offsets, uint32_t n_boxes,
+                                      uint32_t* wave_of) {
+    if (!r || !offsets || !wave_of || n_boxes == 0) return 0;
+    const uint32_t nd = r->ndim;
+    if (nd < 1 || nd > ZCG_MAX_DIMS) return 0;
+    bool empty = false;
+    for (uint32_t d = 0; d < nd; d++) empty |= r->bbox_shape[d] == 0;
+    if (empty) {
+        for (uint32_t b = 0; b < n_boxes; b++) wave_of[b] = 0;
+        return 1;
+    }
+    // Cells: per dimension the smallest multiple of the chunk extent that holds
+    // the box extent, so a box lies in at most two cells per dimension and two
+    // boxes that intersect share a cell.  A box is compared with the boxes of
+    // the current wave that are registered in one of its cells.
+    uint64_t cell[ZCG_MAX_DIMS];
+    for (uint32_t d = 0; d < nd; d++) {
+        const uint64_t cs = r->chunk_shape[d] ? r->chunk_shape[d] : 1, bs = r->bbox_shape[d];
+        const uint64_t k = bs / cs + (bs % cs ? 1 : 0);
+        cell[d] = k > (~0ull) / cs ? ~0ull : k * cs;
+    }
+    auto end_of = [&](uint64_t o, uint32_t d) {
+        const uint64_t e = o + r->bbox_shape[d];
+        return e < o ? ~0ull : e;  // saturating
+    };
+    std::unordered_map<uint64_t, std::vector<uint32_t>> cells;  // hash of the cell position -> boxes
+    uint32_t wave = 0;
+    for (uint32_t b = 0; b < n_boxes; b++) {
+        const uint64_t* ob = offsets + (size_t)b * nd;
+        CellRange cr[ZCG_MAX_DIMS];
+        bool has = true;  // false: the saturated extent is empty, the box intersects nothing
+        uint32_t ncell = 1;
+        for (uint32_t d = 0; d < nd; d++) {
+            const uint64_t e = end_of(ob[d], d);
+            if (e <= ob[d]) { has = false; break; }
+            cr[d] = CellRange{ob[d] / cell[d], (e - 1) / cell[d]};
+            ncell *= (uint32_t)(cr[d].hi - cr[d].lo + 1);
+        }
+        if (!has) {
+            wave_of[b] = wave;
+            continue;
+        }
+        uint64_t keys[1u << ZCG_MAX_DIMS];
+        for (uint32_t c = 0; c < ncell; c++) {
+            uint64_t h = 0x9E3779B97F4A7C15ull;
+            uint32_t rem = c;
+            for (uint32_t d = 0; d < nd; d++) {
+                const uint32_t w = (uint32_t)(cr[d].hi - cr[d].lo + 1);
+                h = (h ^ (cr[d].lo + rem % w)) * 0xFF51AFD7ED558CCDull;
+                h ^= h >> 32;
+                rem /= w;
+            }
+            keys[c] = h;
+        }
+        bool hit = false;
+        for (uint32_t c = 0; c < ncell && !hit; c++) {
+            auto it = cells.find(keys[c]);
+            if (it == cells.end()) continue;
+            for (uint32_t a : it->second) {
+                const uint64_t* oa = offsets + (size_t)a * nd;
+                bool meet = true;
+                for (uint32_t d = 0; d < nd && meet; d++)
+                    meet = std::max(oa[d], ob[d]) < std::min(end_of(oa[d], d), end_of(ob[d], d));
+                if (meet) { hit = true; break; }
+            }
+        }
+        if (hit) {
+            wave++;
+            cells.clear();
+        }
+        wave_of[b] = wave;
+        for (uint32_t c = 0; c < ncell; c++) cells[keys[c]].push_back(b);
+    }
+    return wave + 1;
+}
+
+extern "C" int zcg_store_write_boxes_device(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root,
+                                            const char* path, const uint64_t* box_shape, const int64_t* in_strides,
+                                            const uint64_t* offsets, const void* const* d_ins, uint32_t n_boxes,
+                                            uint64_t slot_budget_bytes, uint32_t io_threads) {
+    return write_boxes(ctx, meta, root, path, box_shape, in_strides, offsets, d_ins, n_boxes, slot_budget_bytes,
+                       io_threads, false);
+}
+
+extern "C" int zcg_store_write_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                                     const uint64_t* box_shape, const uint64_t* offsets, const void* const* ins,
+                                     uint32_t n_boxes, uint64_t slot_budget_bytes, uint32_t io_threads) {
+    return write_boxes(ctx, meta, root, path, box_shape, nullptr, offsets, ins, n_boxes, slot_budget_bytes,
+                       io_threads, true);
+}
 
 extern "C" int zcg_store_read_boxes_device(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root,
                                            const char* path, const uint64_t* box_shape, const int64_t* out_strides,

@@ -396,7 +396,11 @@ uint64_t xz_decode_ws_bytes(const zcg_array* a, uint32_t n);
 // dir 0: chunks -> box (read_ndarray), 1: box -> chunks (write_ndarray)
 hipError_t launch_region(const RegionWalk& w, const BoxTerms& t, uint32_t dir, hipStream_t s);
 hipError_t launch_regions(const RegionWalk& w, const BoxTable& bt, const void* const* d_table,
-                          const zcg_box* d_boxes, int32_t* d_status, hipStream_t s);
+                          const zcg_box* d_boxes, int32_t* d_status, uint32_t dir, hipStream_t s);
+// m device slots of D bytes (d_slots: DEVICE array of their bases, each a
+// multiple of `es`), filled with the element `fillv`
+hipError_t launch_slot_fill(void* const* d_slots, uint32_t m, uint64_t D, uint32_t es, uint64_t fillv,
+                            hipStream_t s);
 hipError_t launch_xz_encode(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n,
                             uint64_t* d_out_len, int32_t* d_status, void* ws, uint64_t ws_bytes,
                             hipStream_t s);

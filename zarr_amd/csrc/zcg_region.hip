@@ -3,7 +3,9 @@
 // (src/ndarray.rs:153-268) for chunks that the batch decoders already left in
 // HBM, for one bounding box per launch (zcg_read_region, zcg_write_region) or
 // many boxes of one common shape, each at its own offset and into its own
-// output view, from one shared chunk table (zcg_read_regions).
+// output view, from one shared chunk table (zcg_read_regions), or scattered
+// into it from its own input view (zcg_write_regions; the slot prefill of
+// chunks the store lacks is here too).
 //
 // Reference semantics kept: the chunks visited are bounded_coord_iter's grid
 // range (ndarray.rs:410-432); each visited chunk covers its full nominal
@@ -95,7 +97,10 @@ __global__ __launch_bounds__(RG_T) void region_rows_kernel(RegionWalk w, BoxTerm
     }
 }
 
-// Many boxes, short rows: a workgroup per (box, tile).
+// Many boxes, short rows: a workgroup per (box, tile).  DIR is the walk's
+// direction, fixed at compile time: the read kernels carry no trace of the
+// write direction.
+template <u32 DIR>
 __global__ __launch_bounds__(RG_T) void regions_kernel(RegionWalk w, BoxTable bt, const u8* const* __restrict__ table,
                                                        const zcg_box* __restrict__ boxes,
                                                        i32* __restrict__ status) {
@@ -106,11 +111,12 @@ __global__ __launch_bounds__(RG_T) void regions_kernel(RegionWalk w, BoxTable bt
         BoxTerms t;
         const bool in_table = box_terms(w, bt, table, boxes, b, t);
         box_status(status, b, in_table, tile == 0 && threadIdx.x == 0);
-        if (in_table) walk_tile(w, t, tile, 0);
+        if (in_table) walk_tile(w, t, tile, DIR);
     }
 }
 
 // Many boxes, long rows: a wave per (box, row, row piece).
+template <u32 DIR>
 __global__ __launch_bounds__(RG_T) void regions_rows_kernel(RegionWalk w, BoxTable bt,
                                                             const u8* const* __restrict__ table,
                                                             const zcg_box* __restrict__ boxes,
@@ -127,7 +133,38 @@ __global__ __launch_bounds__(RG_T) void regions_rows_kernel(RegionWalk w, BoxTab
         box_status(status, b, in_table, ub == 0 && (threadIdx.x & 63) == 0);
         if (!in_table) continue;
         const u64 row = ub / ppr;
-        walk_row_piece<ZCG_MAX_DIMS>(w, t, row, (u32)(ub - row * ppr), 0);
+        walk_row_piece<ZCG_MAX_DIMS>(w, t, row, (u32)(ub - row * ppr), DIR);
+    }
+}
+
+// Slot prefill (write_ndarray's chunk that is absent from the store and only
+// partly covered, ndarray.rs:351-364): m slots of D bytes, each all fill
+// element.  Slots are packed D apart and D is any multiple of the element
+// size, so a slot starts at an element boundary but mostly not at a 16-byte
+// one.  A slot is cut into a head up to the first 16-byte boundary (element
+// stores), aligned 16-byte pieces, and a tail below 16 bytes (element stores);
+// the head is a whole number of elements, so every aligned piece holds the
+// element pattern in phase.  A workgroup per (slot, run of RG_T pieces); piece
+// numbers nb and nb + 1 stand for the head and the tail.  No byte outside
+// [slot, slot + D) is written.
+__global__ __launch_bounds__(RG_T) void slot_fill_kernel(u8* const* __restrict__ slots, u32 m, u64 D, u32 es,
+                                                         u64 fillv, u32 per) {
+    const u32x4 f16 = fill_piece(fillv, es);
+    const u64 nunits = (u64)m * per;
+    for (u64 unit = blockIdx.x; unit < nunits; unit += gridDim.x) {
+        const u64 sl = unit / per;
+        u8* p = (u8*)(uintptr_t)ru64((u64)(uintptr_t)slots[sl]);
+        const u64 to16 = (16 - ((u64)(uintptr_t)p & 15)) & 15;
+        const u64 head = to16 < D ? to16 : D;
+        const u64 nb = (D - head) >> 4;
+        const u64 i = (unit - sl * per) * RG_T + threadIdx.x;
+        if (i < nb) {
+            *(u32x4*)(p + head + (i << 4)) = f16;
+        } else if (i == nb) {
+            for (u64 o = 0; o < head; o += es) fill_elem(p + o, fillv, es);
+        } else if (i == nb + 1) {
+            for (u64 o = head + (nb << 4); o < D; o += es) fill_elem(p + o, fillv, es);
+        }
     }
 }
 
@@ -164,13 +201,26 @@ hipError_t launch_region(const RegionWalk& w, const BoxTerms& t, uint32_t dir, h
 }
 
 hipError_t launch_regions(const RegionWalk& w, const BoxTable& bt0, const void* const* d_table,
-                          const zcg_box* d_boxes, int32_t* d_status, hipStream_t s) {
+                          const zcg_box* d_boxes, int32_t* d_status, uint32_t dir, hipStream_t s) {
     if (w.total == 0 || bt0.nboxes == 0) return hipSuccess;
     const LaunchShape g = launch_shape(w, bt0.nboxes);
     BoxTable bt = bt0;
     bt.upb = g.upb;
-    hipLaunchKernelGGL(g.rows ? regions_rows_kernel : regions_kernel, dim3(g.grid), dim3(RG_T), 0, s, w, bt,
-                       (const u8* const*)d_table, d_boxes, d_status);
+    auto kernel = g.rows ? (dir ? regions_rows_kernel<1> : regions_rows_kernel<0>)
+                         : (dir ? regions_kernel<1> : regions_kernel<0>);
+    hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(RG_T), 0, s, w, bt, (const u8* const*)d_table, d_boxes, d_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_slot_fill(void* const* d_slots, uint32_t m, uint64_t D, uint32_t es, uint64_t fillv,
+                            hipStream_t s) {
+    if (m == 0 || D == 0) return hipSuccess;
+    if (!(es == 1 || es == 2 || es == 4 || es == 8) || D % es) return hipErrorInvalidValue;
+    const u64 per = ((D >> 4) + 2 + RG_T - 1) / RG_T;
+    if (per >= (1ull << 32)) return hipErrorInvalidValue;
+    const u64 units = per * m;
+    hipLaunchKernelGGL(slot_fill_kernel, dim3((u32)(units < 262144 ? units : 262144)), dim3(RG_T), 0, s,
+                       (u8* const*)d_slots, m, D, es, fillv, (u32)per);
     return hipGetLastError();
 }
 

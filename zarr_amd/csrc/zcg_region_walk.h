@@ -44,13 +44,13 @@ __device__ __forceinline__ void fill_elem(u8* dst, u64 v, u32 es) {
 }
 
 // 16 bytes of the fill element
-__device__ __forceinline__ u32x4 fill_piece(const RegionWalk& w) {
-    u64 fv = w.fillv;
-    if (w.es == 1) fv = (fv & 0xFF) * 0x0101010101010101ull;
-    else if (w.es == 2) fv = (fv & 0xFFFF) * 0x0001000100010001ull;
-    else if (w.es == 4) fv = (fv & 0xFFFFFFFFull) * 0x0000000100000001ull;
+__device__ __forceinline__ u32x4 fill_piece(u64 fv, u32 es) {
+    if (es == 1) fv = (fv & 0xFF) * 0x0101010101010101ull;
+    else if (es == 2) fv = (fv & 0xFFFF) * 0x0001000100010001ull;
+    else if (es == 4) fv = (fv & 0xFFFFFFFFull) * 0x0000000100000001ull;
     return u32x4{(u32)fv, (u32)(fv >> 32), (u32)fv, (u32)(fv >> 32)};
 }
+__device__ __forceinline__ u32x4 fill_piece(const RegionWalk& w) { return fill_piece(w.fillv, w.es); }
 
 // where element p of the box is read from (nullptr: no visited chunk), and
 // how many elements from it stay in one chunk row and one box row

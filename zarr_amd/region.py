@@ -269,6 +269,107 @@ def read_ndarrays(hier, path_name: str, meta: ArrayMetadata, offsets, shape: Seq
     return res
 
 
+def scatter_regions(meta: ArrayMetadata, shape: Sequence[int], es: int, table, table_lo, table_n, boxes, status,
+                    box_strides, device: int = 0, stream=None) -> None:
+    """Device-level inverse of assemble_regions (zcg_write_regions): every box
+    (`boxes` = device tensor of _native.Box records whose `out` is element
+    (0, ..., 0) of the box's input view with `box_strides`) is written into the
+    chunk slots of `table`.  Boxes of one call that overlap leave either value;
+    split the call with regions_waves where the later box must win.
+    Asynchronous."""
+    ctx = _native.context(device)
+    nd = meta.get_ndim()
+    r = _region(meta, BoundingBox([0] * nd, shape), es, False, 0, box_strides)
+    lo = (ctypes.c_uint64 * _native.MAX_DIMS)(*[int(x) for x in table_lo])
+    n = (ctypes.c_uint64 * _native.MAX_DIMS)(*[int(x) for x in table_n])
+    n_boxes = boxes.numel() * boxes.element_size() // ctypes.sizeof(_native.Box) if boxes is not None else 0
+    st = ctx.lib.zcg_write_regions(ctx.handle, ctypes.byref(r), ctypes.addressof(lo), ctypes.addressof(n),
+                                   table.data_ptr() if table is not None else None,
+                                   boxes.data_ptr() if n_boxes else None, n_boxes,
+                                   status.data_ptr() if status is not None else None,
+                                   _stream_handle(stream, device))
+    _raise_status(st, ctx, "write_regions")
+
+
+def regions_waves(meta: ArrayMetadata, offsets, shape: Sequence[int]):
+    """zcg_regions_waves (host code, no GPU): the greedy split of the boxes
+    `offsets` (B x ndim) of one `shape` into consecutive runs of pairwise
+    disjoint boxes -> (number of waves, wave index per box).  scatter_regions
+    calls for the waves, in order on one stream, let the later box win."""
+    L = _native.load_library()
+    nd = meta.get_ndim()
+    r = _region(meta, BoundingBox([0] * nd, shape), 1, False, 0, [0] * nd)
+    offs = np.ascontiguousarray(np.array(offsets, dtype=np.uint64).reshape(-1, nd))
+    B = offs.shape[0]
+    wave_of = np.zeros(max(B, 1), np.uint32)
+    n = L.zcg_regions_waves(ctypes.byref(r), offs.ctypes.data, B, wave_of.ctypes.data)
+    return int(n), [int(w) for w in wave_of[:B]]
+
+
+def write_ndarrays(hier, path_name: str, meta: ArrayMetadata, offsets, arrays, device: int = 0,
+                   slot_budget_bytes: int = 0, flags: int = 0, shape: Sequence[int] = None) -> None:
+    """write_ndarray for many boxes of one shape in one native call
+    (zcg_store_write_boxes[_device]): the store ends up as if write_ndarray had
+    run for offsets[0], offsets[1], ... in that order (a later box wins where
+    two overlap), but every chunk the boxes touch is read at most once, and
+    encoded and written once.  `arrays` is a numpy array of shape (B, *shape),
+    or a uint8 device tensor holding the B boxes back to back, each dense in
+    the chunk memory order — what read_ndarrays(..., as_tensor=True) returns,
+    so a read / modify / write round trip needs no host copy; a flat tensor
+    does not say the box shape, which `shape` then gives.  `flags`: decode
+    flags for the chunks that are read first; `slot_budget_bytes` bounds the
+    decoded chunks held on the device at a time (0: 4 GiB)."""
+    tensor_in = not isinstance(arrays, np.ndarray) and hasattr(arrays, "data_ptr")
+    nd = meta.get_ndim()
+    if tensor_in:
+        tensor = arrays
+        if shape is None:
+            raise ZarrIOError("InvalidInput", "a device tensor of boxes needs the box shape")
+        shape = [int(x) for x in shape]
+        if len(shape) != nd:
+            raise ZarrIOError("InvalidData", "Wrong number of dimensions")
+        dt = np.dtype(meta.effective_type().numpy_dtype()).newbyteorder("=")
+    else:
+        arrays = np.asarray(arrays)
+        if arrays.ndim != nd + 1:
+            raise ZarrIOError("InvalidData", "Wrong number of dimensions")
+        shape = [int(x) for x in arrays.shape[1:]]
+        dt = arrays.dtype.newbyteorder("=")
+    check_array_type(dt, meta)
+    es = dt.itemsize
+    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64).reshape(-1, nd))
+    B = offs.shape[0]
+    order = "F" if meta.chunk_memory_layout == "F" else "C"
+    total = int(np.prod(shape)) if shape else 1
+    if not tensor_in and arrays.shape[0] != B:
+        raise ZarrIOError("InvalidData", "Bounding boxes and arrays differ in number")
+    st, am, msg = _native.array_meta_from_json(meta.to_json())
+    if st != _native.OK:
+        raise ZarrIOError(_native.STATUS_NAMES.get(st, str(st)), f"array metadata: {msg}")
+    am.array.compression.flags = flags
+    ctx = _native.context(device)
+    bshape = (ctypes.c_uint64 * _native.MAX_DIMS)(*shape)
+    root, path = os.fsencode(hier.base_path), path_name.encode()
+    if tensor_in:
+        if tensor.numel() * tensor.element_size() < B * total * es:
+            raise ZarrIOError("InvalidData", "Bounding boxes and array have different shape")
+        ins = (ctypes.c_void_p * max(B, 1))(*[tensor.data_ptr() + b * total * es for b in range(B)])
+        istr = (ctypes.c_int64 * _native.MAX_DIMS)(*_strides(shape, order))
+        r = ctx.lib.zcg_store_write_boxes_device(ctx.handle, ctypes.byref(am), root, path, ctypes.addressof(bshape),
+                                                 ctypes.addressof(istr), offs.ctypes.data, ctypes.addressof(ins), B,
+                                                 slot_budget_bytes, 16)
+    else:
+        # box b dense in the chunk memory order, the boxes back to back
+        host = np.ascontiguousarray(arrays.astype(dt, copy=False).transpose([0] + list(range(nd, 0, -1)))
+                                    if order == "F" else arrays.astype(dt, copy=False))
+        base = host.ctypes.data if host.size else 0
+        ins = (ctypes.c_void_p * max(B, 1))(*[base + b * total * es for b in range(B)])
+        r = ctx.lib.zcg_store_write_boxes(ctx.handle, ctypes.byref(am), root, path, ctypes.addressof(bshape),
+                                          offs.ctypes.data, ctypes.addressof(ins), B, slot_budget_bytes, 16)
+    if r != _native.OK:
+        raise ZarrIOError(_native.STATUS_NAMES.get(r, str(r)), f"write_boxes: {ctx.last_error()}")
+
+
 def read_ndarray_into(hier, path_name: str, meta: ArrayMetadata, bbox: BoundingBox, arr: np.ndarray, t,
                       device: int = 0, flags: int = 0) -> None:
     """ZarrNdarrayReader::read_ndarray_into (ndarray.rs:176-268): elements
