@@ -398,6 +398,93 @@ int zcg_write_regions(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_l
  * boxes that share a chunk-aligned cell with it). */
 uint32_t zcg_regions_waves(const zcg_region* r, const uint64_t* offsets, uint32_t n_boxes, uint32_t* wave_of);
 
+/* ---- many bounding boxes of differing shapes in one call ----------------
+ * The reference's read_ndarray / write_ndarray (ndarray.rs:153-385) take any
+ * BoundingBox per call: object or segment bounding boxes, detections, halo
+ * reads whose extent depends on the position, multi-scale crops.  The _v calls
+ * are zcg_read_regions / zcg_write_regions with a shape and a view per box. */
+typedef struct zcg_vbox {
+    uint64_t offset[ZCG_MAX_DIMS];   /* bbox_offset, per array dim                */
+    uint64_t shape[ZCG_MAX_DIMS];    /* this box's bbox_shape, per array dim      */
+    int64_t  strides[ZCG_MAX_DIMS];  /* its view's strides per array dim, elements */
+    void*    base;                   /* DEVICE element (0,..,0) of its view       */
+} zcg_vbox;
+
+/* zcg_regions_grid and zcg_regions_waves with a shape per box: `shapes` is a
+ * host array of n_boxes*ndim, box-major, as `offsets` is; r->bbox_shape is the
+ * bound of the _v calls (no box is expected to exceed it) and r->bbox_offset
+ * is ignored.  Host code, no GPU and no context.
+ *  - zcg_regions_v_grid: the union of the boxes' own zcg_region_grid ranges;
+ *    the return value and lo / n are zcg_regions_grid's.
+ *  - zcg_regions_v_waves: the waves are defined exactly as zcg_regions_waves'
+ *    (greedy and consecutive: box b opens a new wave if and only if its
+ *    unclipped extent offsets[b] .. offsets[b] + shapes[b], ends saturating,
+ *    intersects the extent of a box of the current wave); a box with a zero
+ *    extent intersects nothing.  With one shape repeated the result is
+ *    zcg_regions_waves'.  Boxes are hashed into cells whose extent is the
+ *    smallest multiple of the chunk extent that holds r->bbox_shape (or the
+ *    largest box, should one exceed it), so every box lies in at most two
+ *    cells per dimension.  The cost is linear in n_boxes for disjoint boxes of
+ *    similar size; it degrades towards quadratic when many small boxes share
+ *    one large cell (one large box sets the cell extent for all). */
+uint64_t zcg_regions_v_grid (const zcg_region* r, const uint64_t* offsets, const uint64_t* shapes,
+                             uint32_t n_boxes, uint64_t* lo, uint64_t* n);
+uint32_t zcg_regions_v_waves(const zcg_region* r, const uint64_t* offsets, const uint64_t* shapes,
+                             uint32_t n_boxes, uint32_t* wave_of);
+
+/* Bytes of DEVICE working memory a _v call with n_boxes boxes needs
+ * (d_scratch, 8-byte aligned); monotonic in n_boxes. */
+uint64_t zcg_regions_v_scratch_bytes(uint32_t n_boxes);
+
+/* `r` gives ndim, elem_size, chunk_order, fill_missing, fill_value,
+ * array_shape and chunk_shape for every box.  r->bbox_shape[d] is the LARGEST
+ * EXTENT ANY BOX OF THE CALL MAY HAVE along dimension d: the host checks it
+ * and sizes the launch from it without reading device memory.  r->bbox_offset
+ * and r->out_strides are ignored.  The table arguments are zcg_read_regions'.
+ * d_boxes (zcg_vbox) and d_status are DEVICE arrays of n_boxes entries;
+ * zcg_vbox.base is the box's output view for zcg_read_regions_v and its input
+ * view, which is only read, for zcg_write_regions_v (which also ignores
+ * fill_missing and fill_value).
+ *  - Per-box equivalence: for every box whose status is ZCG_OK the bytes
+ *    written are exactly those zcg_read_region (zcg_write_region) writes for a
+ *    zcg_region with that box's offset, shape and strides and a table holding
+ *    the same pointers over that box's own zcg_region_grid range: clipping to
+ *    array_shape, overhanging edge chunks, fill versus untouched, NULL entries.
+ *    A chunk inside the table but outside the box's own grid range is never
+ *    touched.
+ *  - A box with shape[d] > r->bbox_shape[d] for some d gets
+ *    ZCG_ERR_INVALID_INPUT; nothing of it is written, and the other boxes are
+ *    unaffected.  The same holds for a box whose own grid range is not inside
+ *    the table's range.
+ *  - A box with a zero extent is ZCG_OK and writes nothing.  A box that visits
+ *    no chunk is ZCG_OK, and filled on the read side when fill_missing is set.
+ *  - Every box's status word is written, also for boxes that have no work.
+ *  - r->bbox_shape[d] + chunk_shape[d] - 1 >= 2^32 returns
+ *    ZCG_ERR_UNSUPPORTED; so does n_boxes x the bound's elements >= 2^62.
+ *  - n_boxes == 0 returns ZCG_OK and launches nothing.
+ *  - Asynchronous on `stream`: two launches (a plan kernel that checks every
+ *    box and writes the status words and a prefix sum of work units into
+ *    d_scratch, and the walk), whatever n_boxes and the shapes are.  The call
+ *    allocates nothing and does not synchronize with the host; its only
+ *    working memory is d_scratch (zcg_regions_v_scratch_bytes(n_boxes) bytes),
+ *    which may be reused once the call's kernels have run.  d_boxes is read
+ *    when the kernels run, so the call can be captured in a graph and a replay
+ *    sees new offsets, SHAPES, strides and bases, as long as the shapes stay
+ *    inside the bound.  Work follows the sum of the boxes' sizes, not
+ *    n_boxes x the bound.
+ *  - Overlapping boxes on the write side: zcg_write_regions' rule.  An element
+ *    ends up with one of the values, whole; which box wins is unspecified.
+ *    Callers who need "the later box wins" split the call with
+ *    zcg_regions_v_waves and launch the waves in order on one stream (each
+ *    with its own part of d_status; d_scratch may be shared).
+ *  - Output views of different boxes that overlap are the caller's business. */
+int zcg_read_regions_v (zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+                        const void* const* d_chunk_table, const zcg_vbox* d_boxes, uint32_t n_boxes,
+                        void* d_scratch, int32_t* d_status, void* stream);
+int zcg_write_regions_v(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+                        void* const* d_chunk_table, const zcg_vbox* d_boxes, uint32_t n_boxes,
+                        void* d_scratch, int32_t* d_status, void* stream);
+
 /* ---- FilesystemHierarchy chunk files ---------------
  * The e2e path's two ends: chunk files read into pinned staging by a pool of
  * `io_threads` host threads (open + shared flock + read, as ReadableStore::get,
@@ -521,8 +608,9 @@ int zcg_store_path(const char* root, const char* key, char* out, uint64_t cap, u
  *    lib.rs:340-342, over-count included) -> ZCG_ERR_INVALID_INPUT before any
  *    file is read;
  *  - ndim != chunk_ndim -> ZCG_ERR_INVALID_DATA; a raw (rN) element type ->
- *    ZCG_ERR_INVALID_INPUT; a union chunk table above 2^24 entries ->
- *    ZCG_ERR_UNSUPPORTED (zcg_last_error says so);
+ *    ZCG_ERR_INVALID_INPUT; a union chunk table above 2^24 entries, or boxes
+ *    that hold more than 2^62 bytes in all, -> ZCG_ERR_UNSUPPORTED
+ *    (zcg_last_error says so);
  *  - device memory: boxes are taken in consecutive groups whose unique chunks
  *    need at most slot_budget_bytes of decoded slots (0 = 4 GiB); a single box
  *    that alone exceeds the budget runs as its own group; a chunk two groups
@@ -568,8 +656,9 @@ int zcg_store_read_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* r
  *  - Before any file is read or written: a visited chunk outside the array's
  *    chunk grid (zcg_store_read_boxes' rule) -> ZCG_ERR_INVALID_INPUT;
  *    ndim != chunk_ndim -> ZCG_ERR_INVALID_DATA; a raw (rN) element type ->
- *    ZCG_ERR_INVALID_INPUT; a union chunk table above 2^24 entries ->
- *    ZCG_ERR_UNSUPPORTED (zcg_last_error says so).
+ *    ZCG_ERR_INVALID_INPUT; a union chunk table above 2^24 entries, or boxes
+ *    that hold more than 2^62 bytes in all, -> ZCG_ERR_UNSUPPORTED
+ *    (zcg_last_error says so).
  *  - While running: the first chunk whose read status is neither ZCG_OK nor
  *    ZCG_ABSENT makes the call return that status, and zcg_last_error names
  *    its grid position; reads precede writes within a group, so nothing of
@@ -589,6 +678,45 @@ int zcg_store_write_boxes_device(zcg_ctx* ctx, const zcg_array_meta* meta, const
 int zcg_store_write_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
                           const uint64_t* box_shape, const uint64_t* offsets, const void* const* ins,
                           uint32_t n_boxes, uint64_t slot_budget_bytes, uint32_t io_threads);
+
+/* ---- read_ndarray / write_ndarray for many boxes of differing shapes ------
+ * The four calls above with a shape per box: `box_shapes` holds n_boxes*ndim
+ * extents, box-major, as `offsets` does.  Everything else carries over word
+ * for word: the planning, the in-grid check before any file is touched, the
+ * grouping by slot_budget_bytes, the rule for chunks read first (the
+ * lowest-numbered box that visits the chunk covers its nominal bounds
+ * completely -> the file is not read), the order (the waves of
+ * zcg_regions_v_waves: a later box wins), the error reporting (the first
+ * failing chunk is named by zcg_last_error) and the 2^24 table limit.  Each
+ * shared chunk is read, decoded, encoded and written once; the boxes are
+ * assembled or scattered by zcg_read_regions_v / zcg_write_regions_v, whose
+ * bound is the largest extent per dimension among the boxes.
+ *  - The _device forms take box i at the DEVICE view d_outs[i] / d_ins[i] with
+ *    the strides out_strides / in_strides + i*ndim (n_boxes*ndim entries, per
+ *    array dim, in elements); a NULL strides array means every box is dense in
+ *    the chunk memory order.
+ *  - The host forms take box i at the HOST buffer outs[i] / ins[i], dense in
+ *    the chunk memory order with its own shape.
+ *  - A box with a zero extent reads and writes nothing; n_boxes == 0 returns
+ *    ZCG_OK.
+ *  - A largest extent + chunk extent - 1 >= 2^32 along a dimension ->
+ *    ZCG_ERR_UNSUPPORTED.
+ * For n_boxes = 1 these calls are the reference's read_ndarray /
+ * write_ndarray. */
+int zcg_store_read_boxes_v_device(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                                  const uint64_t* box_shapes, const int64_t* out_strides, uint32_t fill_missing,
+                                  const uint64_t* offsets, void* const* d_outs, uint32_t n_boxes,
+                                  uint64_t slot_budget_bytes, uint32_t io_threads);
+int zcg_store_read_boxes_v(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                           const uint64_t* box_shapes, const uint64_t* offsets, void* const* outs,
+                           uint32_t n_boxes, uint64_t slot_budget_bytes, uint32_t io_threads);
+int zcg_store_write_boxes_v_device(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                                   const uint64_t* box_shapes, const int64_t* in_strides, const uint64_t* offsets,
+                                   const void* const* d_ins, uint32_t n_boxes, uint64_t slot_budget_bytes,
+                                   uint32_t io_threads);
+int zcg_store_write_boxes_v(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                            const uint64_t* box_shapes, const uint64_t* offsets, const void* const* ins,
+                            uint32_t n_boxes, uint64_t slot_budget_bytes, uint32_t io_threads);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,8 @@ from .metadata import ArrayMetadata, u64_ceil_div
 from .chunk import (DefaultChunk, SliceDataChunk, VecDataChunk, ZarrIOError, check_array_type,
                     read_chunks_host)
 from .storage import FilesystemHierarchy, get_chunk_key
-from .region import BoundingBox, read_ndarray, read_ndarrays, write_ndarray, write_ndarrays
+from .region import (BoundingBox, read_ndarray, read_ndarrays, read_ndarrays_v, write_ndarray, write_ndarrays,
+                     write_ndarrays_v)
 from ._native import NativeUnavailable
 
 __all__ = [
@@ -21,6 +22,6 @@ __all__ = [
     "ExtendedDataType", "FilesystemHierarchy", "GZIP_CODEC_ID", "Gzip", "Lz4", "MetadataError",
     "NATIVE_ENDIAN", "NativeUnavailable", "REFLECTED_TYPES", "Raw", "SliceDataChunk",
     "VecDataChunk", "Xz", "ZarrIOError", "check_array_type", "effective_type", "get_chunk_key",
-    "read_chunks_host", "read_ndarray", "read_ndarrays", "u64_ceil_div", "write_ndarray",
-    "write_ndarrays", "zarr_type",
+    "read_chunks_host", "read_ndarray", "read_ndarrays", "read_ndarrays_v", "u64_ceil_div", "write_ndarray",
+    "write_ndarrays", "write_ndarrays_v", "zarr_type",
 ]

@@ -51,6 +51,10 @@ EXPORTED_SYMBOLS = (
     "zcg_store_read_chunks_device", "zcg_store_write_chunks_device",
     "zcg_regions_grid", "zcg_read_regions", "zcg_store_read_boxes_device", "zcg_store_read_boxes",
     "zcg_write_regions", "zcg_regions_waves", "zcg_store_write_boxes_device", "zcg_store_write_boxes",
+    "zcg_regions_v_grid", "zcg_regions_v_waves", "zcg_regions_v_scratch_bytes",
+    "zcg_read_regions_v", "zcg_write_regions_v",
+    "zcg_store_read_boxes_v_device", "zcg_store_read_boxes_v",
+    "zcg_store_write_boxes_v_device", "zcg_store_write_boxes_v",
 )
 
 
@@ -95,6 +99,13 @@ class Box(ctypes.Structure):
     _fields_ = [("offset", ctypes.c_uint64 * MAX_DIMS), ("out", ctypes.c_void_p)]
 
 
+class VBox(ctypes.Structure):
+    """zcg_vbox: one bounding box of a batched call with a shape per box (offset, shape and view strides per
+    array dim, DEVICE base of the view)."""
+    _fields_ = [("offset", ctypes.c_uint64 * MAX_DIMS), ("shape", ctypes.c_uint64 * MAX_DIMS),
+                ("strides", ctypes.c_int64 * MAX_DIMS), ("base", ctypes.c_void_p)]
+
+
 class ArrayMeta(ctypes.Structure):
     _fields_ = [("array", Array), ("ndim", ctypes.c_uint32), ("chunk_ndim", ctypes.c_uint32),
                 ("chunk_order", ctypes.c_uint32), ("dtype_kind", ctypes.c_uint32),
@@ -108,6 +119,7 @@ assert ctypes.sizeof(Region) == 16 + 5 * 8 * MAX_DIMS + 8
 assert ctypes.sizeof(Compression) == 24 and ctypes.sizeof(Array) == 40
 assert ctypes.sizeof(Chunk) == 32
 assert ctypes.sizeof(Box) == 8 * MAX_DIMS + 8
+assert ctypes.sizeof(VBox) == 3 * 8 * MAX_DIMS + 8
 
 _lib = None
 _lock = threading.Lock()
@@ -211,6 +223,28 @@ def load_library(path: str = LIB_PATH):
         L.zcg_store_write_boxes.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
                                             vp, vp, vp, u32, u64, u32]
         L.zcg_store_write_boxes.restype = ctypes.c_int
+        L.zcg_regions_v_grid.argtypes = [ctypes.POINTER(Region), vp, vp, u32, vp, vp]
+        L.zcg_regions_v_grid.restype = u64
+        L.zcg_regions_v_waves.argtypes = [ctypes.POINTER(Region), vp, vp, u32, vp]
+        L.zcg_regions_v_waves.restype = u32
+        L.zcg_regions_v_scratch_bytes.argtypes = [u32]
+        L.zcg_regions_v_scratch_bytes.restype = u64
+        L.zcg_read_regions_v.argtypes = [vp, ctypes.POINTER(Region), vp, vp, vp, vp, u32, vp, vp, vp]
+        L.zcg_read_regions_v.restype = ctypes.c_int
+        L.zcg_write_regions_v.argtypes = [vp, ctypes.POINTER(Region), vp, vp, vp, vp, u32, vp, vp, vp]
+        L.zcg_write_regions_v.restype = ctypes.c_int
+        L.zcg_store_read_boxes_v_device.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
+                                                    vp, vp, u32, vp, vp, u32, u64, u32]
+        L.zcg_store_read_boxes_v_device.restype = ctypes.c_int
+        L.zcg_store_read_boxes_v.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
+                                             vp, vp, vp, u32, u64, u32]
+        L.zcg_store_read_boxes_v.restype = ctypes.c_int
+        L.zcg_store_write_boxes_v_device.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
+                                                     vp, vp, vp, vp, u32, u64, u32]
+        L.zcg_store_write_boxes_v_device.restype = ctypes.c_int
+        L.zcg_store_write_boxes_v.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
+                                              vp, vp, vp, u32, u64, u32]
+        L.zcg_store_write_boxes_v.restype = ctypes.c_int
         _lib = L
         return L
 

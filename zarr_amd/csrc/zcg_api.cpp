@@ -597,8 +597,9 @@ int zcg_write_region(zcg_ctx* ctx, const zcg_region* r, void* const* d_chunk_tab
     return region_call(ctx, r, (const void* const*)d_chunk_table, (void*)d_in, stream, 1);
 }
 
-uint64_t zcg_regions_grid(const zcg_region* r, const uint64_t* offsets, uint32_t n_boxes, uint64_t* lo,
-                          uint64_t* n) {
+// The union of the boxes' grid ranges; `shapes` NULL: every box has r->bbox_shape.
+static uint64_t regions_grid(const zcg_region* r, const uint64_t* offsets, const uint64_t* shapes, uint32_t n_boxes,
+                             uint64_t* lo, uint64_t* n) {
     if (!r || r->ndim < 1 || r->ndim > ZCG_MAX_DIMS) return 0;
     const uint32_t nd = r->ndim;
     uint64_t ulo[ZCG_MAX_DIMS] = {0}, uhi[ZCG_MAX_DIMS] = {0};
@@ -606,7 +607,10 @@ uint64_t zcg_regions_grid(const zcg_region* r, const uint64_t* offsets, uint32_t
     zcg_region one = *r;
     for (uint32_t b = 0; b < n_boxes && offsets; b++) {
         uint64_t blo[ZCG_MAX_DIMS], bn[ZCG_MAX_DIMS];
-        for (uint32_t d = 0; d < nd; d++) one.bbox_offset[d] = offsets[(size_t)b * nd + d];
+        for (uint32_t d = 0; d < nd; d++) {
+            one.bbox_offset[d] = offsets[(size_t)b * nd + d];
+            if (shapes) one.bbox_shape[d] = shapes[(size_t)b * nd + d];
+        }
         if (zcg_region_grid(&one, blo, bn) == 0) continue;  // visits no chunk
         for (uint32_t d = 0; d < nd; d++) {
             ulo[d] = any ? std::min(ulo[d], blo[d]) : blo[d];
@@ -621,6 +625,16 @@ uint64_t zcg_regions_grid(const zcg_region* r, const uint64_t* offsets, uint32_t
         cnt *= uhi[d] - ulo[d];
     }
     return cnt;
+}
+
+uint64_t zcg_regions_grid(const zcg_region* r, const uint64_t* offsets, uint32_t n_boxes, uint64_t* lo,
+                          uint64_t* n) {
+    return regions_grid(r, offsets, nullptr, n_boxes, lo, n);
+}
+
+uint64_t zcg_regions_v_grid(const zcg_region* r, const uint64_t* offsets, const uint64_t* shapes, uint32_t n_boxes,
+                            uint64_t* lo, uint64_t* n) {
+    return regions_grid(r, offsets, shapes, shapes ? n_boxes : 0, lo, n);
 }
 
 static int regions_call(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
@@ -666,6 +680,62 @@ int zcg_write_regions(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_l
                       void* stream) {
     return regions_call(ctx, r, table_lo, table_n, (const void* const*)d_chunk_table, d_boxes, n_boxes, d_status,
                         stream, 1);
+}
+
+uint64_t zcg_regions_v_scratch_bytes(uint32_t n_boxes) { return (regions_v_prefix_bytes(n_boxes) + 255) & ~255ull; }
+
+static int regions_v_call(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+                          const void* const* d_chunk_table, const zcg_vbox* d_boxes, uint32_t n_boxes,
+                          void* d_scratch, int32_t* d_status, void* stream, uint32_t dir) {
+    if (n_boxes == 0) return region_head(ctx, r);
+    RegionWalk w;  // w.bs, w.total: the bound
+    uint64_t entries;
+    const int rc = region_walk(ctx, r, nullptr, table_n,
+                               "regions_v: largest box extent + chunk extent along a dimension must stay below "
+                               "2^32 elements",
+                               &w, &entries);
+    if (rc != ZCG_OK) return rc;
+    if (dir) w.fill = 0;
+    BoxTable bt{};
+    bt.nboxes = n_boxes;
+    uint64_t total = 1;  // every extent is below 2^32: saturate at 2^63
+    for (uint32_t k = 0; k < w.nd; k++) {
+        const uint32_t d = region_dim(r, k);
+        bt.dim[k] = d;
+        bt.as[k] = r->array_shape[d];
+        bt.tlo[k] = table_lo ? table_lo[d] : 0;
+        bt.tn[k] = table_n ? table_n[d] : 0;
+        w.ostr[k] = 0;
+        total = w.bs[k] && total > (1ull << 63) / w.bs[k] ? 1ull << 63 : total * w.bs[k];
+    }
+    w.total = total;
+    if (!d_boxes || !d_status || !d_scratch || ((uintptr_t)d_scratch & 7) || (entries && !d_chunk_table))
+        return ZCG_ERR_INVALID_INPUT;
+    // zcg_read_regions' limit, on the bound: it keeps a box's element count and
+    // the 64-bit prefix sum of all boxes' work units from overflowing
+    if (total > (1ull << 62) / n_boxes) {
+        ctx->err = "regions_v: n_boxes x the bound's elements must stay below 2^62";
+        return ZCG_ERR_UNSUPPORTED;
+    }
+    (void)hipSetDevice(ctx->device);
+    const hipError_t e =
+        launch_regions_v(w, bt, d_chunk_table, d_boxes, d_scratch, d_status, dir, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, e, "regions_v launch");
+    return ZCG_OK;
+}
+
+int zcg_read_regions_v(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+                       const void* const* d_chunk_table, const zcg_vbox* d_boxes, uint32_t n_boxes, void* d_scratch,
+                       int32_t* d_status, void* stream) {
+    return regions_v_call(ctx, r, table_lo, table_n, d_chunk_table, d_boxes, n_boxes, d_scratch, d_status, stream,
+                          0);
+}
+
+int zcg_write_regions_v(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+                        void* const* d_chunk_table, const zcg_vbox* d_boxes, uint32_t n_boxes, void* d_scratch,
+                        int32_t* d_status, void* stream) {
+    return regions_v_call(ctx, r, table_lo, table_n, (const void* const*)d_chunk_table, d_boxes, n_boxes, d_scratch,
+                          d_status, stream, 1);
 }
 
 }  // extern "C"

@@ -12,6 +12,11 @@
 // ones prefilled), the boxes are scattered in the waves of zcg_regions_waves
 // (zcg_write_regions per wave, so a later box wins), and every chunk of the
 // group is encoded and written once (zcg_store_write_chunks_device).
+//
+// The _v calls take a shape per box; they share the planner and the two
+// drivers with the one-shape calls, which pass one shape for all boxes and
+// keep the one-shape kernels (zcg_read_regions / zcg_write_regions); boxes of
+// differing shapes go through zcg_read_regions_v / zcg_write_regions_v.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -70,12 +75,32 @@ int fail_hip(zcg_ctx* ctx, hipError_t e, const char* what) {
 struct Plan {
     zcg_region r;
     uint32_t nd = 0, es = 0;
-    uint64_t D = 0, box_elems = 1;      // bytes of a decoded chunk; elements of a box
+    uint64_t D = 0;                     // bytes of a decoded chunk
+    bool varied = false;                // a shape per box (the _v calls); r.bbox_shape is then their bound
+    const uint64_t* shapes = nullptr;   // box b's shape: shapes + b * sstep
+    const int64_t* strides = nullptr;   // varied, device views: box b's strides, strides + b * nd; NULL: dense
+    size_t sstep = 0;
+    std::vector<uint64_t> at;           // byte offset of box b among the boxes back to back, dense (n_boxes + 1)
     uint64_t gstr[ZCG_MAX_DIMS];        // linear chunk keys over the array's grid
     bool nothing = false;               // n_boxes == 0: the call is done
     std::vector<Group> groups;
     std::vector<uint64_t> glo, gn, gentries;  // per group: table range (ZCG_MAX_DIMS each), entries
 
+    const uint64_t* shape_of(uint32_t b) const { return shapes + (size_t)b * sstep; }
+    uint64_t box_bytes(uint32_t b) const { return at[b + 1] - at[b]; }
+    // varied shapes: box b's view strides per array dim, the caller's or dense in the chunk memory order
+    void strides_of(uint32_t b, int64_t* out) const {
+        if (strides) {
+            for (uint32_t d = 0; d < nd; d++) out[d] = strides[(size_t)b * nd + d];
+            return;
+        }
+        int64_t acc = 1;
+        for (uint32_t k = 0; k < nd; k++) {
+            const uint32_t d = r.chunk_order == 1 ? k : nd - 1 - k;
+            out[d] = acc;
+            acc *= (int64_t)std::max<uint64_t>(shape_of(b)[d], 1);
+        }
+    }
     void key_pos(uint64_t key, uint64_t* pos) const {
         for (uint32_t d = 0; d < nd; d++) { pos[d] = key / gstr[d]; key -= pos[d] * gstr[d]; }
     }
@@ -85,12 +110,17 @@ struct Plan {
 // panics at storage.rs:217) and the grouping under the slot budget.  `what`
 // prefixes the messages.  host == true: boxes are host buffers, each dense in
 // the chunk memory order; else device views with the caller's strides.
+// varied == false: every box has the shape box_shape (ndim) and, as a device
+// view, the strides `strides` (ndim); true: box_shape and strides hold
+// n_boxes * ndim entries, box-major, and NULL strides mean dense views.
 // cover == true (write): Group::read_first is filled in.
 int plan_boxes(zcg_ctx* ctx, const std::string& what, const zcg_array_meta* meta, const char* root, const char* path,
-               const uint64_t* box_shape, const int64_t* strides, uint32_t fill_missing, const uint64_t* offsets,
-               const void* const* bufs, uint32_t n_boxes, uint64_t slot_budget_bytes, bool host, bool cover,
-               Plan& P) {
-    if (!ctx || !meta || !root || !path || !box_shape || (!host && !strides)) return ZCG_ERR_INVALID_INPUT;
+               const uint64_t* box_shape, const int64_t* strides, bool varied, uint32_t fill_missing,
+               const uint64_t* offsets, const void* const* bufs, uint32_t n_boxes, uint64_t slot_budget_bytes,
+               bool host, bool cover, Plan& P) {
+    if (!ctx || !meta || !root || !path || (!box_shape && !(varied && n_boxes == 0)) ||
+        (!host && !strides && !varied))
+        return ZCG_ERR_INVALID_INPUT;
     if (n_boxes && (!offsets || !bufs)) return ZCG_ERR_INVALID_INPUT;
     if (meta->ndim != meta->chunk_ndim) {
         ctx_set_error(ctx, what + ": shape and chunk_shape differ in their number of dimensions");
@@ -113,7 +143,10 @@ int plan_boxes(zcg_ctx* ctx, const std::string& what, const zcg_array_meta* meta
 
     zcg_region& r = P.r;
     uint64_t* gstr = P.gstr;
-    uint64_t& box_elems = P.box_elems;
+    P.varied = varied;
+    P.shapes = box_shape;
+    P.sstep = varied ? nd : 0;
+    P.strides = varied && !host ? strides : nullptr;
     memset(&r, 0, sizeof r);
     r.ndim = nd;
     r.elem_size = es;
@@ -121,22 +154,34 @@ int plan_boxes(zcg_ctx* ctx, const std::string& what, const zcg_array_meta* meta
     r.fill_missing = host ? 1u : (fill_missing ? 1u : 0u);
     r.fill_value = meta->has_fill_value ? meta->fill_value : 0;
     uint64_t extent[ZCG_MAX_DIMS];
-    box_elems = 1;
     for (uint32_t d = 0; d < nd; d++) {
         if (meta->chunk_shape[d] == 0) return ZCG_ERR_INVALID_INPUT;
         r.array_shape[d] = meta->shape[d];
         r.chunk_shape[d] = meta->chunk_shape[d];
-        r.bbox_shape[d] = box_shape[d];
         extent[d] = u64_ceil_div(meta->shape[d], meta->chunk_shape[d]);
-        box_elems *= box_shape[d];
+    }
+    // the boxes back to back, and the bound of their extents
+    P.at.assign((size_t)n_boxes + 1, 0);
+    for (uint32_t b = 0; b < n_boxes; b++) {
+        uint64_t elems = 1;
+        for (uint32_t d = 0; d < nd; d++) {
+            const uint64_t s = P.shape_of(b)[d];
+            r.bbox_shape[d] = std::max(r.bbox_shape[d], s);
+            elems = s && elems > (1ull << 62) / s ? 1ull << 62 : elems * s;
+        }
+        if (elems >= (1ull << 62) / es || P.at[b] + elems * es < P.at[b]) {
+            ctx_set_error(ctx, what + ": the boxes hold more than 2^62 bytes");
+            return ZCG_ERR_UNSUPPORTED;
+        }
+        P.at[b + 1] = P.at[b] + elems * es;
     }
     {   // dense host layout in the chunk memory order; linear chunk keys over the grid
         int64_t acc = 1;
         uint64_t g = 1;
         for (uint32_t k = 0; k < nd; k++) {
             const uint32_t d = meta->chunk_order == 1 ? k : nd - 1 - k;
-            r.out_strides[d] = host ? acc : strides[d];
-            acc *= (int64_t)std::max<uint64_t>(box_shape[d], 1);
+            r.out_strides[d] = varied ? 0 : host ? acc : strides[d];
+            acc *= (int64_t)std::max<uint64_t>(r.bbox_shape[d], 1);
         }
         for (int d = (int)nd - 1; d >= 0; d--) {
             gstr[d] = g;
@@ -171,8 +216,12 @@ int plan_boxes(zcg_ctx* ctx, const std::string& what, const zcg_array_meta* meta
         };
         for (uint32_t b = 0; b < n_boxes; b++) {
             uint64_t lo[ZCG_MAX_DIMS], n[ZCG_MAX_DIMS], pos[ZCG_MAX_DIMS];
-            for (uint32_t d = 0; d < nd; d++) r.bbox_offset[d] = offsets[(size_t)b * nd + d];
-            const uint64_t cnt = zcg_region_grid(&r, lo, n);
+            zcg_region rb = r;  // this box alone
+            for (uint32_t d = 0; d < nd; d++) {
+                rb.bbox_offset[d] = offsets[(size_t)b * nd + d];
+                rb.bbox_shape[d] = P.shape_of(b)[d];
+            }
+            const uint64_t cnt = zcg_region_grid(&rb, lo, n);
             for (uint32_t d = 0; cnt && d < nd; d++)
                 if (lo[d] + n[d] > extent[d]) {
                     for (uint32_t k = 0; k < nd; k++) pos[k] = lo[k] + n[k] - 1;
@@ -194,7 +243,7 @@ int plan_boxes(zcg_ctx* ctx, const std::string& what, const zcg_array_meta* meta
                         key += c * gstr[d];
                         rem /= n[d];
                         if (cover) {  // write_bb == nom_chunk_bb (ndarray.rs:327), per dimension
-                            const uint64_t cs = r.chunk_shape[d], o = r.bbox_offset[d], o1 = o + r.bbox_shape[d];
+                            const uint64_t cs = rb.chunk_shape[d], o = rb.bbox_offset[d], o1 = o + rb.bbox_shape[d];
                             part |= c * cs < o || c * cs + cs > (o1 < o ? ~0ull : o1);
                         }
                     }
@@ -218,8 +267,11 @@ int plan_boxes(zcg_ctx* ctx, const std::string& what, const zcg_array_meta* meta
     P.gentries.resize(groups.size());
     for (size_t g = 0; g < groups.size(); g++) {
         const Group& G = groups[g];
-        P.gentries[g] = zcg_regions_grid(&r, offsets + (size_t)G.b0 * nd, G.b1 - G.b0, &P.glo[g * ZCG_MAX_DIMS],
-                                         &P.gn[g * ZCG_MAX_DIMS]);
+        P.gentries[g] =
+            varied ? zcg_regions_v_grid(&r, offsets + (size_t)G.b0 * nd, box_shape + (size_t)G.b0 * nd, G.b1 - G.b0,
+                                        &P.glo[g * ZCG_MAX_DIMS], &P.gn[g * ZCG_MAX_DIMS])
+                   : zcg_regions_grid(&r, offsets + (size_t)G.b0 * nd, G.b1 - G.b0, &P.glo[g * ZCG_MAX_DIMS],
+                                      &P.gn[g * ZCG_MAX_DIMS]);
         if (P.gentries[g] > BOXES_MAX_TABLE) {
             ctx_set_error(ctx, what + ": the boxes' union chunk table (" + std::to_string(P.gentries[g]) +
                                    " entries) exceeds 2^24; split the boxes over several calls");
@@ -282,27 +334,71 @@ int chunk_failed(zcg_ctx* ctx, const std::string& what, const Plan& P, uint64_t 
     return status;
 }
 
+// The records of boxes b0 .. b0 + nb as the region kernels take them: zcg_box
+// for one shape, zcg_vbox (shape and strides per box) for varied shapes.  Box
+// b's view is bufs[b], or, host == true, its place in the dense staging buffer.
+size_t record_bytes(const Plan& P) { return P.varied ? sizeof(zcg_vbox) : sizeof(zcg_box); }
+
+std::vector<uint8_t> box_records(const Plan& P, const uint64_t* offsets, const void* const* bufs, void* staging,
+                                 uint32_t b0, uint32_t nb, bool host) {
+    std::vector<uint8_t> recs((size_t)nb * record_bytes(P), 0);
+    for (uint32_t i = 0; i < nb; i++) {
+        const uint32_t b = b0 + i;
+        void* view = host ? (void*)((uint8_t*)staging + (P.at[b] - P.at[b0])) : (void*)bufs[b];
+        if (P.varied) {
+            zcg_vbox& x = ((zcg_vbox*)recs.data())[i];
+            for (uint32_t d = 0; d < P.nd; d++) {
+                x.offset[d] = offsets[(size_t)b * P.nd + d];
+                x.shape[d] = P.shape_of(b)[d];
+            }
+            P.strides_of(b, x.strides);
+            x.base = view;
+        } else {
+            zcg_box& x = ((zcg_box*)recs.data())[i];
+            for (uint32_t d = 0; d < P.nd; d++) x.offset[d] = offsets[(size_t)b * P.nd + d];
+            x.out = view;
+        }
+    }
+    return recs;
+}
+
+// One region call for records first .. first + count of a group (dir 0:
+// assemble, 1: scatter): the one-shape kernels, or the _v kernels for varied
+// shapes (d_scratch: zcg_regions_v_scratch_bytes(count) bytes).
+int regions_launch(zcg_ctx* ctx, const Plan& P, const uint64_t* lo, const uint64_t* n, void* d_table, void* d_recs,
+                   uint32_t first, uint32_t count, void* d_scratch, int32_t* d_status, hipStream_t s, uint32_t dir) {
+    if (P.varied) {
+        const zcg_vbox* bx = (const zcg_vbox*)d_recs + first;
+        return dir ? zcg_write_regions_v(ctx, &P.r, lo, n, (void* const*)d_table, bx, count, d_scratch,
+                                         d_status + first, (void*)s)
+                   : zcg_read_regions_v(ctx, &P.r, lo, n, (const void* const*)d_table, bx, count, d_scratch,
+                                        d_status + first, (void*)s);
+    }
+    const zcg_box* bx = (const zcg_box*)d_recs + first;
+    return dir ? zcg_write_regions(ctx, &P.r, lo, n, (void* const*)d_table, bx, count, d_status + first, (void*)s)
+               : zcg_read_regions(ctx, &P.r, lo, n, (const void* const*)d_table, bx, count, d_status + first,
+                                  (void*)s);
+}
+
 // host == true: outs are host buffers, each box dense in the chunk memory
-// order with fill (read_ndarray); else device views with the caller's strides
+// order with fill (read_ndarray); else device views with the caller's strides.
+// varied: plan_boxes' (a shape, and as a device view strides, per box).
 int read_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
-               const uint64_t* box_shape, const int64_t* out_strides, uint32_t fill_missing,
+               const uint64_t* box_shape, const int64_t* out_strides, bool varied, uint32_t fill_missing,
                const uint64_t* offsets, void* const* outs, uint32_t n_boxes, uint64_t slot_budget_bytes,
                uint32_t io_threads, bool host) {
     const std::string what = "read_boxes";
     Plan P;
     // 1. before any file is read
-    const int prc = plan_boxes(ctx, what, meta, root, path, box_shape, out_strides, fill_missing, offsets, outs,
-                               n_boxes, slot_budget_bytes, host, false, P);
+    const int prc = plan_boxes(ctx, what, meta, root, path, box_shape, out_strides, varied, fill_missing, offsets,
+                               outs, n_boxes, slot_budget_bytes, host, false, P);
     if (prc != ZCG_OK) return prc;
-    if (P.nothing || P.box_elems == 0) return ZCG_OK;
-    const zcg_region& r = P.r;
-    const uint32_t nd = P.nd, es = P.es;
+    if (P.nothing || P.at[n_boxes] == 0) return ZCG_OK;
 
     (void)hipSetDevice(ctx_device(ctx));
     Stream st;
     hipError_t e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
     if (e != hipSuccess) return fail_hip(ctx, e, "read_boxes stream");
-    const uint64_t box_bytes = P.box_elems * es;
 
     // 2. per group: read + decode its chunks once, build the table, one launch
     for (size_t g = 0; g < P.groups.size(); g++) {
@@ -327,29 +423,25 @@ int read_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const
                 table[S.tidx[i]] = S.ptrs[i];
             }
         }
-        // device: [table entries][boxes nb][status nb]
+        // device: [table entries][boxes nb][status nb][scratch of the _v kernels]
+        const uint64_t group_bytes = P.at[G.b1] - P.at[G.b0];
         const size_t o_box = (entries * sizeof(void*) + 255) & ~(size_t)255;
-        const size_t o_st = (o_box + (size_t)nb * sizeof(zcg_box) + 255) & ~(size_t)255;
-        if ((e = meta_dev.alloc(o_st + (size_t)nb * sizeof(int32_t))) != hipSuccess)
+        const size_t o_st = (o_box + (size_t)nb * record_bytes(P) + 255) & ~(size_t)255;
+        const size_t o_scr = (o_st + (size_t)nb * sizeof(int32_t) + 255) & ~(size_t)255;
+        if ((e = meta_dev.alloc(o_scr + (P.varied ? zcg_regions_v_scratch_bytes(nb) : 0))) != hipSuccess)
             return fail_hip(ctx, e, "read_boxes table");
-        if (host && (e = staging.alloc((size_t)nb * box_bytes)) != hipSuccess)
+        if (host && (e = staging.alloc(group_bytes)) != hipSuccess)
             return fail_hip(ctx, e, "read_boxes staging");
-        std::vector<zcg_box> boxes(nb);
-        for (uint32_t i = 0; i < nb; i++) {
-            memset(&boxes[i], 0, sizeof(zcg_box));
-            for (uint32_t d = 0; d < nd; d++) boxes[i].offset[d] = offsets[(size_t)(G.b0 + i) * nd + d];
-            boxes[i].out = host ? (void*)((uint8_t*)staging.p + (size_t)i * box_bytes) : outs[G.b0 + i];
-        }
+        const std::vector<uint8_t> boxes = box_records(P, offsets, outs, staging.p, G.b0, nb, host);
         uint8_t* db = (uint8_t*)meta_dev.p;
         if (entries) e = hipMemcpyAsync(db, table.data(), entries * sizeof(void*), hipMemcpyHostToDevice, st.s);
         if (e == hipSuccess)
-            e = hipMemcpyAsync(db + o_box, boxes.data(), (size_t)nb * sizeof(zcg_box), hipMemcpyHostToDevice, st.s);
+            e = hipMemcpyAsync(db + o_box, boxes.data(), boxes.size(), hipMemcpyHostToDevice, st.s);
         if (e != hipSuccess) {
             (void)hipStreamSynchronize(st.s);  // the host vectors of an enqueued copy end with this scope
             return fail_hip(ctx, e, "read_boxes H2D");
         }
-        const int rc = zcg_read_regions(ctx, &r, lo, n, (const void* const*)db, (const zcg_box*)(db + o_box), nb,
-                                        (int32_t*)(db + o_st), (void*)st.s);
+        const int rc = regions_launch(ctx, P, lo, n, db, db + o_box, 0, nb, db + o_scr, (int32_t*)(db + o_st), st.s, 0);
         if (rc != ZCG_OK) {
             (void)hipStreamSynchronize(st.s);
             return rc;
@@ -362,13 +454,13 @@ int read_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const
             // consecutive in memory, else through a bounce buffer
             bool dense = true;
             for (uint32_t i = 1; i < nb && dense; i++)
-                dense = (uint8_t*)outs[G.b0 + i] == (uint8_t*)outs[G.b0] + (size_t)i * box_bytes;
+                dense = (uint8_t*)outs[G.b0 + i] == (uint8_t*)outs[G.b0] + (P.at[G.b0 + i] - P.at[G.b0]);
             uint8_t* dst = (uint8_t*)outs[G.b0];
             if (!dense) {
-                bounce.resize((size_t)nb * box_bytes);
+                bounce.resize(group_bytes);
                 dst = bounce.data();
             }
-            e = hipMemcpyAsync(dst, staging.p, (size_t)nb * box_bytes, hipMemcpyDeviceToHost, st.s);
+            if (group_bytes) e = hipMemcpyAsync(dst, staging.p, group_bytes, hipMemcpyDeviceToHost, st.s);
         }
         if (e == hipSuccess) e = hipStreamSynchronize(st.s);
         else (void)hipStreamSynchronize(st.s);
@@ -379,7 +471,9 @@ int read_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const
                 return bst[i];
             }
         if (!bounce.empty())
-            for (uint32_t i = 0; i < nb; i++) memcpy(outs[G.b0 + i], bounce.data() + (size_t)i * box_bytes, box_bytes);
+            for (uint32_t i = 0; i < nb; i++)
+                if (P.box_bytes(G.b0 + i))
+                    memcpy(outs[G.b0 + i], bounce.data() + (P.at[G.b0 + i] - P.at[G.b0]), P.box_bytes(G.b0 + i));
     }
     return ZCG_OK;
 }
@@ -387,18 +481,19 @@ int read_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const
 // write_ndarray for the boxes in order (ndarray.rs:276-385).  Per group: the
 // slots of chunks whose first visiting box is partial are read (or, absent,
 // prefilled); the boxes are scattered wave by wave; every slot is encoded and
-// written.  host == true: ins are host buffers, dense in the chunk memory order.
+// written.  host == true: ins are host buffers, dense in the chunk memory
+// order.  varied: plan_boxes'.
 int write_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
-                const uint64_t* box_shape, const int64_t* in_strides, const uint64_t* offsets,
+                const uint64_t* box_shape, const int64_t* in_strides, bool varied, const uint64_t* offsets,
                 const void* const* ins, uint32_t n_boxes, uint64_t slot_budget_bytes, uint32_t io_threads,
                 bool host) {
     const std::string what = "write_boxes";
     Plan P;
     // 1. before any file is read or written
-    const int prc = plan_boxes(ctx, what, meta, root, path, box_shape, in_strides, 0, offsets, ins, n_boxes,
+    const int prc = plan_boxes(ctx, what, meta, root, path, box_shape, in_strides, varied, 0, offsets, ins, n_boxes,
                                slot_budget_bytes, host, true, P);
     if (prc != ZCG_OK) return prc;
-    if (P.nothing || P.box_elems == 0) return ZCG_OK;
+    if (P.nothing || P.at[n_boxes] == 0) return ZCG_OK;
     const zcg_region& r = P.r;
     const uint32_t nd = P.nd, es = P.es;
     const uint64_t fillv = meta->has_fill_value ? meta->fill_value : 0;
@@ -408,7 +503,6 @@ int write_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, cons
     Stream st;
     hipError_t e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
     if (e != hipSuccess) return fail_hip(ctx, e, "write_boxes stream");
-    const uint64_t box_bytes = P.box_elems * es;
     std::vector<uint32_t> wave_of;
 
     for (size_t g = 0; g < P.groups.size(); g++) {
@@ -447,27 +541,25 @@ int write_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, cons
             }
         }
 
-        // 3. device: [table entries][boxes nb][status nb][absent slots]; every visited chunk has a slot
+        // 3. device: [table entries][boxes nb][status nb][absent slots][scratch of the _v kernels]; every
+        // visited chunk has a slot
         std::vector<void*> table(entries, nullptr);
         for (uint32_t i = 0; i < m; i++) table[S.tidx[i]] = S.ptrs[i];
+        const uint64_t group_bytes = P.at[G.b1] - P.at[G.b0];
         const size_t o_box = (entries * sizeof(void*) + 255) & ~(size_t)255;
-        const size_t o_st = (o_box + (size_t)nb * sizeof(zcg_box) + 255) & ~(size_t)255;
+        const size_t o_st = (o_box + (size_t)nb * record_bytes(P) + 255) & ~(size_t)255;
         const size_t o_abs = (o_st + (size_t)nb * sizeof(int32_t) + 255) & ~(size_t)255;
-        if ((e = meta_dev.alloc(o_abs + absent.size() * sizeof(void*))) != hipSuccess)
+        const size_t o_scr = (o_abs + absent.size() * sizeof(void*) + 255) & ~(size_t)255;
+        if ((e = meta_dev.alloc(o_scr + (P.varied ? zcg_regions_v_scratch_bytes(nb) : 0))) != hipSuccess)
             return fail_hip(ctx, e, "write_boxes table");
-        if (host && (e = staging.alloc((size_t)nb * box_bytes)) != hipSuccess)
+        if (host && (e = staging.alloc(group_bytes)) != hipSuccess)
             return fail_hip(ctx, e, "write_boxes staging");
-        std::vector<zcg_box> boxes(nb);
-        for (uint32_t i = 0; i < nb; i++) {
-            memset(&boxes[i], 0, sizeof(zcg_box));
-            for (uint32_t d = 0; d < nd; d++) boxes[i].offset[d] = offsets[(size_t)(G.b0 + i) * nd + d];
-            boxes[i].out = host ? (void*)((uint8_t*)staging.p + (size_t)i * box_bytes) : (void*)ins[G.b0 + i];
-        }
+        const std::vector<uint8_t> boxes = box_records(P, offsets, ins, staging.p, G.b0, nb, host);
         uint8_t* db = (uint8_t*)meta_dev.p;
         std::vector<uint8_t> bounce;
         e = hipMemcpyAsync(db, table.data(), entries * sizeof(void*), hipMemcpyHostToDevice, st.s);
         if (e == hipSuccess)
-            e = hipMemcpyAsync(db + o_box, boxes.data(), (size_t)nb * sizeof(zcg_box), hipMemcpyHostToDevice, st.s);
+            e = hipMemcpyAsync(db + o_box, boxes.data(), boxes.size(), hipMemcpyHostToDevice, st.s);
         if (e == hipSuccess && !absent.empty())
             e = hipMemcpyAsync(db + o_abs, absent.data(), absent.size() * sizeof(void*), hipMemcpyHostToDevice, st.s);
         if (e == hipSuccess && host) {
@@ -475,14 +567,16 @@ int write_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, cons
             // consecutive in memory, else through a bounce buffer
             bool dense = true;
             for (uint32_t i = 1; i < nb && dense; i++)
-                dense = (const uint8_t*)ins[G.b0 + i] == (const uint8_t*)ins[G.b0] + (size_t)i * box_bytes;
+                dense = (const uint8_t*)ins[G.b0 + i] == (const uint8_t*)ins[G.b0] + (P.at[G.b0 + i] - P.at[G.b0]);
             const uint8_t* src = (const uint8_t*)ins[G.b0];
             if (!dense) {
-                bounce.resize((size_t)nb * box_bytes);
-                for (uint32_t i = 0; i < nb; i++) memcpy(bounce.data() + (size_t)i * box_bytes, ins[G.b0 + i], box_bytes);
+                bounce.resize(group_bytes);
+                for (uint32_t i = 0; i < nb; i++)
+                    if (P.box_bytes(G.b0 + i))
+                        memcpy(bounce.data() + (P.at[G.b0 + i] - P.at[G.b0]), ins[G.b0 + i], P.box_bytes(G.b0 + i));
                 src = bounce.data();
             }
-            e = hipMemcpyAsync(staging.p, src, (size_t)nb * box_bytes, hipMemcpyHostToDevice, st.s);
+            if (group_bytes) e = hipMemcpyAsync(staging.p, src, group_bytes, hipMemcpyHostToDevice, st.s);
         }
         if (e == hipSuccess)
             e = launch_slot_fill((void* const*)(db + o_abs), (uint32_t)absent.size(), P.D, es, fillv, st.s);
@@ -493,12 +587,14 @@ int write_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, cons
 
         // 4. the scatter, wave by wave: a later box wins what it shares with an earlier one
         wave_of.resize(nb);
-        zcg_regions_waves(&r, offsets + (size_t)G.b0 * nd, nb, wave_of.data());
+        if (P.varied)
+            zcg_regions_v_waves(&r, offsets + (size_t)G.b0 * nd, box_shape + (size_t)G.b0 * nd, nb, wave_of.data());
+        else
+            zcg_regions_waves(&r, offsets + (size_t)G.b0 * nd, nb, wave_of.data());
         for (uint32_t b0 = 0; b0 < nb;) {
             uint32_t b1 = b0 + 1;
             while (b1 < nb && wave_of[b1] == wave_of[b0]) b1++;
-            rc = zcg_write_regions(ctx, &r, lo, n, (void* const*)db, (const zcg_box*)(db + o_box) + b0, b1 - b0,
-                                   (int32_t*)(db + o_st) + b0, (void*)st.s);
+            rc = regions_launch(ctx, P, lo, n, db, db + o_box, b0, b1 - b0, db + o_scr, (int32_t*)(db + o_st), st.s, 1);
             if (rc != ZCG_OK) {
                 (void)hipStreamSynchronize(st.s);
                 return rc;
@@ -532,31 +628,28 @@ struct CellRange {
     uint64_t lo, hi;
 };
 
-}  // namespace
-
-extern "C" uint32_t zcg_regions_waves(const zcg_region* r, const uint64_t* offsets, uint32_t n_boxes,
-                                      uint32_t* wave_of) {
-    if (!r || !offsets || !wave_of || n_boxes == 0) return 0;
+// zcg_regions_waves and zcg_regions_v_waves: box b's shape is shapes + b * sstep
+// (sstep 0: one shape for all).
+uint32_t regions_waves(const zcg_region* r, const uint64_t* offsets, const uint64_t* shapes, size_t sstep,
+                       uint32_t n_boxes, uint32_t* wave_of) {
+    if (!r || !offsets || !shapes || !wave_of || n_boxes == 0) return 0;
     const uint32_t nd = r->ndim;
     if (nd < 1 || nd > ZCG_MAX_DIMS) return 0;
-    bool empty = false;
-    for (uint32_t d = 0; d < nd; d++) empty |= r->bbox_shape[d] == 0;
-    if (empty) {
-        for (uint32_t b = 0; b < n_boxes; b++) wave_of[b] = 0;
-        return 1;
-    }
     // Cells: per dimension the smallest multiple of the chunk extent that holds
-    // the box extent, so a box lies in at most two cells per dimension and two
-    // boxes that intersect share a cell.  A box is compared with the boxes of
-    // the current wave that are registered in one of its cells.
+    // the largest box extent (r->bbox_shape, unless a box exceeds it), so a box
+    // lies in at most two cells per dimension and two boxes that intersect
+    // share a cell.  A box is compared with the boxes of the current wave that
+    // are registered in one of its cells.
     uint64_t cell[ZCG_MAX_DIMS];
     for (uint32_t d = 0; d < nd; d++) {
-        const uint64_t cs = r->chunk_shape[d] ? r->chunk_shape[d] : 1, bs = r->bbox_shape[d];
-        const uint64_t k = bs / cs + (bs % cs ? 1 : 0);
+        uint64_t bs = sstep ? r->bbox_shape[d] : shapes[d];
+        for (uint32_t b = 0; sstep && b < n_boxes; b++) bs = std::max(bs, shapes[(size_t)b * sstep + d]);
+        const uint64_t cs = r->chunk_shape[d] ? r->chunk_shape[d] : 1;
+        const uint64_t k = std::max<uint64_t>(bs / cs + (bs % cs ? 1 : 0), 1);
         cell[d] = k > (~0ull) / cs ? ~0ull : k * cs;
     }
-    auto end_of = [&](uint64_t o, uint32_t d) {
-        const uint64_t e = o + r->bbox_shape[d];
+    auto end_of = [&](uint32_t b, uint32_t d) {
+        const uint64_t o = offsets[(size_t)b * nd + d], e = o + shapes[(size_t)b * sstep + d];
         return e < o ? ~0ull : e;  // saturating
     };
     std::unordered_map<uint64_t, std::vector<uint32_t>> cells;  // hash of the cell position -> boxes
@@ -567,7 +660,7 @@ extern "C" uint32_t zcg_regions_waves(const zcg_region* r, const uint64_t* offse
         bool has = true;  // false: the saturated extent is empty, the box intersects nothing
         uint32_t ncell = 1;
         for (uint32_t d = 0; d < nd; d++) {
-            const uint64_t e = end_of(ob[d], d);
+            const uint64_t e = end_of(b, d);
             if (e <= ob[d]) { has = false; break; }
             cr[d] = CellRange{ob[d] / cell[d], (e - 1) / cell[d]};
             ncell *= (uint32_t)(cr[d].hi - cr[d].lo + 1);
@@ -596,7 +689,7 @@ extern "C" uint32_t zcg_regions_waves(const zcg_region* r, const uint64_t* offse
                 const uint64_t* oa = offsets + (size_t)a * nd;
                 bool meet = true;
                 for (uint32_t d = 0; d < nd && meet; d++)
-                    meet = std::max(oa[d], ob[d]) < std::min(end_of(oa[d], d), end_of(ob[d], d));
+                    meet = std::max(oa[d], ob[d]) < std::min(end_of(a, d), end_of(b, d));
                 if (meet) { hit = true; break; }
             }
         }
@@ -610,18 +703,30 @@ extern "C" uint32_t zcg_regions_waves(const zcg_region* r, const uint64_t* offse
     return wave + 1;
 }
 
+}  // namespace
+
+extern "C" uint32_t zcg_regions_waves(const zcg_region* r, const uint64_t* offsets, uint32_t n_boxes,
+                                      uint32_t* wave_of) {
+    return regions_waves(r, offsets, r ? r->bbox_shape : nullptr, 0, n_boxes, wave_of);
+}
+
+extern "C" uint32_t zcg_regions_v_waves(const zcg_region* r, const uint64_t* offsets, const uint64_t* shapes,
+                                        uint32_t n_boxes, uint32_t* wave_of) {
+    return regions_waves(r, offsets, shapes, r ? r->ndim : 0, n_boxes, wave_of);
+}
+
 extern "C" int zcg_store_write_boxes_device(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root,
                                             const char* path, const uint64_t* box_shape, const int64_t* in_strides,
                                             const uint64_t* offsets, const void* const* d_ins, uint32_t n_boxes,
                                             uint64_t slot_budget_bytes, uint32_t io_threads) {
-    return write_boxes(ctx, meta, root, path, box_shape, in_strides, offsets, d_ins, n_boxes, slot_budget_bytes,
-                       io_threads, false);
+    return write_boxes(ctx, meta, root, path, box_shape, in_strides, false, offsets, d_ins, n_boxes,
+                       slot_budget_bytes, io_threads, false);
 }
 
 extern "C" int zcg_store_write_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
                                      const uint64_t* box_shape, const uint64_t* offsets, const void* const* ins,
                                      uint32_t n_boxes, uint64_t slot_budget_bytes, uint32_t io_threads) {
-    return write_boxes(ctx, meta, root, path, box_shape, nullptr, offsets, ins, n_boxes, slot_budget_bytes,
+    return write_boxes(ctx, meta, root, path, box_shape, nullptr, false, offsets, ins, n_boxes, slot_budget_bytes,
                        io_threads, true);
 }
 
@@ -629,13 +734,45 @@ extern "C" int zcg_store_read_boxes_device(zcg_ctx* ctx, const zcg_array_meta* m
                                            const char* path, const uint64_t* box_shape, const int64_t* out_strides,
                                            uint32_t fill_missing, const uint64_t* offsets, void* const* d_outs,
                                            uint32_t n_boxes, uint64_t slot_budget_bytes, uint32_t io_threads) {
-    return read_boxes(ctx, meta, root, path, box_shape, out_strides, fill_missing, offsets, d_outs, n_boxes,
+    return read_boxes(ctx, meta, root, path, box_shape, out_strides, false, fill_missing, offsets, d_outs, n_boxes,
                       slot_budget_bytes, io_threads, false);
 }
 
 extern "C" int zcg_store_read_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
                                     const uint64_t* box_shape, const uint64_t* offsets, void* const* outs,
                                     uint32_t n_boxes, uint64_t slot_budget_bytes, uint32_t io_threads) {
-    return read_boxes(ctx, meta, root, path, box_shape, nullptr, 1, offsets, outs, n_boxes, slot_budget_bytes,
+    return read_boxes(ctx, meta, root, path, box_shape, nullptr, false, 1, offsets, outs, n_boxes, slot_budget_bytes,
                       io_threads, true);
+}
+
+extern "C" int zcg_store_read_boxes_v_device(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root,
+                                             const char* path, const uint64_t* box_shapes,
+                                             const int64_t* out_strides, uint32_t fill_missing,
+                                             const uint64_t* offsets, void* const* d_outs, uint32_t n_boxes,
+                                             uint64_t slot_budget_bytes, uint32_t io_threads) {
+    return read_boxes(ctx, meta, root, path, box_shapes, out_strides, true, fill_missing, offsets, d_outs, n_boxes,
+                      slot_budget_bytes, io_threads, false);
+}
+
+extern "C" int zcg_store_read_boxes_v(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                                      const uint64_t* box_shapes, const uint64_t* offsets, void* const* outs,
+                                      uint32_t n_boxes, uint64_t slot_budget_bytes, uint32_t io_threads) {
+    return read_boxes(ctx, meta, root, path, box_shapes, nullptr, true, 1, offsets, outs, n_boxes, slot_budget_bytes,
+                      io_threads, true);
+}
+
+extern "C" int zcg_store_write_boxes_v_device(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root,
+                                              const char* path, const uint64_t* box_shapes,
+                                              const int64_t* in_strides, const uint64_t* offsets,
+                                              const void* const* d_ins, uint32_t n_boxes,
+                                              uint64_t slot_budget_bytes, uint32_t io_threads) {
+    return write_boxes(ctx, meta, root, path, box_shapes, in_strides, true, offsets, d_ins, n_boxes,
+                       slot_budget_bytes, io_threads, false);
+}
+
+extern "C" int zcg_store_write_boxes_v(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                                       const uint64_t* box_shapes, const uint64_t* offsets, const void* const* ins,
+                                       uint32_t n_boxes, uint64_t slot_budget_bytes, uint32_t io_threads) {
+    return write_boxes(ctx, meta, root, path, box_shapes, nullptr, true, offsets, ins, n_boxes, slot_budget_bytes,
+                       io_threads, true);
 }

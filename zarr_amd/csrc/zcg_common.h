@@ -251,7 +251,10 @@ static __constant__ u32 g_crc32_table[256] = {
     0xb40bbe37u, 0xc30c8ea1u, 0x5a05df1bu, 0x2d02ef8du};
 
 // Region assembly arguments (zcg_region.hip, zcg_region_walk.h), built by
-// zcg_api.cpp.  RegionWalk: what every box of a launch shares.
+// zcg_api.cpp.  RegionWalk: what every box of a launch shares.  The kernels
+// for boxes of differing shapes (zcg_read_regions_v) get the bound of the
+// boxes' extents in bs / total, and hand the walk a register copy in which bs,
+// total and ostr are the box's own (vbox_terms, zcg_region_v.hip).
 struct RegionWalk {
     u32 nd, es, fill, V;       // dims, element bytes, fill flag, elements per thread (16/es)
     u64 total;                 // elements in one box
@@ -397,6 +400,13 @@ uint64_t xz_decode_ws_bytes(const zcg_array* a, uint32_t n);
 hipError_t launch_region(const RegionWalk& w, const BoxTerms& t, uint32_t dir, hipStream_t s);
 hipError_t launch_regions(const RegionWalk& w, const BoxTable& bt, const void* const* d_table,
                           const zcg_box* d_boxes, int32_t* d_status, uint32_t dir, hipStream_t s);
+// Boxes of differing shapes: w.bs is the bound of every box's extent, w.total
+// the bound's elements; w.ostr is unused (each zcg_vbox has its strides).
+// d_prefix: regions_v_prefix_bytes(nboxes) bytes of device scratch.
+uint64_t regions_v_prefix_bytes(uint32_t nboxes);
+hipError_t launch_regions_v(const RegionWalk& w, const BoxTable& bt, const void* const* d_table,
+                            const zcg_vbox* d_boxes, void* d_prefix, int32_t* d_status, uint32_t dir,
+                            hipStream_t s);
 // m device slots of D bytes (d_slots: DEVICE array of their bases, each a
 // multiple of `es`), filled with the element `fillv`
 hipError_t launch_slot_fill(void* const* d_slots, uint32_t m, uint64_t D, uint32_t es, uint64_t fillv,

@@ -5,7 +5,8 @@
 // many boxes of one common shape, each at its own offset and into its own
 // output view, from one shared chunk table (zcg_read_regions), or scattered
 // into it from its own input view (zcg_write_regions; the slot prefill of
-// chunks the store lacks is here too).
+// chunks the store lacks is here too).  Boxes that each have their own shape
+// and view (zcg_read_regions_v, zcg_write_regions_v) are zcg_region_v.hip's.
 //
 // Reference semantics kept: the chunks visited are bounded_coord_iter's grid
 // range (ndarray.rs:410-432); each visited chunk covers its full nominal

@@ -1,7 +1,9 @@
 // zcg_region_walk.h — the region assembly walk, written once for the four
 // kernels of zcg_region.hip (one box or many boxes per launch; a workgroup per
-// tile or a wave per row piece).  A kernel only decides where a box's terms
-// (BoxTerms) come from; what is done with them is here.
+// tile or a wave per row piece) and the kernel of zcg_region_v.hip (boxes of
+// differing shapes).  A kernel only decides where a box's terms (BoxTerms, and
+// for differing shapes the box's part of RegionWalk) come from; what is done
+// with them is here.
 //
 // The walk goes through a box in the chunks' memory order, 16 bytes per lane,
 // so reads from a chunk row and writes to an output row with unit stride are

@@ -370,6 +370,191 @@ def write_ndarrays(hier, path_name: str, meta: ArrayMetadata, offsets, arrays, d
         raise ZarrIOError(_native.STATUS_NAMES.get(r, str(r)), f"write_boxes: {ctx.last_error()}")
 
 
+def vboxes_tensor(offsets, shapes, strides, bases, device: int = 0):
+    """Device uint8 tensor of _native.VBox records (zcg_vbox): per box its
+    offset, shape and view strides (elements) per array dim and the device
+    address of element (0, ..., 0) of its view."""
+    import torch
+    B = len(offsets)
+    arr = (_native.VBox * max(B, 1))()
+    for b in range(B):
+        for d in range(len(offsets[b])):
+            arr[b].offset[d] = int(offsets[b][d])
+            arr[b].shape[d] = int(shapes[b][d])
+            arr[b].strides[d] = int(strides[b][d])
+        arr[b].base = int(bases[b])
+    raw = np.frombuffer(bytes(arr), np.uint8)[: B * ctypes.sizeof(_native.VBox)].copy()
+    return torch.from_numpy(raw).to(torch.device("cuda", device))
+
+
+def regions_v_scratch_bytes(n_boxes: int) -> int:
+    """zcg_regions_v_scratch_bytes: device working memory of one _v call."""
+    return int(_native.load_library().zcg_regions_v_scratch_bytes(int(n_boxes)))
+
+
+def _regions_v(name: str, meta: ArrayMetadata, bound, es, table, table_lo, table_n, boxes, status, scratch, fill,
+               fill_value, device, stream) -> None:
+    ctx = _native.context(device)
+    nd = meta.get_ndim()
+    r = _region(meta, BoundingBox([0] * nd, bound), es, fill, fill_value, [0] * nd)
+    lo = (ctypes.c_uint64 * _native.MAX_DIMS)(*[int(x) for x in table_lo])
+    n = (ctypes.c_uint64 * _native.MAX_DIMS)(*[int(x) for x in table_n])
+    n_boxes = boxes.numel() * boxes.element_size() // ctypes.sizeof(_native.VBox) if boxes is not None else 0
+    if n_boxes and scratch is None:
+        import torch
+        scratch = torch.empty(regions_v_scratch_bytes(n_boxes), dtype=torch.uint8, device=boxes.device)
+    st = getattr(ctx.lib, name)(ctx.handle, ctypes.byref(r), ctypes.addressof(lo), ctypes.addressof(n),
+                                table.data_ptr() if table is not None else None,
+                                boxes.data_ptr() if n_boxes else None, n_boxes,
+                                scratch.data_ptr() if scratch is not None else None,
+                                status.data_ptr() if status is not None else None, _stream_handle(stream, device))
+    _raise_status(st, ctx, name[4:])
+
+
+def assemble_regions_v(meta: ArrayMetadata, bound: Sequence[int], es: int, table, table_lo, table_n, boxes, status,
+                       fill: bool, fill_value: int, device: int = 0, stream=None, scratch=None) -> None:
+    """Device-level call for many boxes of differing shapes
+    (zcg_read_regions_v): assemble_regions with `boxes` = device tensor of
+    _native.VBox records (vboxes_tensor), each with its own shape and view, and
+    `bound` = the largest extent per dimension any box may have.  `scratch` =
+    device tensor of regions_v_scratch_bytes(B) bytes (None: allocated here,
+    which a captured call must not do).  Asynchronous."""
+    _regions_v("zcg_read_regions_v", meta, bound, es, table, table_lo, table_n, boxes, status, scratch, fill,
+               fill_value, device, stream)
+
+
+def scatter_regions_v(meta: ArrayMetadata, bound: Sequence[int], es: int, table, table_lo, table_n, boxes, status,
+                      device: int = 0, stream=None, scratch=None) -> None:
+    """Device-level inverse of assemble_regions_v (zcg_write_regions_v): every
+    box's view is written into the chunk slots of `table`.  Boxes of one call
+    that overlap leave either value; split the call with regions_v_waves where
+    the later box must win.  Asynchronous."""
+    _regions_v("zcg_write_regions_v", meta, bound, es, table, table_lo, table_n, boxes, status, scratch, False, 0,
+               device, stream)
+
+
+def _bound(shapes, nd: int) -> List[int]:
+    return [max([int(s[d]) for s in shapes] or [0]) for d in range(nd)]
+
+
+def regions_v_grid(meta: ArrayMetadata, offsets, shapes):
+    """zcg_regions_v_grid (host code, no GPU): the union of the boxes' grid
+    ranges -> (lo, n)."""
+    L = _native.load_library()
+    nd = meta.get_ndim()
+    r = _region(meta, BoundingBox([0] * nd, _bound(shapes, nd)), 1, False, 0, [0] * nd)
+    offs = np.ascontiguousarray(np.array(offsets, dtype=np.uint64).reshape(-1, nd))
+    shp = np.ascontiguousarray(np.array(shapes, dtype=np.uint64).reshape(-1, nd))
+    lo = (ctypes.c_uint64 * _native.MAX_DIMS)()
+    n = (ctypes.c_uint64 * _native.MAX_DIMS)()
+    L.zcg_regions_v_grid(ctypes.byref(r), offs.ctypes.data, shp.ctypes.data, offs.shape[0], ctypes.addressof(lo),
+                         ctypes.addressof(n))
+    return [int(lo[d]) for d in range(nd)], [int(n[d]) for d in range(nd)]
+
+
+def regions_v_waves(meta: ArrayMetadata, offsets, shapes):
+    """zcg_regions_v_waves (host code, no GPU): regions_waves for boxes
+    `offsets` (B x ndim) with `shapes` (B x ndim) -> (number of waves, wave
+    index per box)."""
+    L = _native.load_library()
+    nd = meta.get_ndim()
+    r = _region(meta, BoundingBox([0] * nd, _bound(shapes, nd)), 1, False, 0, [0] * nd)
+    offs = np.ascontiguousarray(np.array(offsets, dtype=np.uint64).reshape(-1, nd))
+    shp = np.ascontiguousarray(np.array(shapes, dtype=np.uint64).reshape(-1, nd))
+    B = offs.shape[0]
+    wave_of = np.zeros(max(B, 1), np.uint32)
+    n = L.zcg_regions_v_waves(ctypes.byref(r), offs.ctypes.data, shp.ctypes.data, B, wave_of.ctypes.data)
+    return int(n), [int(w) for w in wave_of[:B]]
+
+
+def _native_meta(meta: ArrayMetadata, flags: int):
+    st, am, msg = _native.array_meta_from_json(meta.to_json())
+    if st != _native.OK:
+        raise ZarrIOError(_native.STATUS_NAMES.get(st, str(st)), f"array metadata: {msg}")
+    am.array.compression.flags = flags
+    return am
+
+
+def read_ndarrays_v(hier, path_name: str, meta: ArrayMetadata, boxes: Sequence[BoundingBox], t, device: int = 0,
+                    as_tensor: bool = False, flags: int = 0, slot_budget_bytes: int = 0):
+    """read_ndarray for many boxes of differing shapes in one native call
+    (zcg_store_read_boxes_v[_device]): a list of arrays whose [b] equals
+    read_ndarray(..., boxes[b], t).  The chunks the boxes share are read and
+    decoded once.  With as_tensor the result is (uint8 device tensor of the
+    boxes back to back, byte offset per box, element strides per box), each box
+    dense in the chunk memory order."""
+    import torch
+    check_array_type(t, meta)
+    nd = meta.get_ndim()
+    for bb in boxes:
+        if len(bb.offset) != nd:
+            raise ZarrIOError("InvalidData", "Wrong number of dimensions")
+    B = len(boxes)
+    dt = np.dtype(t).newbyteorder("=")
+    es = dt.itemsize
+    order = "F" if meta.chunk_memory_layout == "F" else "C"
+    offs = np.ascontiguousarray(np.array([bb.offset for bb in boxes], dtype=np.uint64).reshape(-1, nd))
+    shp = np.ascontiguousarray(np.array([bb.shape for bb in boxes], dtype=np.uint64).reshape(-1, nd))
+    strides = [_strides(bb.shape, order) for bb in boxes]
+    at = [0]
+    for bb in boxes:
+        at.append(at[-1] + int(np.prod(bb.shape, dtype=object)) * es)
+    am = _native_meta(meta, flags)
+    ctx = _native.context(device)
+    root, path = os.fsencode(hier.base_path), path_name.encode()
+    if as_tensor:
+        out = torch.empty(max(at[-1], 1), dtype=torch.uint8, device=torch.device("cuda", device))
+        outs = (ctypes.c_void_p * max(B, 1))(*[out.data_ptr() + at[b] for b in range(B)])
+        r = ctx.lib.zcg_store_read_boxes_v_device(ctx.handle, ctypes.byref(am), root, path, shp.ctypes.data, None, 1,
+                                                  offs.ctypes.data, ctypes.addressof(outs), B, slot_budget_bytes, 16)
+    else:
+        host = np.empty(max(at[-1], 1), np.uint8)
+        outs = (ctypes.c_void_p * max(B, 1))(*[host.ctypes.data + at[b] for b in range(B)])
+        r = ctx.lib.zcg_store_read_boxes_v(ctx.handle, ctypes.byref(am), root, path, shp.ctypes.data,
+                                           offs.ctypes.data, ctypes.addressof(outs), B, slot_budget_bytes, 16)
+    if r != _native.OK:
+        raise ZarrIOError(_native.STATUS_NAMES.get(r, str(r)), f"read_boxes: {ctx.last_error()}")
+    if as_tensor:
+        return out[: at[-1]], at[:-1], strides
+    return [np.ndarray(tuple(bb.shape), dtype=dt, buffer=host, offset=at[b],
+                       strides=tuple(s * es for s in strides[b])).copy(order=order)
+            for b, bb in enumerate(boxes)]
+
+
+def write_ndarrays_v(hier, path_name: str, meta: ArrayMetadata, offsets, arrays, device: int = 0,
+                     slot_budget_bytes: int = 0, flags: int = 0) -> None:
+    """write_ndarray for many boxes of differing shapes in one native call
+    (zcg_store_write_boxes_v): `arrays` is a sequence of numpy arrays, box b
+    written at offsets[b].  The store ends up as if write_ndarray had run for
+    box 0, 1, ... in that order (a later box wins where two overlap), but every
+    chunk the boxes touch is read at most once, and encoded and written once.
+    `flags`: decode flags for the chunks that are read first."""
+    nd = meta.get_ndim()
+    arrays = [np.asarray(a) for a in arrays]
+    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64).reshape(-1, nd))
+    B = offs.shape[0]
+    if len(arrays) != B:
+        raise ZarrIOError("InvalidData", "Bounding boxes and arrays differ in number")
+    order = "F" if meta.chunk_memory_layout == "F" else "C"
+    dense = []
+    for a in arrays:
+        if a.ndim != nd:
+            raise ZarrIOError("InvalidData", "Wrong number of dimensions")
+        dt = a.dtype.newbyteorder("=")
+        check_array_type(dt, meta)
+        # dense in the chunk memory order
+        dense.append(np.ascontiguousarray(a.astype(dt, copy=False).T if order == "F" else a.astype(dt, copy=False)))
+    shp = np.ascontiguousarray(np.array([a.shape for a in arrays], dtype=np.uint64).reshape(-1, nd))
+    am = _native_meta(meta, flags)
+    ctx = _native.context(device)
+    ins = (ctypes.c_void_p * max(B, 1))(*[a.ctypes.data if a.size else 0 for a in dense])
+    r = ctx.lib.zcg_store_write_boxes_v(ctx.handle, ctypes.byref(am), os.fsencode(hier.base_path),
+                                        path_name.encode(), shp.ctypes.data, offs.ctypes.data, ctypes.addressof(ins),
+                                        B, slot_budget_bytes, 16)
+    if r != _native.OK:
+        raise ZarrIOError(_native.STATUS_NAMES.get(r, str(r)), f"write_boxes: {ctx.last_error()}")
+
+
 def read_ndarray_into(hier, path_name: str, meta: ArrayMetadata, bbox: BoundingBox, arr: np.ndarray, t,
                       device: int = 0, flags: int = 0) -> None:
     """ZarrNdarrayReader::read_ndarray_into (ndarray.rs:176-268): elements
