@@ -17,6 +17,7 @@ import pytest
 
 import zref
 from golden_util import CODEC_IDS, dtype_info
+from lz4_craft import xxh32
 from zarr_amd import ArrayMetadata, DefaultChunk, FilesystemHierarchy, Gzip, Lz4, SliceDataChunk, _native
 from zarr_amd.chunk import ZarrIOError, abi_array
 
@@ -66,34 +67,6 @@ def text(n, seed):
 
 def noise(n, seed, hi=256):
     return np.random.default_rng(seed).integers(0, hi, n).astype(np.uint8).tobytes()
-
-
-def xxh32(data, seed=0):
-    """XXH32, as the LZ4 frame format uses it (header and content checksums)."""
-    P1, P2, P3, P4, P5, M = 2654435761, 2246822519, 3266489917, 668265263, 374761393, 0xFFFFFFFF
-    rotl = lambda x, r: ((x << r) | (x >> (32 - r))) & M  # noqa: E731
-    n, i = len(data), 0
-    if n >= 16:
-        v = [(seed + P1 + P2) & M, (seed + P2) & M, seed & M, (seed - P1) & M]
-        while i + 16 <= n:
-            for k, w in enumerate(struct.unpack_from("<4I", data, i)):
-                v[k] = rotl((v[k] + w * P2) & M, 13) * P1 & M
-            i += 16
-        h = (rotl(v[0], 1) + rotl(v[1], 7) + rotl(v[2], 12) + rotl(v[3], 18)) & M
-    else:
-        h = (seed + P5) & M
-    h = (h + n) & M
-    while i + 4 <= n:
-        h = rotl((h + struct.unpack_from("<I", data, i)[0] * P3) & M, 17) * P4 & M
-        i += 4
-    while i < n:
-        h = rotl((h + data[i] * P5) & M, 11) * P1 & M
-        i += 1
-    h ^= h >> 15
-    h = h * P2 & M
-    h ^= h >> 13
-    h = h * P3 & M
-    return h ^ (h >> 16)
 
 
 def lz4_stored_frame(blocks, content_checksum=True, content_size=None, end_mark=True):
