@@ -18,18 +18,37 @@ uint64_t crc64_byte(uint64_t c, uint32_t b) {
     return c;
 }
 
-struct XzHostIO {
+// CHECKED: at, in, pget and pset count every index outside [0, D + 64),
+// [0, n) and [0, the model's size) in `bad` and clamp it, so that a stream
+// can be shown to keep the core inside its buffers before it reaches a GPU.
+template <bool CHECKED>
+struct XzHostIOT {
     uint64_t n, D, pos;
     const uint8_t* src;
     uint8_t* dst;
     uint16_t probs[1846 + (0x300 << 4)];
     uint8_t tail[64];  // output bytes from D on (a BCJ block's look-past, zx::xz_decode)
-    uint8_t& at(uint64_t i) { return i < D ? dst[i] : tail[i - D]; }
+    uint64_t bad;      // CHECKED: indexes out of bounds so far
+    uint32_t nprobs;   // CHECKED: the model's size (init_probs)
+    uint8_t& at(uint64_t i) {
+        if (CHECKED && i >= D + 64) { bad++; i = 0; }
+        return i < D ? dst[i] : tail[i - D];
+    }
     void make_uniform() {}
-    uint32_t in(uint64_t i) const { return src[i]; }
-    uint32_t pget(uint32_t i) const { return probs[i]; }
-    void pset(uint32_t i, uint32_t v) { probs[i] = (uint16_t)v; }
-    void init_probs(uint32_t count) { for (uint32_t i = 0; i < count; i++) probs[i] = 1024; }
+    uint32_t in(uint64_t i) {
+        if (CHECKED && i >= n) { bad++; return 0; }
+        return src[i];
+    }
+    uint32_t pidx(uint32_t i) {
+        if (CHECKED && i >= nprobs) { bad++; return 0; }
+        return i;
+    }
+    uint32_t pget(uint32_t i) { return probs[pidx(i)]; }
+    void pset(uint32_t i, uint32_t v) { probs[pidx(i)] = (uint16_t)v; }
+    void init_probs(uint32_t count) {
+        nprobs = count;
+        for (uint32_t i = 0; i < count; i++) probs[i] = 1024;
+    }
     bool lclp_ok(uint32_t) const { return true; }
     void put(uint32_t b) { at(pos++) = (uint8_t)b; }
     uint32_t back(uint64_t dist) { return at(pos - 1 - dist); }
@@ -38,7 +57,7 @@ struct XzHostIO {
         pos += len;
     }
     void copy_in(uint64_t ip, uint32_t len) {
-        for (uint32_t k = 0; k < len; k++) at(pos + k) = src[ip + k];
+        for (uint32_t k = 0; k < len; k++) at(pos + k) = (uint8_t)in(ip + k);
         pos += len;
     }
     void finish() {}
@@ -82,6 +101,7 @@ struct XzHostIO {
         return ~c;
     }
 };
+typedef XzHostIOT<false> XzHostIO;
 
 }  // namespace
 
@@ -93,6 +113,34 @@ extern "C" int zh_xz_decode(const uint8_t* src, uint64_t n, uint8_t* dst, uint64
     io.src = src;
     io.dst = dst;
     return zx::xz_decode(io);
+}
+
+// the same decode with every index of the IO counted: *bad = how many fell
+// outside the output (D + 64 with the tail), the input or the model
+extern "C" int zh_xz_decode_checked(const uint8_t* src, uint64_t n, uint8_t* dst, uint64_t D, uint64_t* bad) {
+    static thread_local XzHostIOT<true> io;
+    io.n = n;
+    io.D = D;
+    io.pos = 0;
+    io.src = src;
+    io.dst = dst;
+    io.bad = 0;
+    io.nprobs = 0;
+    const int r = zx::xz_decode(io);
+    *bad = io.bad;
+    return r;
+}
+
+// the counting IO counts: one index past each of the three bounds, one at each (3 expected)
+extern "C" uint64_t zh_xz_checked_selftest() {
+    static thread_local XzHostIOT<true> io;
+    uint8_t in[4] = {1, 2, 3, 4}, out[4] = {0, 0, 0, 0};
+    io.n = 4; io.D = 4; io.pos = 0; io.src = in; io.dst = out; io.bad = 0;
+    io.init_probs(10);
+    io.at(4 + 63) = 1; io.at(4 + 64) = 1;
+    (void)io.in(3); (void)io.in(4);
+    io.pset(9, 7); io.pset(10, 7);
+    return io.bad + (io.pget(9) == 7 ? 0 : 100) + (out[0] == 1 ? 0 : 100);
 }
 
 // ---------------------------------------------------------------------------

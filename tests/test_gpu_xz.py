@@ -161,7 +161,17 @@ def test_xz_filter_chains(chain):
 
 def test_xz_sha256_check_parity():
     """Check ID 10: liblzma verifies the SHA-256 of each block; whole and
-    partial reads, a corrupted digest byte, corrupted data, two blocks."""
+    partial reads, a corrupted digest byte, corrupted data, and two blocks
+    (liblzma's encoder writes one: the two-block streams, one of them with
+    the first block's digest wrong, are the hand-written ones of
+    tests/xz_cases.py)."""
+    import xz_cases
+    import xz_craft
+    (_, good, _, _), (_, bad_spec, _, bad) = xz_cases.check_cases(10)   # family G's, built alone
+    assert len(good["blocks"]) == 2 and good["check"] == 10 and bad != xz_craft.write(bad_spec)
+    for s2 in (xz_craft.write(good), bad):
+        for D in (xz_cases.MAIN, 1500, 900):  # whole, inside the second block, inside the first
+            check("xz", s2, "u1", D)
     rng = np.random.default_rng(11)
     payload = rw(150000, seed=2).tobytes()
     s = lzma.compress(payload, format=lzma.FORMAT_XZ, check=lzma.CHECK_SHA256, preset=6)
