@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import zref
-from test_gpu_parity import DATASETS, check, check_many, rw
+from gpu_check import DATASETS, check, check_many, rw
 
 pytestmark = pytest.mark.gpu
 

@@ -21,7 +21,7 @@ import pytest
 
 import bz2_cases as cs
 import bz2_craft as bc
-from test_gpu_parity import check_many, rw
+from gpu_check import check_many, rw
 
 pytestmark = pytest.mark.gpu
 

@@ -597,7 +597,7 @@ def test_bzip2_encode_quant_ratio():
     """C2-shaped f32 chunks: same Huffman machinery as libbz2, so the ratio
     must be close to libbz2 level 9's on the same data."""
     import bz2
-    from test_gpu_parity import quant_f32
+    from gpu_check import quant_f32
     from zarr_amd.compression import Bzip2
     arrays = [quant_f32(s) for s in range(4)]
     D = arrays[0].nbytes

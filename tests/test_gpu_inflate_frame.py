@@ -15,59 +15,20 @@ import zlib
 import numpy as np
 import pytest
 
-import zref
-from golden_util import CODEC_IDS, dtype_info
-from zarr_amd import ArrayMetadata, Gzip, _native
+from deflate_kit import PLAIN_HEADER, stored, text, trailer
+from golden_util import dtype_info
+from gpu_check import GUARD, check_many
+from zarr_amd import _native
 
 pytestmark = pytest.mark.gpu
 
-KIND = {zref.OK: "Ok", zref.EOF: "UnexpectedEof", zref.INVALID_DATA: "InvalidData"}
 FLAG_SETS = (0, _native.FLAG_SERIAL_INFLATE, _native.FLAG_INFLATE_BLOCK_PAR, _native.FLAG_INFLATE_WAVE)
-GUARD = 4096
-PLAIN_HEADER = bytes([0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 255])
-
-
-def trailer(payload):
-    return struct.pack("<II", zlib.crc32(payload), len(payload) & 0xFFFFFFFF)
-
-
-def stored(data, last=False):
-    """One stored block (byte aligned: the header's 3 bits and 5 bits of padding)."""
-    return bytes([1 if last else 0]) + struct.pack("<HH", len(data), len(data) ^ 0xFFFF) + data
-
-
-def text(n, seed):
-    rng = np.random.default_rng(seed)
-    words = [bytes(rng.integers(97, 123, int(rng.integers(2, 10))).astype(np.uint8)) for _ in range(300)]
-    p = 1.0 / (np.arange(300) + 1.0)
-    out = b" ".join(words[i] for i in rng.choice(300, size=n // 4, p=p / p.sum()))
-    assert len(out) >= n
-    return out[:n]
 
 
 def check_group(streams, dt, n, want):
     """`want`: the oracle's answer for each stream (checked first).  Then one
     launch per flag set: oracle parity of status and bytes, guard intact."""
-    import torch
-    from zarr_amd.batch import BatchCodec, PackedStreams
-    es, be, isb, _ = dtype_info(dt)
-    D = n * es
-    st_ref, out_ref = zref.decode_batch(CODEC_IDS["gzip"], [np.frombuffer(s, np.uint8) for s in streams],
-                                        D, elem_size=es, big_endian=be, is_bool=isb)
-    assert [KIND[int(x)] for x in st_ref] == list(want), (n, [KIND[int(x)] for x in st_ref])
-    meta = ArrayMetadata.new([n], [n], dt, Gzip(-1))
-    for flags in FLAG_SETS:
-        dst = torch.full((len(streams) * (D + GUARD),), 0xAB, dtype=torch.uint8, device="cuda:0")
-        packed = PackedStreams(streams, D + GUARD, "cuda:0", dst=dst)
-        BatchCodec(0).decode(meta, packed, flags=flags)
-        torch.cuda.synchronize()
-        st = packed.status.cpu().numpy()
-        out = dst.cpu().numpy().reshape(len(streams), D + GUARD)
-        for i in range(len(streams)):
-            assert KIND[int(st[i])] == KIND[int(st_ref[i])], (i, n, flags, int(st[i]), int(st_ref[i]))
-            if st_ref[i] == zref.OK:
-                assert out[i, :D].tobytes() == out_ref[i].tobytes(), (i, n, flags)
-            assert (out[i, D:] == 0xAB).all(), (i, n, flags)
+    check_many("gzip", streams, dt, n, FLAG_SETS, guard=GUARD, want=want)
 
 
 # ---- 1. stored blocks ---------------------------------------------------------------------------

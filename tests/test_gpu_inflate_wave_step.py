@@ -9,102 +9,25 @@ the system zlib; their structure (code lengths, token positions) is read back
 with a small deflate parser so that each case checks that it has the property
 it is there for.
 """
-import struct
 import zlib
 
-import numpy as np
 import pytest
 
-import zref
-from golden_util import CODEC_IDS, dtype_info
-from zarr_amd import ArrayMetadata, Gzip, _native
+from deflate_kit import (DIST_EXTRA, LEN_BASE, LEN_EXTRA, Bits, _skewed_with_copies, _three_symbols, block_header,
+                         canon, deflate, gzip_wrap, sym)
+from golden_util import dtype_info
+from gpu_check import GUARD, check_many
+from zarr_amd import _native
 
 pytestmark = pytest.mark.gpu
 
-KIND = {zref.OK: "Ok", zref.EOF: "UnexpectedEof", zref.INVALID_DATA: "InvalidData"}
 FLAG_SETS = (0, _native.FLAG_INFLATE_WAVE, _native.FLAG_DEBUG_INFLATE_LONG_SEG,
              _native.FLAG_INFLATE_WAVE | _native.FLAG_DEBUG_INFLATE_LONG_SEG)
-GUARD = 4096
-
-
-def gzip_wrap(raw_deflate, payload):
-    h = bytes([0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 255])
-    return h + raw_deflate + struct.pack("<II", zlib.crc32(payload), len(payload) & 0xFFFFFFFF)
-
-
-def deflate(payload, level=6, strategy=zlib.Z_DEFAULT_STRATEGY, mem=8):
-    c = zlib.compressobj(level, zlib.DEFLATED, -15, mem, strategy)
-    return c.compress(payload) + c.flush()
 
 
 def check_batch(streams, dt, n):
     """One launch per flag set: oracle parity of status and bytes, guard intact."""
-    import torch
-    from zarr_amd.batch import BatchCodec, PackedStreams
-    es, be, isb, _ = dtype_info(dt)
-    D = n * es
-    st_ref, out_ref = zref.decode_batch(CODEC_IDS["gzip"], [np.frombuffer(s, np.uint8) for s in streams],
-                                        D, elem_size=es, big_endian=be, is_bool=isb)
-    meta = ArrayMetadata.new([n], [n], dt, Gzip(-1))
-    for flags in FLAG_SETS:
-        dst = torch.full((len(streams) * (D + GUARD),), 0xAB, dtype=torch.uint8, device="cuda:0")
-        packed = PackedStreams(streams, D + GUARD, "cuda:0", dst=dst)
-        BatchCodec(0).decode(meta, packed, flags=flags)
-        torch.cuda.synchronize()
-        st = packed.status.cpu().numpy()
-        out = dst.cpu().numpy().reshape(len(streams), D + GUARD)
-        for i in range(len(streams)):
-            assert KIND[int(st[i])] == KIND[int(st_ref[i])], (i, flags, int(st[i]), int(st_ref[i]))
-            if st_ref[i] == zref.OK:
-                assert out[i, :D].tobytes() == out_ref[i].tobytes(), (i, flags)
-            assert (out[i, D:] == 0xAB).all(), (i, flags)
-    return st_ref
-
-
-# ---- a small deflate parser: code lengths and token positions of the first blocks ----
-LEN_BASE = [3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195,
-            227, 258]
-LEN_EXTRA = [0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0]
-DIST_EXTRA = [0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13]
-CLEN_ORDER = [16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15]
-
-
-class Bits:
-    def __init__(self, b):
-        self.b = b
-        self.p = 0
-
-    def bits(self, n):  # n <= 16
-        p = self.p
-        x = (int.from_bytes(self.b[p >> 3:(p >> 3) + 4], "little") >> (p & 7)) & ((1 << n) - 1)
-        self.p = p + n
-        return x
-
-
-def canon(lens):
-    count = [0] * 16
-    for l in lens:
-        count[l] += 1
-    count[0] = 0
-    nxt, code = [0] * 16, 0
-    for b in range(1, 16):
-        code = (code + count[b - 1]) << 1
-        nxt[b] = code
-    table = {}
-    for s, l in enumerate(lens):
-        if l:
-            table[(l, nxt[l])] = s
-            nxt[l] += 1
-    return table
-
-
-def sym(br, table):
-    c = l = 0
-    while True:
-        c = (c << 1) | br.bits(1)
-        l += 1
-        if (l, c) in table:
-            return table[(l, c)]
+    return check_many("gzip", streams, dt, n, FLAG_SETS, guard=GUARD)
 
 
 def parse_blocks(raw, nblocks):
@@ -112,27 +35,8 @@ def parse_blocks(raw, nblocks):
     [{lmax, dmax, tokens: [(stream bit after the token, output bytes after it, length)]}]."""
     br, out, produced = Bits(raw), [], 0
     for _ in range(nblocks):
-        last, ty = br.bits(1), br.bits(2)
-        assert ty in (1, 2), ty
-        if ty == 1:
-            hl, ls = 288, [8] * 144 + [9] * 112 + [7] * 24 + [8] * 8 + [5] * 30
-        else:
-            hl, hd, hc = br.bits(5) + 257, br.bits(5) + 1, br.bits(4) + 4
-            cl = [0] * 19
-            for i in range(hc):
-                cl[CLEN_ORDER[i]] = br.bits(3)
-            ct, ls = canon(cl), []
-            while len(ls) < hl + hd:
-                s = sym(br, ct)
-                if s < 16:
-                    ls.append(s)
-                elif s == 16:
-                    ls += [ls[-1]] * (3 + br.bits(2))
-                elif s == 17:
-                    ls += [0] * (3 + br.bits(3))
-                else:
-                    ls += [0] * (11 + br.bits(7))
-        lt, dt = canon(ls[:hl]), canon(ls[hl:])
+        last, ll, dl = block_header(br)
+        lt, dt = canon(ll), canon(dl)
         toks = []
         while True:
             s = sym(br, lt)
@@ -144,30 +48,10 @@ def parse_blocks(raw, nblocks):
                 br.bits(DIST_EXTRA[sym(br, dt)])
             produced += n
             toks.append((br.p, produced, n))
-        out.append({"lmax": max(ls[:hl]), "dmax": max(ls[hl:]), "tokens": toks})
+        out.append({"lmax": max(ll), "dmax": max(dl), "tokens": toks})
         if last:
             break
     return out
-
-
-# ---- payloads (built once) ---------------------------------------------------------------
-def _skewed_with_copies():
-    """128 KiB, p(i) ~ 1 / (i + 1)^1.3, ~2 000 copies of 3-40 bytes from up to 32 K back."""
-    rng = np.random.default_rng(1307)
-    p = 1.0 / (np.arange(256) + 1.0) ** 1.3
-    a = rng.choice(256, size=128 << 10, p=p / p.sum()).astype(np.uint8)
-    for _ in range(2000):
-        n = int(rng.integers(3, 41))
-        at = int(rng.integers(64, a.size - n))
-        d = int(rng.integers(1, min(at, 32768) + 1))
-        for k in range(n):  # (byte by byte: a copy may overlap itself, as in LZ77)
-            a[at + k] = a[at + k - d]
-    return a.tobytes()
-
-
-def _three_symbols():
-    rng = np.random.default_rng(2207)
-    return rng.choice(np.array([0, 7, 255], np.uint8), size=64 << 10, p=[0.9, 0.08, 0.02]).tobytes()
 
 
 @pytest.fixture(scope="module")
@@ -192,7 +76,7 @@ def test_subtable_codes_through_rewritten_tables(case1):
     blocks = parse_blocks(raw, 2)
     assert max(b["lmax"] for b in blocks) > 9 and max(b["dmax"] for b in blocks) > 8
     st = check_batch([s], "u1", len(payload))
-    assert st[0] == zref.OK
+    assert st[0] == "Ok"
 
 
 def test_list_cap_and_steady_to_edge_switch(case2):
@@ -205,7 +89,7 @@ def test_list_cap_and_steady_to_edge_switch(case2):
     span = sum(1 for t in toks[i0:i0 + 4096] if t[0] < toks[i0][0] + 4096)
     assert span > 3000, span
     st = check_batch([s], "u1", len(payload))
-    assert st[0] == zref.OK
+    assert st[0] == "Ok"
 
 
 def test_short_segments_inside_the_mark_zone(case1):
@@ -217,7 +101,7 @@ def test_short_segments_inside_the_mark_zone(case1):
     assert len(small) >= 100 and max(len(b["tokens"]) for b in small) <= 128, len(small)
     streams = [gzip_wrap(deflate(payload, lv, mem=mem), payload) for mem in (1, 4, 9) for lv in (1, 6, 9)]
     st = check_batch(streams, "u1", len(payload))
-    assert (st == zref.OK).all()
+    assert set(st) == {"Ok"}
 
 
 def test_stream_end_in_the_edge_body(case1):
@@ -227,7 +111,7 @@ def test_stream_end_in_the_edge_body(case1):
     payload, raw, s = case1
     cuts = [len(s) - k for k in range(1, 49)] + [len(s) * k // 18 for k in range(1, 17)]
     st = check_batch([s[:c] for c in cuts], "u1", len(payload))
-    assert (st != zref.OK).sum() >= 48 - 8  # (the last cuts fall in the 8-byte gzip trailer)
+    assert sum(k != "Ok" for k in st) >= 48 - 8  # (the last cuts fall in the 8-byte gzip trailer)
 
 
 @pytest.mark.parametrize("which", ["case1", "case2"])
@@ -261,4 +145,4 @@ def test_swapped_and_bool_dtypes(case1, dt):
     payload, raw, s = case1
     es = dtype_info(dt)[0]
     st = check_batch([s], dt, len(payload) // es)
-    assert st[0] == zref.OK
+    assert st[0] == "Ok"

@@ -7,8 +7,9 @@ stores incompressible blocks raw and takes the offsets and lengths the data
 offers.  tests/lz4_craft.py writes frames sequence by sequence and
 tests/lz4_cases.py holds the tables; tests/test_lz4_craft_host.py pins them
 against the reference decoder and a plain model on the CPU.  Each batch runs
-through the default pick, the wave-per-block kernel (lz4_block_wave, 0x800)
-and the lane-per-block kernel (lz4_lane_block with LaneRing, 0x1000); frames
+through the default pick, the wave-per-block kernel (lz4_block_wave,
+FLAG_LZ4_WAVE_PER_BLOCK) and the lane-per-block kernel (lz4_lane_block with
+LaneRing, FLAG_LZ4_LANE_PER_BLOCK); frames
 the block placement cannot serve (linked, short block in mid-frame, early
 end) reach the serial lz4_block under every flag.  Per stream: the status
 kind is the oracle's, Ok chunks have the oracle's bytes, and the 0xAB guard
@@ -62,60 +63,27 @@ lists in tests/lz4_cases.py when one of them changes):
 Nothing here is meant to fault: the invalid cases are streams the kernels'
 own checks reject with a status.
 """
-import functools
-
 import numpy as np
 import pytest
 
 import lz4_cases as cs
 import lz4_craft as lc
-import zref
 from golden_util import dtype_info
-from zarr_amd import ArrayMetadata, Lz4, _native
+from gpu_check import GUARD, check_many, oracle
+from zarr_amd import _native
 
 pytestmark = pytest.mark.gpu
 
-KIND = {zref.OK: "ok", zref.EOF: "eof", zref.INVALID_DATA: "invalid"}
 WAVE, LANE = _native.FLAG_LZ4_WAVE_PER_BLOCK, _native.FLAG_LZ4_LANE_PER_BLOCK
 FLAGS = [0, WAVE, LANE]
-GUARD = 4096
-
-
-def decode(streams, D, dt, flags):
-    import torch
-    from zarr_amd.batch import BatchCodec, PackedStreams
-    meta = ArrayMetadata.new([D // dtype_info(dt)[0]], [D // dtype_info(dt)[0]], dt, Lz4(65536))
-    dst = torch.full((len(streams) * (D + GUARD),), 0xAB, dtype=torch.uint8, device="cuda:0")
-    packed = PackedStreams(streams, D + GUARD, "cuda:0", dst=dst)
-    BatchCodec(0).decode(meta, packed, flags=flags)
-    torch.cuda.synchronize()
-    return packed.status.cpu().numpy(), dst.cpu().numpy().reshape(len(streams), D + GUARD)
-
-
-@functools.lru_cache(maxsize=None)
-def reference(streams, D, dt):
-    """The oracle's (kinds, bytes) of a batch, computed once."""
-    es, be, isb, _ = dtype_info(dt)
-    st, out = zref.decode_batch(zref.LZ4, [np.frombuffer(s, np.uint8) for s in streams], D, elem_size=es,
-                                big_endian=be, is_bool=isb)
-    return [KIND[int(x)] for x in st], [o.tobytes() for o in out]
 
 
 def check(streams, D, flags, dt="u1", want=None):
     """One batch under one flag set; want: the kinds the table names (the
-    oracle's must equal them)."""
-    streams = tuple(streams)
-    assert D % dtype_info(dt)[0] == 0
-    kinds, outs = reference(streams, D, dt)
-    if want is not None:
-        assert kinds == list(want)
-    st, out = decode(streams, D, dt, flags)
-    for i in range(len(streams)):
-        assert KIND[int(st[i])] == kinds[i], (i, D, dt, hex(flags), int(st[i]), kinds[i])
-        if kinds[i] == "ok":
-            assert out[i, :D].tobytes() == outs[i], (i, D, dt, hex(flags))
-        assert (out[i, D:] == 0xAB).all(), (i, D, dt, hex(flags))
-    return kinds
+    oracle's, asked once per batch, must equal them)."""
+    es = dtype_info(dt)[0]
+    assert D % es == 0
+    check_many("lz4", streams, dt, D // es, flags, guard=GUARD, want=want, cache=True)
 
 
 def family_batches(family, valid):
@@ -182,16 +150,11 @@ def test_content_checksum_verification():
         D, cases = cs.batches()[batch]
         good = [lc.frame(c.blocks, linked=c.linked, content_checksum=True) for c in cases]
         bad = [flip_literal(c, f) for c, f in zip(cases, good)]
-        streams = tuple(good + bad)
-        kinds, outs = reference(streams, D, "u1")
-        assert kinds == ["ok"] * len(streams)
-        for c, o in zip(cases, outs):
+        streams = good + bad
+        ref = oracle("lz4", streams, "u1", D, cache=True)
+        assert ref[0] == ["Ok"] * len(streams)
+        for c, o in zip(cases, ref[1]):
             assert o == lc.model(c.blocks, c.linked)[:D]
-        for f in FLAGS:
-            st, out = decode(streams, D, "u1", f | _native.FLAG_VERIFY)
-            for i in range(len(streams)):
-                want = "ok" if i < len(good) else "invalid"
-                assert KIND[int(st[i])] == want, (batch, i, hex(f), int(st[i]))
-                if want == "ok":
-                    assert out[i, :D].tobytes() == outs[i], (batch, i, hex(f))
-                assert (out[i, D:] == 0xAB).all(), (batch, i, hex(f))
+        check_many("lz4", streams, "u1", D, [f | _native.FLAG_VERIFY for f in FLAGS], guard=GUARD, ref=ref,
+                   expect=["Ok"] * len(good) + ["InvalidData"] * len(bad),
+                   names=[f"{batch}-{i}" for i in range(len(streams))])

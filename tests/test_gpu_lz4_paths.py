@@ -3,31 +3,16 @@ block, picked for large batches; one wave per block, picked for small ones)
 and the default pick must give the same bytes and statuses on valid,
 truncated and corrupted frames (lz.rs:81-83 -> LZ4F_decompress), and all must
 match the oracle."""
-import os
-import sys
-
 import numpy as np
 import pytest
 
+import zref
+from gpu_check import decode
 from zarr_amd import ArrayMetadata, Lz4
+from zarr_amd._native import FLAG_LZ4_LANE_PER_BLOCK as FLAG_LANE, FLAG_LZ4_WAVE_PER_BLOCK as FLAG_WAVE
 from zarr_amd.batch import BatchCodec, PackedStreams
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
-import zref  # noqa: E402  (oracle: checker only)
-
 pytestmark = pytest.mark.gpu
-
-FLAG_WAVE = 0x800
-FLAG_LANE = 0x1000
-
-
-def _decode(streams, D, flags, dt="u1"):
-    import torch
-    meta = ArrayMetadata.new([D * len(streams)], [D], dt, Lz4(65536))
-    packed = PackedStreams(streams, D, "cuda:0")
-    BatchCodec(0).decode(meta, packed, flags=flags)
-    torch.cuda.synchronize()
-    return packed.status.cpu().numpy(), packed.dst.view(len(streams), -1).cpu().numpy()
 
 
 def _payloads():
@@ -60,9 +45,9 @@ def test_lane_and_wave_decoders_agree():
         b[int(rng.integers(7, len(b)))] ^= int(rng.integers(1, 256))
         extra.append(bytes(b))
     allst = streams + extra
-    s0, o0 = _decode(allst, D, FLAG_LANE)
-    s1, o1 = _decode(allst, D, FLAG_WAVE)
-    s2, o2 = _decode(allst, D, 0)
+    s0, o0 = decode("lz4", allst, "u1", D, FLAG_LANE)
+    s1, o1 = decode("lz4", allst, "u1", D, FLAG_WAVE)
+    s2, o2 = decode("lz4", allst, "u1", D, 0)
     assert s0.tolist() == s1.tolist() == s2.tolist()
     for i, p in enumerate(pays):
         assert s0[i] == 0 and bytes(o0[i]) == p and bytes(o1[i]) == p and bytes(o2[i]) == p
@@ -91,7 +76,7 @@ def test_decoder_frame_variants(frame, flags):
         else:
             streams.append(zref.lz4_frame_custom(p, **FRAMES[frame]))
     for D in (1 << 20, (1 << 20) - 1000, 65536 * 3, 65536 * 3 + 7):
-        st, out = _decode(streams, D, flags)
+        st, out = decode("lz4", streams, "u1", D, flags)
         for i, s in enumerate(streams):
             ost, ref = zref.decode(zref.LZ4, s, D, 1)
             assert ost == st[i], (frame, D, i)

@@ -5,7 +5,6 @@ tests/integration_test.rs) plus stream variants the reference decoder
 accepts.  Every expected output comes from the oracle (oracle/zref.c over the
 reference's own C codec libraries) or from the committed golden fixtures.
 """
-import os
 import struct
 import zlib
 
@@ -13,52 +12,16 @@ import numpy as np
 import pytest
 
 import zref
-from golden_util import (CODEC_IDS, DEFAULT_PARAM, doc_spec, dtype_info, reencoded,
-                         zarrita_chunks, zarrita_meta_json)
-from zarr_amd import (ArrayMetadata, DefaultChunk, Gzip, Lz4, NativeUnavailable, Raw, SliceDataChunk,
-                      ZarrIOError, read_chunks_host)
-from zarr_amd.compression import Bzip2, Xz
+from deflate_kit import deflate, gzip_wrap
+from golden_util import CODEC_IDS, DEFAULT_PARAM, doc_spec, dtype_info, reencoded, zarrita_chunks, zarrita_meta_json
+from gpu_check import COMP, DATASETS, GUARD, check, check_many, decode, gpu_decode, meta_for, rw
+from zarr_amd import ArrayMetadata, DefaultChunk, NativeUnavailable, Raw, SliceDataChunk, ZarrIOError, read_chunks_host
+from zarr_amd._native import (FLAG_INFLATE_WAVE, FLAG_LZ4_LANE_PER_BLOCK, FLAG_LZ4_WAVE_PER_BLOCK,
+                              FLAG_SKIP_LZ4_BLOCK_CHECKSUM)
 
 pytestmark = pytest.mark.gpu
 
 GPU_DECODE = ["raw", "gzip", "lz4", "xz", "bzip2"]
-COMP = {"raw": lambda p: Raw(), "gzip": lambda p: Gzip(p), "lz4": lambda p: Lz4(p),
-        "bzip2": lambda p: Bzip2(p), "xz": lambda p: Xz(p)}
-NPT = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}
-
-
-def meta_for(codec, dt, n, param=None):
-    p = DEFAULT_PARAM[codec] if param is None else param
-    return ArrayMetadata.new([n], [n], dt, COMP[codec](p))
-
-
-def gpu_decode(codec, stream, dt, n, param=None, flags=0):
-    """read_chunk on the GPU; returns (kind or 'Ok', host-native bytes)."""
-    es, be, isb, npdt = dtype_info(dt)
-    meta = meta_for(codec, dt, n, param)
-    try:
-        ch = DefaultChunk.read_chunk(stream, meta, [0], npdt, flags=flags)
-    except ZarrIOError as e:
-        return e.kind, b""
-    return "Ok", ch.get_data().tobytes()
-
-
-# a one-chunk gzip read runs the 256-lane kernel by default (small batch);
-# every gzip check also forces the one-wave-per-chunk kernel (the C2 kernel)
-FLAG_INFLATE_WAVE = 0x4000
-
-
-KIND = {zref.OK: "Ok", zref.EOF: "UnexpectedEof", zref.INVALID_DATA: "InvalidData"}
-
-
-def check(codec, stream, dt, n, param=None):
-    es, be, isb, _ = dtype_info(dt)
-    st, ref = zref.decode(CODEC_IDS[codec], stream, n * es, es, be, isb)
-    for flags in ((0, FLAG_INFLATE_WAVE) if codec == "gzip" else (0,)):
-        kind, out = gpu_decode(codec, stream, dt, n, param, flags)
-        assert kind == KIND[st], (kind, st, flags)
-        if st == zref.OK:
-            assert out == ref, flags
 
 
 def test_native_library_is_loaded():
@@ -154,48 +117,6 @@ def test_unsupported_codecs_fail_loudly():
 
 
 # ---- larger streams: every deflate/LZ4 structure the reference decoder accepts --
-def rw(n, seed=0):
-    return np.cumsum(np.random.default_rng(seed).integers(-3, 4, n)).astype("<i2")
-
-
-def quant_f32(seed=0):
-    i = np.arange(256)[:, None, None]
-    j = np.arange(256)[None, :, None]
-    k = np.arange(4)[None, None, :]
-    phi = seed * 7
-    v = np.round(64 * (100 * np.sin(0.05 * (i + phi)) * np.cos(0.03 * j) + k)) / 64
-    return v.astype("<f4").reshape(-1)
-
-
-def gzip_wrap(raw_deflate: bytes, payload: bytes, flags=0, extra=b"", name=b"", comment=b"",
-              hcrc=False):
-    h = bytearray([0x1f, 0x8b, 8, flags | (2 if hcrc else 0), 0, 0, 0, 0, 0, 255])
-    if flags & 4:
-        h += struct.pack("<H", len(extra)) + extra
-    if flags & 8:
-        h += name + b"\0"
-    if flags & 16:
-        h += comment + b"\0"
-    if hcrc:
-        h += struct.pack("<H", zlib.crc32(bytes(h)) & 0xFFFF)
-    tr = struct.pack("<II", zlib.crc32(payload), len(payload) & 0xFFFFFFFF)
-    return bytes(h) + raw_deflate + tr
-
-
-def deflate(payload, level=6, strategy=zlib.Z_DEFAULT_STRATEGY, mem=8, wbits=-15):
-    c = zlib.compressobj(level, zlib.DEFLATED, wbits, mem, strategy)
-    return c.compress(payload) + c.flush()
-
-
-DATASETS = {
-    "randwalk_i2": lambda: rw(524288).tobytes(),
-    "quant_f4": lambda: quant_f32(3).tobytes(),
-    "uniform_u1": lambda: np.random.default_rng(5).integers(0, 256, 1 << 20, dtype=np.uint8).tobytes(),
-    "zeros": lambda: bytes(1 << 20),
-    "text_like": lambda: (b"the quick brown fox jumps over the lazy dog %d\n" * 30000)[: 1 << 20],
-}
-
-
 @pytest.mark.parametrize("data", list(DATASETS))
 @pytest.mark.parametrize("variant", ["l1", "l6", "l9", "l0_stored", "huffman_only", "rle",
                                      "fixed", "flags_hdr"])
@@ -292,9 +213,6 @@ def test_lz4_skip_block_checksum_flag():
     checksum words are corrupt is InvalidData by default (LZ4F verifies them,
     as the oracle does) and decodes to the intact payload with the flag, on
     both block decoders."""
-    import torch
-    from zarr_amd._native import FLAG_SKIP_LZ4_BLOCK_CHECKSUM
-    from zarr_amd.batch import BatchCodec, PackedStreams
     payload = rw(300000).tobytes()
     s = zref.lz4_frame_custom(payload, block_checksum=True)
     # walk the blocks (7-byte header: magic, FLG, BD, HC) and corrupt every checksum word
@@ -311,15 +229,11 @@ def test_lz4_skip_block_checksum_flag():
     assert nblk >= 4
     st_ref, _ = zref.decode_batch(zref.LZ4, [np.frombuffer(bytes(bad), np.uint8)], len(payload))
     assert st_ref[0] == zref.INVALID_DATA
-    for lz4_sel in (0, 0x800, 0x1000):
+    for lz4_sel in (0, FLAG_LZ4_WAVE_PER_BLOCK, FLAG_LZ4_LANE_PER_BLOCK):
         for flags, want in ((0, zref.INVALID_DATA), (FLAG_SKIP_LZ4_BLOCK_CHECKSUM, zref.OK)):
-            packed = PackedStreams([bytes(bad)] * 3, len(payload), "cuda:0")
-            BatchCodec(0).decode(meta_for("lz4", "u1", len(payload)), packed, flags=flags | lz4_sel)
-            torch.cuda.synchronize()
-            st = packed.status.cpu().numpy()
+            st, out = decode("lz4", [bytes(bad)] * 3, "u1", len(payload), flags | lz4_sel)
             assert (st == want).all(), (lz4_sel, flags, st)
             if want == zref.OK:
-                out = packed.dst.cpu().numpy().reshape(3, len(payload))
                 assert all(out[i].tobytes() == payload for i in range(3))
 
 
@@ -339,7 +253,8 @@ def test_lz4_errors():
     check("lz4", bytes(bad), "u1", len(payload))
 
 
-@pytest.mark.parametrize("lz4_flags", [0, 0x1000, 0x800], ids=["default", "lane_per_block", "wave_per_block"])
+@pytest.mark.parametrize("lz4_flags", [0, FLAG_LZ4_LANE_PER_BLOCK, FLAG_LZ4_WAVE_PER_BLOCK],
+                         ids=["default", "lane_per_block", "wave_per_block"])
 def test_lz4_corruption_sweep(lz4_flags):
     """Byte corruptions and truncations of LZ4 frames everywhere (block
     headers, tokens, length bytes, offsets, literals, end mark, checksums),
@@ -466,44 +381,18 @@ def test_inflate_parallel_vs_serial_kernel(data):
 def test_decode_never_writes_past_n(codec):
     """read_exact stops at byte N even inside a long match: the bytes after
     N*elem_size in the caller's buffer stay untouched (chunk.rs:112-113)."""
-    import torch
     from zarr_amd._native import FLAG_INFLATE_BLOCK_PAR, FLAG_SERIAL_INFLATE
-    from zarr_amd.batch import BatchCodec, PackedStreams
     payloads = [bytes(300000), (b"abcdefgh" * 40000), rw(150000).tobytes()]
     streams = [zref.encode(CODEC_IDS[codec], DEFAULT_PARAM[codec], np.frombuffer(p, np.uint8))[1]
                for p in payloads]
-    guard = 4096
     for D in (1, 777, 16385, 65537, 99999, 200003):
         flag_sets = (0, FLAG_SERIAL_INFLATE, FLAG_INFLATE_BLOCK_PAR, FLAG_INFLATE_WAVE) if codec == "gzip" else (0,)
         for flags in flag_sets:
-            dst = torch.full((len(streams) * (D + guard),), 0xAB, dtype=torch.uint8, device="cuda:0")
-            packed = PackedStreams(streams, D + guard, "cuda:0", dst=dst)
-            BatchCodec(0).decode(meta_for(codec, "u1", D), packed, flags=flags)
-            torch.cuda.synchronize()
-            assert (packed.status.cpu().numpy() == 0).all()
-            out = dst.cpu().numpy().reshape(len(streams), D + guard)
+            st, out = decode(codec, streams, "u1", D, flags, guard=GUARD)
+            assert (st == 0).all()
             for i, p in enumerate(payloads):
                 assert out[i, :D].tobytes() == p[:D], (D, i)
                 assert (out[i, D:] == 0xAB).all(), (D, i, flags)
-
-
-def check_many(codec, streams, dt, n, flags=0, param=None):
-    """Batch decode of many streams; each result must classify and decode like
-    the oracle (one launch, so sweeps of corruptions stay fast)."""
-    import torch
-    from zarr_amd.batch import BatchCodec, PackedStreams
-    es, be, isb, _ = dtype_info(dt)
-    st_ref, out_ref = zref.decode_batch(CODEC_IDS[codec], [np.frombuffer(s, np.uint8) for s in streams],
-                                        n * es, elem_size=es, big_endian=be, is_bool=isb)
-    packed = PackedStreams(streams, n * es, "cuda:0")
-    BatchCodec(0).decode(meta_for(codec, dt, n, param), packed, flags=flags)
-    torch.cuda.synchronize()
-    st = packed.status.cpu().numpy()
-    out = packed.dst.cpu().numpy().reshape(len(streams), n * es)
-    for i in range(len(streams)):
-        assert KIND[int(st[i])] == KIND[int(st_ref[i])], (i, int(st[i]), int(st_ref[i]))
-        if st_ref[i] == zref.OK:
-            assert out[i].tobytes() == out_ref[i].tobytes(), i
 
 
 def test_gzip_dynamic_header_corruption():

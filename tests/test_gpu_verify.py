@@ -16,59 +16,23 @@ import numpy as np
 import pytest
 
 import zref
-from golden_util import CODEC_IDS, dtype_info
+from deflate_kit import PLAIN_HEADER, deflate, flip, member, noise, stored, text
+from golden_util import dtype_info
+from gpu_check import GUARD, check_many, decode, oracle
 from lz4_craft import xxh32
 from zarr_amd import ArrayMetadata, DefaultChunk, FilesystemHierarchy, Gzip, Lz4, SliceDataChunk, _native
 from zarr_amd.chunk import ZarrIOError, abi_array
 
 pytestmark = pytest.mark.gpu
 
-KIND = {zref.OK: "Ok", zref.EOF: "UnexpectedEof", zref.INVALID_DATA: "InvalidData"}
 VG, VL = _native.FLAG_VERIFY_GZIP_TRAILER, _native.FLAG_VERIFY_LZ4_CONTENT
 GZ_SETS = (0, _native.FLAG_SERIAL_INFLATE, _native.FLAG_INFLATE_BLOCK_PAR, _native.FLAG_INFLATE_WAVE)
 LZ_SETS = (0, _native.FLAG_LZ4_WAVE_PER_BLOCK, _native.FLAG_LZ4_LANE_PER_BLOCK)
-GUARD = 4096
-PLAIN_HEADER = bytes([0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 255])
 DTYPES = ["u1", ">u2", ">f4", ">u8", "bool"]
 OK, EOF, BAD = "Ok", "UnexpectedEof", "InvalidData"
 
 
-# ---- builders -----------------------------------------------------------------------------------
-def trailer(payload):
-    return struct.pack("<II", zlib.crc32(payload), len(payload) & 0xFFFFFFFF)
-
-
-def stored(data, last=False):
-    """One stored block (byte aligned: the header's 3 bits and 5 bits of padding)."""
-    return bytes([1 if last else 0]) + struct.pack("<HH", len(data), len(data) ^ 0xFFFF) + data
-
-
-def deflate(data, level=6, strategy=zlib.Z_DEFAULT_STRATEGY):
-    co = zlib.compressobj(level, zlib.DEFLATED, -15, 9, strategy)
-    return co.compress(data) + co.flush()
-
-
-def member(raw, payload, header=PLAIN_HEADER):
-    return header + raw + trailer(payload)
-
-
-def flip(b, i, bit=1):
-    return b[:i] + bytes([b[i] ^ bit]) + b[i + 1:]
-
-
-def text(n, seed):
-    rng = np.random.default_rng(seed)
-    words = [bytes(rng.integers(97, 123, int(rng.integers(2, 10))).astype(np.uint8)) for _ in range(300)]
-    p = 1.0 / (np.arange(300) + 1.0)
-    out = b" ".join(words[i] for i in rng.choice(300, size=n // 4 + 8, p=p / p.sum()))
-    assert len(out) >= n
-    return out[:n]
-
-
-def noise(n, seed, hi=256):
-    return np.random.default_rng(seed).integers(0, hi, n).astype(np.uint8).tobytes()
-
-
+# ---- builders (this file's streams: zlib at memLevel 9, text() with 8 spare words) ---------------
 def lz4_stored_frame(blocks, content_checksum=True, content_size=None, end_mark=True):
     """An LZ4 frame of stored (uncompressed) blocks, independent, 64 KiB block maximum."""
     flg = 0x60 | (0x04 if content_checksum else 0) | (0x08 if content_size is not None else 0)
@@ -102,47 +66,25 @@ def lz4_frame(payload):
 
 
 # ---- the check ----------------------------------------------------------------------------------
-def run(codec, streams, dt, n, flags):
-    import torch
-    from zarr_amd.batch import BatchCodec, PackedStreams
-    es = dtype_info(dt)[0]
-    D = n * es
-    meta = ArrayMetadata.new([n], [n], dt, Gzip(-1) if codec == "gzip" else Lz4(65536))
-    dst = torch.full((len(streams) * (D + GUARD),), 0xAB, dtype=torch.uint8, device="cuda:0")
-    packed = PackedStreams(streams, D + GUARD, "cuda:0", dst=dst)
-    BatchCodec(0).decode(meta, packed, flags=flags)
-    torch.cuda.synchronize()
-    return packed.status.cpu().numpy(), dst.cpu().numpy().reshape(len(streams), D + GUARD)
-
-
 def check_group(codec, cases, dt, n, flag_sets=None):
     """cases: [(stream, status without verification, status with)].  The oracle
     must give the first; every flag set OR-ed with the codec's verify flag the
     second (and the oracle's bytes for Ok chunks); the other codec's verify
     flag must change nothing against a plain decode."""
     streams = [c[0] for c in cases]
-    es, be, isb, _ = dtype_info(dt)
-    D = n * es
-    st_ref, out_ref = zref.decode_batch(CODEC_IDS[codec], [np.frombuffer(s, np.uint8) for s in streams],
-                                        D, elem_size=es, big_endian=be, is_bool=isb)
-    assert [KIND[int(x)] for x in st_ref] == [c[1] for c in cases], (n, dt, [KIND[int(x)] for x in st_ref])
+    ref = oracle(codec, streams, dt, n)
+    assert ref[0] == [c[1] for c in cases], (n, dt, ref[0])
     mine, other = (VG, VL) if codec == "gzip" else (VL, VG)
     sets = flag_sets if flag_sets is not None else (GZ_SETS if codec == "gzip" else LZ_SETS)
-    st0, out0 = run(codec, streams, dt, n, 0)
-    st1, out1 = run(codec, streams, dt, n, other)
+    st0, out0 = decode(codec, streams, dt, n, 0, guard=GUARD)
+    st1, out1 = decode(codec, streams, dt, n, other, guard=GUARD)
     assert st0.tolist() == st1.tolist() and out0.tobytes() == out1.tobytes(), (n, dt, st0.tolist(), st1.tolist())
-    for flags, want in [(f | mine, [c[2] for c in cases]) for f in sets]:
-        st, out = run(codec, streams, dt, n, flags)
-        for i in range(len(streams)):
-            assert KIND[int(st[i])] == want[i], (i, n, dt, hex(flags), int(st[i]), want[i])
-            if want[i] == OK:
-                assert out[i, :D].tobytes() == out_ref[i].tobytes(), (i, n, dt, hex(flags))
-            assert (out[i, D:] == 0xAB).all(), (i, n, dt, hex(flags))
+    check_many(codec, streams, dt, n, [f | mine for f in sets], guard=GUARD, expect=[c[2] for c in cases], ref=ref)
 
 
 def payload_for(dt, D, seed):
     # bool: bytes above 1 must come out as 1, and the CRC is of the bytes as stored
-    return noise(D, seed) if dt == "bool" else text(D, seed)
+    return noise(D, seed) if dt == "bool" else text(D, seed, spare=8)
 
 
 # ---- gzip ---------------------------------------------------------------------------------------
@@ -155,8 +97,8 @@ def test_gzip_valid_members(dt):
     for size in GZ_SIZES:
         n = (size + es - 1) // es if es > 1 and size > 17 else size
         p = payload_for(dt, n * es, 100 + size)
-        cases = [(member(deflate(p), p), OK, OK), (member(deflate(p, 0), p), OK, OK),
-                 (member(deflate(p, 6, zlib.Z_FIXED), p), OK, OK)]
+        cases = [(member(deflate(p, mem=9), p), OK, OK), (member(deflate(p, 0, mem=9), p), OK, OK),
+                 (member(deflate(p, 6, zlib.Z_FIXED, mem=9), p), OK, OK)]
         check_group("gzip", cases, dt, n)
 
 
@@ -165,15 +107,15 @@ def test_gzip_one_mib(dt):
     es = dtype_info(dt)[0]
     D = 1 << 20
     p = payload_for(dt, D, 7)
-    good = member(deflate(p), p)
-    bad = member(deflate(p), flip(p, D - 3))  # the trailer of another payload
+    good = member(deflate(p, mem=9), p)
+    bad = member(deflate(p, mem=9), flip(p, D - 3))  # the trailer of another payload
     check_group("gzip", [(good, OK, OK), (bad, OK, BAD)], dt, D // es)
 
 
 def fixed_literal_flip(payload):
     """A fixed-Huffman stream of `payload` with one bit flipped so that it still
     parses to the end and inflates to as many, but different, bytes."""
-    raw = deflate(payload, 6, zlib.Z_FIXED)
+    raw = deflate(payload, 6, zlib.Z_FIXED, mem=9)
     for bit in range(40, len(raw) * 8 - 40):
         cand = flip(raw, bit // 8, 1 << (bit % 8))
         d = zlib.decompressobj(-15)
@@ -199,10 +141,10 @@ def gzip_cases(n, seed):
     st_p = member(stored(p, True), p)
     empties = b"\x00\x00\x00\xff\xff" * 10000  # 50 000 bytes of empty stored blocks: past flate2's window
     sync = stored(p) + empties + stored(b"", True)
-    second = member(deflate(text(500, 3)), text(500, 3))
+    second = member(deflate(text(500, 3, spare=8), mem=9), text(500, 3, spare=8))
     cases = [
         (st_p, OK, OK),
-        (member(deflate(p), p), OK, OK),
+        (member(deflate(p, mem=9), p), OK, OK),
         (flip(st_p, 10 + 5 + n // 2), OK, BAD),                       # stored payload byte
         (member(fixed_literal_flip(p), p), OK, BAD),                  # fixed-Huffman literal
         (flip(st_p, len(st_p) - 8), OK, BAD),                         # CRC field
@@ -212,7 +154,7 @@ def gzip_cases(n, seed):
     cases += [(st_p[:-k], OK, EOF) for k in range(1, 9)]              # cut inside the trailer
     cases += [
         (member(stored(q[:n]) + stored(q[n:], True), q), OK, BAD),    # longer: n at a block boundary
-        (member(deflate(q, 6, zlib.Z_FIXED), q), OK, BAD),            # longer: Huffman tokens go on
+        (member(deflate(q, 6, zlib.Z_FIXED, mem=9), q), OK, BAD),     # longer: Huffman tokens go on
         (member(stored(q, True), q), OK, BAD),                        # longer: inside a stored block
         (member(sync, p), OK, OK),
         (flip(member(sync, p), 10 + 5 + 7), OK, BAD),
@@ -223,8 +165,8 @@ def gzip_cases(n, seed):
         (st_p[:10 + 5 + n // 2], EOF, EOF),                           # already short
         (PLAIN_HEADER + b"\x07" + st_p[11:], BAD, BAD),               # block type 3
         (b"\x1f\x8c" + st_p[2:], BAD, BAD),                           # bad magic
-        (member(deflate(p, 0), p), OK, OK),
-        (member(deflate(p, 9, zlib.Z_FIXED), p), OK, OK),
+        (member(deflate(p, 0, mem=9), p), OK, OK),
+        (member(deflate(p, 9, zlib.Z_FIXED, mem=9), p), OK, OK),
     ]
     return cases
 
@@ -232,9 +174,9 @@ def gzip_cases(n, seed):
 def test_gzip_mixed_batch_of_33():
     n = 3001
     cases = gzip_cases(n, 50)
-    p = text(n, 9)
+    p = text(n, 9, spare=8)
     while len(cases) < 33:
-        cases.append((member(deflate(p), p), OK, OK))
+        cases.append((member(deflate(p, mem=9), p), OK, OK))
     assert len(cases) == 33
     check_group("gzip", cases, "u1", n)
 
@@ -246,8 +188,8 @@ def test_gzip_cases_with_element_transform(dt):
 
 def test_gzip_output_fills_inside_a_match():
     p = b"\0" * 1000
-    m = member(deflate(p), p)
-    check_group("gzip", [(m, OK, BAD), (member(deflate(p[:100]), p[:100]), OK, OK)], "u1", 100)
+    m = member(deflate(p, mem=9), p)
+    check_group("gzip", [(m, OK, BAD), (member(deflate(p[:100], mem=9), p[:100]), OK, OK)], "u1", 100)
 
 
 # ---- LZ4 ----------------------------------------------------------------------------------------
@@ -274,8 +216,8 @@ def test_lz4_one_mib(dt):
 
 
 def lz4_cases(n, seed):
-    p = text(n, seed)
-    q = text(n + 100, seed + 1)
+    p = text(n, seed, spare=8)
+    q = text(n + 100, seed + 1, spare=8)
     f = lz4_frame(p)
     r = noise(n, seed + 2)
     cases = [
@@ -302,7 +244,7 @@ def lz4_cases(n, seed):
 def test_lz4_mixed_batch_of_33():
     n = 3001
     cases = lz4_cases(n, 70)
-    p = text(n, 10)
+    p = text(n, 10, spare=8)
     while len(cases) < 33:
         cases.append((lz4_frame(p), OK, OK))
     assert len(cases) == 33
@@ -316,7 +258,7 @@ def test_lz4_cases_with_element_transform(dt):
 
 def test_lz4_linked_block_frame():
     n = 70000  # two linked blocks: the serial path
-    p = text(n // 2, 90)
+    p = text(n // 2, 90, spare=8)
     linked = zref.lz4_frame_custom(p + p, linked=True, content_checksum=True)
     assert linked[4] & 0x20 == 0
     bad = flip_first_literal(linked)
@@ -325,7 +267,7 @@ def test_lz4_linked_block_frame():
 
 # ---- entry points -------------------------------------------------------------------------------
 def test_read_chunk_flag():
-    p = text(4000, 5)
+    p = text(4000, 5, spare=8)
     good = member(stored(p, True), p)
     bad = flip(good, 100)
     meta = ArrayMetadata.new([4000], [4000], "u1", Gzip(-1))
@@ -376,8 +318,8 @@ def test_workspace_and_fresh_stream(codec):
         plain = lib.zcg_workspace_bytes(ctypes.byref(abi_array(meta, extra)), 40, 0)
         ver = lib.zcg_workspace_bytes(ctypes.byref(abi_array(meta, extra | _native.FLAG_VERIFY)), 40, 0)
         assert ver >= plain and ver > 0
-    p = text(n, 12)
-    good = member(deflate(p), p) if codec == "gzip" else lz4_frame(p)
+    p = text(n, 12, spare=8)
+    good = member(deflate(p, mem=9), p) if codec == "gzip" else lz4_frame(p)
     bad = flip(good, len(good) - 1)
     s = torch.cuda.Stream()
     for flags in (_native.FLAG_SERIAL_INFLATE | _native.FLAG_VERIFY, _native.FLAG_VERIFY):
@@ -397,8 +339,8 @@ def test_capture_and_replay(codec):
     n = 20000
     dt = ">u2"
     meta = ArrayMetadata.new([n // 2], [n // 2], dt, Gzip(-1) if codec == "gzip" else Lz4(65536))
-    p, q = text(n, 13), text(n, 14)
-    mk = (lambda x: member(deflate(x), x)) if codec == "gzip" else lz4_frame
+    p, q = text(n, 13, spare=8), text(n, 14, spare=8)
+    mk = (lambda x: member(deflate(x, mem=9), x)) if codec == "gzip" else lz4_frame
     streams = [mk(p), flip(mk(q), len(mk(q)) - 1), mk(q), mk(p)[:-2]]
     want = [zref.OK, zref.INVALID_DATA, zref.OK, zref.EOF]
     packed = PackedStreams(streams, n, "cuda:0")

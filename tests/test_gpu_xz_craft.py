@@ -51,59 +51,27 @@ constant of zcg_xz.hip or a rule of zcg_xz_core.h changes):
 Nothing here is meant to fault: the invalid cases are streams the decoder's
 own checks reject with a status.
 """
-import functools
-
 import numpy as np
 import pytest
 
 import xz_cases as cs
-import zref
 from golden_util import dtype_info
-from zarr_amd import ArrayMetadata
-from zarr_amd.compression import Xz
+from gpu_check import GUARD, check_many
+from zarr_amd._native import FLAG_XZ_RING_32K as RING_32K
 
 pytestmark = pytest.mark.gpu
 
-KIND = {zref.OK: "ok", zref.EOF: "eof", zref.INVALID_DATA: "invalid"}
-RING_32K = 0x400
 FLAGS = [0, RING_32K]
 FLAG_IDS = ["ring4k", "ring32k"]
-GUARD = 4096
-
-
-def decode(streams, D, dt, flags):
-    import torch
-    from zarr_amd.batch import BatchCodec, PackedStreams
-    es = dtype_info(dt)[0]
-    meta = ArrayMetadata.new([D // es], [D // es], dt, Xz(6))
-    dst = torch.full((len(streams) * (D + GUARD),), 0xAB, dtype=torch.uint8, device="cuda:0")
-    packed = PackedStreams(streams, D + GUARD, "cuda:0", dst=dst)
-    BatchCodec(0).decode(meta, packed, flags=flags)
-    torch.cuda.synchronize()
-    return packed.status.cpu().numpy(), dst.cpu().numpy().reshape(len(streams), D + GUARD)
-
-
-@functools.lru_cache(maxsize=None)
-def reference(streams, D, dt):
-    """The oracle's (kinds, bytes) of a batch, computed once."""
-    es, be, isb, _ = dtype_info(dt)
-    st, out = zref.decode_batch(zref.XZ, [np.frombuffer(s, np.uint8) for s in streams], D, elem_size=es,
-                                big_endian=be, is_bool=isb)
-    return [KIND[int(x)] for x in st], [o.tobytes() for o in out]
 
 
 def check(cases, D, flags, dt="u1"):
-    """One batch under one flag set: statuses, bytes and guards."""
-    streams = tuple(c.frame for c in cases)
-    assert D % dtype_info(dt)[0] == 0 and all(c.D == D for c in cases)
-    kinds, outs = reference(streams, D, dt)
-    assert kinds == [c.want for c in cases]
-    st, out = decode(streams, D, dt, flags)
-    for i, c in enumerate(cases):
-        assert KIND.get(int(st[i]), int(st[i])) == kinds[i], (c.name, D, dt, hex(flags), int(st[i]), kinds[i])
-        if kinds[i] == "ok":
-            assert out[i, :D].tobytes() == outs[i], (c.name, D, dt, hex(flags))
-        assert (out[i, D:] == 0xAB).all(), (c.name, D, dt, hex(flags))
+    """One batch under one flag set: statuses, bytes and guards (the oracle is
+    asked once per batch and must give the kinds the table names)."""
+    es = dtype_info(dt)[0]
+    assert D % es == 0 and all(c.D == D for c in cases)
+    check_many("xz", [c.frame for c in cases], dt, D // es, flags, guard=GUARD, want=[c.want for c in cases],
+               names=[c.name for c in cases], cache=True)
 
 
 def family_batches(family):

@@ -6,13 +6,10 @@ import lzma
 import numpy as np
 import pytest
 
-from zarr_amd import ArrayMetadata
-from zarr_amd.batch import BatchCodec, PackedStreams
-from zarr_amd.compression import Xz
+from gpu_check import decode
+from zarr_amd._native import FLAG_XZ_RING_32K
 
 pytestmark = pytest.mark.gpu
-
-FLAG_RING_32K = 0x400
 
 
 def _data(kind, n, seed):
@@ -31,15 +28,6 @@ def _data(kind, n, seed):
     return (np.cumsum(rng.integers(-2, 3, n)) % 97).astype(np.uint8)
 
 
-def _decode(streams, D, flags):
-    import torch
-    meta = ArrayMetadata.new([D * len(streams)], [D], "u1", Xz(6))
-    packed = PackedStreams(streams, D, "cuda:0")
-    BatchCodec(0).decode(meta, packed, flags=flags)
-    torch.cuda.synchronize()
-    return packed.status.cpu().numpy(), packed.dst.view(len(streams), -1).cpu().numpy()
-
-
 @pytest.mark.parametrize("kind", ["far", "walk"])
 @pytest.mark.parametrize("check", [lzma.CHECK_CRC64, lzma.CHECK_CRC32, lzma.CHECK_NONE])
 def test_ring_32k_matches_default(kind, check):
@@ -47,8 +35,8 @@ def test_ring_32k_matches_default(kind, check):
     datas = [_data(kind, D, s) for s in range(4)]
     streams = [lzma.compress(d.tobytes(), format=lzma.FORMAT_XZ, check=check, preset=6) for d in datas]
     streams.append(streams[0][: len(streams[0]) // 2])  # truncated -> UnexpectedEof
-    s0, o0 = _decode(streams, D, 0)
-    s1, o1 = _decode(streams, D, FLAG_RING_32K)
+    s0, o0 = decode("xz", streams, "u1", D, 0)
+    s1, o1 = decode("xz", streams, "u1", D, FLAG_XZ_RING_32K)
     assert s0.tolist() == s1.tolist()
     assert s0[:4].tolist() == [0, 0, 0, 0] and s0[4] == 1
     for i in range(4):

@@ -29,9 +29,9 @@ import pytest
 import xz_cases as cs
 import xz_craft as xc
 import zref
+from gpu_check import KIND, SHORT
 from test_hostcore import host, host_xz
 
-KIND = {zref.OK: "ok", zref.EOF: "eof", zref.INVALID_DATA: "invalid"}
 FAMILIES = "A B C D E F G H".split()
 
 
@@ -58,12 +58,12 @@ def test_cases_against_oracle_model_and_host_core(family):
         for c, s, o in zip(cases, st, out):
             seen += 1
             kind = KIND[int(s)]
-            assert kind == c.want, (c.name, D, kind, c.want)
+            assert kind == SHORT[c.want], (c.name, D, kind, c.want)
             hs, ho = host_xz(c.frame, D)
             assert hs == int(s), (c.name, D, hs, int(s))
             cs_, co, bad = host_xz_checked(c.frame, D)
             assert (cs_, bad) == (int(s), 0), (c.name, D, cs_, bad)
-            if kind != "ok":
+            if kind != "Ok":
                 continue
             assert ho == o.tobytes() and co == ho, c.name
             if c.exact:

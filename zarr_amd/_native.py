@@ -26,6 +26,7 @@ FLAG_VERIFY = FLAG_VERIFY_GZIP_TRAILER | FLAG_VERIFY_LZ4_CONTENT
 FLAG_SKIP_LZ4_BLOCK_CHECKSUM = 0x4
 FLAG_SERIAL_INFLATE = 0x100
 FLAG_DEBUG_COUNTERS = 0x200
+FLAG_XZ_RING_32K = 0x400
 FLAG_LZ4_WAVE_PER_BLOCK = 0x800
 FLAG_LZ4_LANE_PER_BLOCK = 0x1000
 FLAG_INFLATE_BLOCK_PAR = 0x2000
