@@ -176,6 +176,58 @@ def bwt(t: bytes) -> Tuple[bytes, int]:
     return a[(sa - 1) % n].tobytes(), int(np.flatnonzero(sa == 0)[0])
 
 
+def rotation_ranks(t: bytes) -> List[Tuple[int, np.ndarray]]:
+    """[(k, rank)] for k = 1, 2, 4, ...: rank[i] orders rotation i by its
+    first k bytes (cyclic), equal prefixes share a rank.  The list ends once
+    all ranks differ or k >= len(t): the last entry is the order of the
+    whole rotations, equal rotations still sharing a rank."""
+    a = np.frombuffer(t, np.uint8)
+    n = len(a)
+    assert n > 0
+    idx = np.arange(n)
+    rank = np.unique(a, return_inverse=True)[1].reshape(-1).astype(np.int64)
+    k = 1
+    out = [(1, rank)]
+    while int(rank.max()) + 1 < n and k < n:
+        m = int(rank.max()) + 1
+        rank = np.unique(rank * m + rank[(idx + k) % n], return_inverse=True)[1].reshape(-1).astype(np.int64)
+        k *= 2
+        out.append((k, rank))
+    return out
+
+
+def prefix_group_sizes(t: bytes, dpre: int) -> np.ndarray:
+    """Sizes of the groups of rotations of t that share their first dpre
+    bytes (cyclic), in sorted order of the prefix."""
+    a = np.frombuffer(t, np.uint8).astype(np.int64)
+    idx = np.arange(len(a))
+    key = np.zeros(len(a), np.int64)
+    for d in range(dpre):
+        key = key * 256 + a[(idx + d) % len(a)]
+    return np.unique(key, return_counts=True)[1]
+
+
+def adjacent_lcp(t: bytes, cap: Optional[int] = None, levels=None) -> np.ndarray:
+    """Common prefix length (cyclic, at most len(t) or cap) of each pair of
+    neighbours among the sorted rotations of t: len(t) - 1 values.  `levels`
+    is rotation_ranks(t), for a caller that has it."""
+    n = len(t)
+    levels = rotation_ranks(t) if levels is None else levels
+    sa = np.argsort(levels[-1][1], kind="stable")
+    x, y = sa[:-1], sa[1:]
+    lcp = np.zeros(n - 1, np.int64)
+    for k, rank in reversed(levels):
+        lcp += k * (rank[(x + lcp) % n] == rank[(y + lcp) % n])
+    return np.minimum(lcp, n if cap is None else min(n, cap))
+
+
+def orig_range(t: bytes) -> Tuple[int, int]:
+    """(first, count): the positions, among the sorted rotations of t, of
+    the rotations equal to t itself; count is 1 unless t is periodic."""
+    rank = rotation_ranks(t)[-1][1]
+    return int((rank < rank[0]).sum()), int((rank == rank[0]).sum())
+
+
 def is_one_cycle(L: bytes, orig: int) -> bool:
     """Whether the inverse-BWT links of L form a single cycle (what a real
     BWT of an aperiodic block gives)."""
