@@ -1,13 +1,17 @@
 """What the GPU decode-parity tests share: the payloads, the one-chunk check
 through read_chunk, and the batch check (pack the streams, one launch per flag
-set, compare every chunk with the oracle).  Every expected output comes from
+set, compare every chunk with the oracle); and what the encode tests share:
+one encode call over a batch, and the check of a gzip member against zlib.  Every expected output comes from
 the oracle (oracle/zref.c over the reference's own C codec libraries).
 """
 import functools
+import struct
+import zlib
 
 import numpy as np
 
 import zref
+from deflate_kit import deflate, first_difference
 from golden_util import CODEC_IDS, DEFAULT_PARAM, dtype_info
 from zarr_amd import ArrayMetadata, DefaultChunk, Gzip, Lz4, Raw, ZarrIOError, _native
 from zarr_amd.compression import Bzip2, Xz
@@ -129,3 +133,52 @@ def check_many(codec, streams, dt, n, flags=0, param=None, guard=0, want=None, e
                 assert out[i, :D].tobytes() == outs[i], at
             assert (out[i, D:] == 0xAB).all(), at
     return kinds
+
+
+# ---- encode: one zcg_encode_batch call, and the gzip member check ---------------------------------
+def encode_batch(meta, arrays, cap_extra=0):
+    """zcg_encode_batch over device buffers; returns (status, [bytes])."""
+    import torch
+    from zarr_amd.batch import BatchCodec, make_encode_batch
+    codec = BatchCodec(0)
+    D = arrays[0].nbytes
+    n = len(arrays)
+    host = np.concatenate([a.view(np.uint8).reshape(-1) for a in arrays]) if D else np.zeros(1, np.uint8)
+    elems = torch.from_numpy(host).to("cuda:0")
+    cap = codec.encode_bound(meta, D) + cap_extra
+    desc, dst, out_len, status = make_encode_batch(elems, n, cap, "cuda:0") if D else (None,) * 4
+    if not D:  # zero-byte chunks: descriptors by hand
+        desc, dst, out_len, status = make_encode_batch(torch.zeros(n, dtype=torch.uint8, device="cuda:0"),
+                                                       n, cap, "cuda:0")
+        d = desc.cpu().numpy().view(np.uint64).reshape(n, 4).copy()
+        d[:, 1] = 0
+        desc = torch.from_numpy(d.view(np.int64)).to("cuda:0")
+    codec.encode(meta, desc, n, out_len, status)
+    torch.cuda.synchronize()
+    st = status.cpu().numpy()
+    ol = out_len.cpu().numpy()
+    buf = dst.cpu().numpy().reshape(n, cap)
+    return st, [buf[i, : ol[i]].tobytes() for i in range(n)]
+
+
+def zlib_raw(content: bytes, level: int) -> bytes:
+    """flate2's deflate body: zlib raw deflate, windowBits -15, memLevel 8, default strategy."""
+    return deflate(content, level)
+
+
+def check_gzip_member(stream: bytes, content: bytes, level: int, exact=None):
+    eff = 6 if (level < 0 or level > 9) else level
+    xfl = 2 if eff >= 9 else (4 if eff <= 1 else 0)
+    assert stream[:10] == bytes([0x1F, 0x8B, 8, 0, 0, 0, 0, 0, xfl, 255])
+    crc, isize = struct.unpack_from("<II", stream, len(stream) - 8)
+    assert crc == zlib.crc32(content) and isize == len(content) & 0xFFFFFFFF
+    d = zlib.decompressobj(-15)
+    assert d.decompress(stream[10:-8]) == content and d.eof and not d.unused_data
+    if exact if exact is not None else eff >= 1:
+        # levels 1-9: byte-identical to zlib (gzip.rs:54-56 -> flate2 -> zlib deflate_fast / deflate_slow)
+        ref = zlib_raw(content, eff)
+        body = stream[10:-8]
+        if body != ref:
+            k = next((i for i in range(min(len(body), len(ref))) if body[i] != ref[i]), min(len(body), len(ref)))
+            raise AssertionError(f"gzip level {eff}: deflate body differs from zlib's at byte {k} "
+                                 f"(len {len(body)} vs {len(ref)}): {first_difference(body, ref)}")

@@ -50,10 +50,15 @@ struct FastTab {
     }
 };
 
+// What zz_host_report_blocks returns per block (ZZ_BLOCK_WORDS u32 each)
+constexpr uint32_t ZZ_BLOCK_WORDS = 13;
 static int64_t emit_blocks(const uint8_t* src, const std::vector<uint32_t>& syms,
-                           const std::vector<zz::BlockRec>& blocks, uint8_t* out, uint64_t cap);
+                           const std::vector<zz::BlockRec>& blocks, uint8_t* out, uint64_t cap,
+                           uint32_t* report = nullptr);
 
-extern "C" int64_t zz_host_deflate(const uint8_t* src, uint32_t D, int level, uint8_t* out, uint64_t cap) {
+// The serial model's symbols and block records of one chunk (levels 1-9)
+static void serial_parse(const uint8_t* src, uint32_t D, int level, std::vector<uint32_t>& syms,
+                         std::vector<zz::BlockRec>& blocks) {
     using namespace zz;
     const Config cfg = level_config(level);
     if (level >= 1 && level <= 3) {  // deflate_fast: the parse builds its chains
@@ -64,14 +69,13 @@ extern "C" int64_t zz_host_deflate(const uint8_t* src, uint32_t D, int level, ui
             return v;
         };
         FastTab tab;
-        std::vector<uint32_t> syms, pos;
+        std::vector<uint32_t> pos;
         auto emit = [&](uint32_t s, uint32_t at) { syms.push_back(s); pos.push_back(at); };
         const uint32_t nsym = parse_fast(D, cfg, tab, byte4, byte, emit);
-        std::vector<BlockRec> blocks;
         auto P = [&](uint32_t i) -> uint32_t { return pos[i]; };
         auto Y = [&](uint32_t i) -> uint32_t { return syms[i]; };
         for (uint32_t k = 0; k < num_blocks(nsym); k++) blocks.push_back(block_rec(k, nsym, nsym, D, P, Y, true));
-        return emit_blocks(src, syms, blocks, out, cap);
+        return;
     }
     std::vector<uint32_t> prev(D ? D : 1, NONE), head(1u << 15, NONE);
     for (uint32_t p = 0; p + MIN_MATCH <= D; p++) {
@@ -88,17 +92,56 @@ extern "C" int64_t zz_host_deflate(const uint8_t* src, uint32_t D, int level, ui
     auto pr = [&](uint32_t i) -> uint32_t { return prev[i]; };
     std::vector<Match2> g(D ? D : 1);
     for (uint32_t p = 0; p < D; p++) g[p] = search(p, D, cfg, byte4, byte, pr);
-    std::vector<uint32_t> syms;
-    std::vector<BlockRec> blocks;
     auto get = [&](uint32_t p) -> Match2 { return g[p]; };
     auto emit = [&](uint32_t, uint32_t s) { syms.push_back(s); };
     auto flush = [&](const BlockRec& b) { blocks.push_back(b); };
     parse(D, cfg, get, byte, emit, flush);
+}
+
+extern "C" int64_t zz_host_deflate(const uint8_t* src, uint32_t D, int level, uint8_t* out, uint64_t cap) {
+    std::vector<uint32_t> syms;
+    std::vector<zz::BlockRec> blocks;
+    serial_parse(src, D, level, syms, blocks);
     return emit_blocks(src, syms, blocks, out, cap);
 }
 
+// Whether gen_bitlen had to limit this tree's lengths, read from what
+// build_tree leaves behind: a leaf whose path to the root over dad[] is longer
+// than max_length.  (Leaves are the nodes below `elems` with a frequency, the
+// forced ones included; internal nodes are numbered from `elems` up, the root
+// last.)
+template <class Tree>
+static uint32_t tree_limited(const Tree& t, int elems, int max_length) {
+    int leaves = 0;
+    for (int n = 0; n < elems; n++) leaves += t.freq[n] != 0;
+    const int root = elems + leaves - 2;
+    for (int n = 0; n < elems; n++) {
+        if (!t.freq[n]) continue;
+        int depth = 0;
+        for (int m = n; m != root; m = t.dad[m]) depth++;
+        if (depth > max_length) return 1;
+    }
+    return 0;
+}
+
+// The serial model's path through one chunk, as plain integers: per block
+// s0, s1, b0, b1, in_win, last, type, opt_lenb, static_lenb, max_blindex and
+// whether the literal/length, distance and code-length trees were
+// length-limited.  Returns the block count (blocks past cap_blocks are not
+// written).
+extern "C" int32_t zz_host_report_blocks(const uint8_t* src, uint32_t D, int level, uint32_t* out,
+                                         uint32_t cap_blocks) {
+    std::vector<uint32_t> syms;
+    std::vector<zz::BlockRec> blocks;
+    serial_parse(src, D, level, syms, blocks);
+    if (blocks.size() > cap_blocks) blocks.resize(cap_blocks);
+    std::vector<uint8_t> sink(D + D / 8 + 1024);
+    emit_blocks(src, syms, blocks, sink.data(), sink.size(), out);
+    return (int32_t)blocks.size();
+}
+
 static int64_t emit_blocks(const uint8_t* src, const std::vector<uint32_t>& syms,
-                           const std::vector<zz::BlockRec>& blocks, uint8_t* out, uint64_t cap) {
+                           const std::vector<zz::BlockRec>& blocks, uint8_t* out, uint64_t cap, uint32_t* report) {
     using namespace zz;
     BitOut bo{out, cap};
     BlockWork* bw = new BlockWork;
@@ -116,6 +159,15 @@ static int64_t emit_blocks(const uint8_t* src, const std::vector<uint32_t>& syms
         }
         bw->lt.freq[END_BLOCK] = 1;
         const BlockPlan pl = plan_block(*bw, b.b1 - b.b0, b.in_win != 0);
+        if (report) {
+            const uint32_t r[ZZ_BLOCK_WORDS] = {b.s0, b.s1, b.b0, b.b1, b.in_win, b.last, pl.type,
+                                                (uint32_t)((pl.opt_len + 10) >> 3), (uint32_t)((pl.static_len + 10) >> 3),
+                                                pl.max_blindex, tree_limited(bw->lt, L_CODES, MAX_BITS),
+                                                tree_limited(bw->dt, D_CODES, MAX_BITS),
+                                                tree_limited(bw->bt, BL_CODES, MAX_BL_BITS)};
+            memcpy(report, r, sizeof r);
+            report += ZZ_BLOCK_WORDS;
+        }
         auto put = [&](uint32_t v, uint32_t n) { bo.put(v, n); };
         send_header(*bw, pl, b.last != 0, put);
         if (pl.type == BT_STORED) {
@@ -144,9 +196,17 @@ static int64_t emit_blocks(const uint8_t* src, const std::vector<uint32_t>& syms
 // until it reaches a canonical loop top the next segments' parses marked
 // (pass 2), the true path stitched through the sync points, blocks cut by
 // zz::block_rec.  Must equal zlib byte for byte for any `seg`.
-extern "C" int64_t zz_host_deflate_seg(const uint8_t* src, uint32_t D, int level, uint32_t seg, uint8_t* out,
-                                       uint64_t cap) {
+struct SegParse {
+    uint32_t nseg = 0, fin_src = 0, fallback = 0;  // fin_src: 0 none, 1 the last segment's pass 1, 2 a tail that ran to D
+    std::vector<uint32_t> n1, nt, sync_q, into;    // per segment (sync_q NONE: the tail ran to D or the segment is the last)
+    std::vector<uint32_t> syms, pos;               // the stitched stream
+};
+// `tailcap`: the kernel's DZ_TAILCAP, for the fallback flag alone (a tail that
+// must take a step with tailcap - 1 symbols stored sends the chunk to the
+// serial parse there; the model's tails go on, so the stitch is always there)
+static SegParse seg_parse(const uint8_t* src, uint32_t D, int level, uint32_t seg, uint32_t tailcap) {
     using namespace zz;
+    SegParse R;
     const Config cfg = level_config(level);
     std::vector<uint32_t> prev(D ? D : 1, NONE), head(1u << 15, NONE);
     for (uint32_t p = 0; p + MIN_MATCH <= D; p++) {
@@ -201,17 +261,26 @@ extern "C" int64_t zz_host_deflate_seg(const uint8_t* src, uint32_t D, int level
                 sync_q[k] = st.p;
                 break;
             }
+            if (ty[k].size() + 1 >= tailcap) R.fallback = 1;
             step(st, D, cfg, get, byte, em);
         }
     }
-    std::vector<uint32_t> syms, pos;
-    bool finlit = false;
+    std::vector<uint32_t>& syms = R.syms;
+    std::vector<uint32_t>& pos = R.pos;
+    R.nseg = nseg;
+    R.into.assign(nseg, NONE);
+    R.sync_q = sync_q;
+    for (uint32_t k = 0; k < nseg; k++) {
+        R.n1.push_back((uint32_t)sy[k].size());
+        R.nt.push_back((uint32_t)ty[k].size());
+        if (sync_q[k] != NONE) R.into[k] = sync_q[k] / seg;
+    }
     uint32_t cur = 0, idx = 0;
     while (true) {
         for (uint32_t i = idx; i < sy[cur].size(); i++) { syms.push_back(sy[cur][i]); pos.push_back(ps[cur][i]); }
-        if (cur + 1 == nseg) { finlit = fin_lit[cur]; break; }
+        if (cur + 1 == nseg) { R.fin_src = fin_lit[cur] ? 1u : 0u; break; }
         for (uint32_t i = 0; i < ty[cur].size(); i++) { syms.push_back(ty[cur][i]); pos.push_back(tp[cur][i]); }
-        if (sync_q[cur] == NONE) { finlit = tail_fin[cur]; break; }
+        if (sync_q[cur] == NONE) { R.fin_src = tail_fin[cur] ? 2u : 0u; break; }
         const uint32_t q = sync_q[cur];
         const uint32_t nx = q / seg;
         uint32_t j = 0;
@@ -219,6 +288,51 @@ extern "C" int64_t zz_host_deflate_seg(const uint8_t* src, uint32_t D, int level
         cur = nx;
         idx = j;
     }
+    return R;
+}
+
+// The segment emulation's path: head[0..3] = nseg, final-literal source
+// (0 none, 1 last segment, 2 a tail), fallback flag, stitched symbol count;
+// per segment (4 u32 each, up to cap_seg segments): pass-1 symbols, tail
+// symbols, sync position (NONE: ran to D), segment synced into (NONE).
+extern "C" int32_t zz_host_report_seg(const uint8_t* src, uint32_t D, int level, uint32_t seg, uint32_t tailcap,
+                                      uint32_t* head, uint32_t* per_seg, uint32_t cap_seg) {
+    const SegParse R = seg_parse(src, D, level, seg, tailcap);
+    head[0] = R.nseg, head[1] = R.fin_src, head[2] = R.fallback, head[3] = (uint32_t)R.syms.size();
+    for (uint32_t k = 0; k < R.nseg && k < cap_seg; k++) {
+        per_seg[4 * k] = R.n1[k], per_seg[4 * k + 1] = R.nt[k];
+        per_seg[4 * k + 2] = R.sync_q[k], per_seg[4 * k + 3] = R.into[k];
+    }
+    return (int32_t)R.nseg;
+}
+
+// The block records zz::block_rec cuts from the stitched stream (what the GPU
+// parse kernels store): s0, s1, b0, b1, in_win, last per block, 6 u32 each.
+// The serial parse of zz_host_report_blocks tracks the window slides itself,
+// so the two agree only if block_rec's flush top is right.
+extern "C" int32_t zz_host_report_seg_blocks(const uint8_t* src, uint32_t D, int level, uint32_t seg, uint32_t* out,
+                                             uint32_t cap_blocks) {
+    using namespace zz;
+    const SegParse R = seg_parse(src, D, level, seg, NONE);
+    const uint32_t nsym = (uint32_t)R.syms.size(), nloop = nsym - (R.fin_src ? 1u : 0u);
+    auto P = [&](uint32_t i) { return R.pos[i]; };
+    auto Y = [&](uint32_t i) { return R.syms[i]; };
+    const uint32_t nb = num_blocks(nloop);
+    for (uint32_t k = 0; k < nb && k < cap_blocks; k++) {
+        const BlockRec b = block_rec(k, nsym, nloop, D, P, Y);
+        const uint32_t r[6] = {b.s0, b.s1, b.b0, b.b1, b.in_win, b.last};
+        memcpy(out + 6 * k, r, sizeof r);
+    }
+    return (int32_t)nb;
+}
+
+extern "C" int64_t zz_host_deflate_seg(const uint8_t* src, uint32_t D, int level, uint32_t seg, uint8_t* out,
+                                       uint64_t cap) {
+    using namespace zz;
+    const SegParse R = seg_parse(src, D, level, seg, NONE);
+    const std::vector<uint32_t>& syms = R.syms;
+    const std::vector<uint32_t>& pos = R.pos;
+    const bool finlit = R.fin_src != 0;
     const uint32_t nsym = (uint32_t)syms.size(), nloop = nsym - (finlit ? 1u : 0u);
     auto P = [&](uint32_t i) { return pos[i]; };
     auto Y = [&](uint32_t i) { return syms[i]; };

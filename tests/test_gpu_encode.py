@@ -25,6 +25,8 @@ pytestmark = pytest.mark.gpu
 
 zref = pytest.importorskip("zref")
 
+from gpu_check import check_gzip_member, encode_batch, zlib_raw  # noqa: E402,F401
+
 
 def xxh32(b: bytes) -> int:
     import xxhash
@@ -36,31 +38,6 @@ def serialised(data: np.ndarray, dt: str) -> bytes:
     if dt == "bool":
         return data.astype(np.uint8).tobytes()
     return data.astype(np.dtype(dt)).tobytes()
-
-
-def encode_batch(meta, arrays, cap_extra=0):
-    """zcg_encode_batch over device buffers; returns (status, [bytes])."""
-    import torch
-    from zarr_amd.batch import BatchCodec, make_encode_batch
-    codec = BatchCodec(0)
-    D = arrays[0].nbytes
-    n = len(arrays)
-    host = np.concatenate([a.view(np.uint8).reshape(-1) for a in arrays]) if D else np.zeros(1, np.uint8)
-    elems = torch.from_numpy(host).to("cuda:0")
-    cap = codec.encode_bound(meta, D) + cap_extra
-    desc, dst, out_len, status = make_encode_batch(elems, n, cap, "cuda:0") if D else (None,) * 4
-    if not D:  # zero-byte chunks: descriptors by hand
-        desc, dst, out_len, status = make_encode_batch(torch.zeros(n, dtype=torch.uint8, device="cuda:0"),
-                                                       n, cap, "cuda:0")
-        d = desc.cpu().numpy().view(np.uint64).reshape(n, 4).copy()
-        d[:, 1] = 0
-        desc = torch.from_numpy(d.view(np.int64)).to("cuda:0")
-    codec.encode(meta, desc, n, out_len, status)
-    torch.cuda.synchronize()
-    st = status.cpu().numpy()
-    ol = out_len.cpu().numpy()
-    buf = dst.cpu().numpy().reshape(n, cap)
-    return st, [buf[i, : ol[i]].tobytes() for i in range(n)]
 
 
 def check_lz4_frame(stream: bytes, content: bytes, block_size: int):
@@ -194,30 +171,6 @@ def test_lz4_encode_errors():
 import zlib  # noqa: E402
 
 from zarr_amd import Gzip  # noqa: E402
-
-
-def zlib_raw(content: bytes, level: int) -> bytes:
-    """flate2's deflate body: zlib raw deflate, windowBits -15, memLevel 8, default strategy."""
-    c = zlib.compressobj(level, zlib.DEFLATED, -15, 8, zlib.Z_DEFAULT_STRATEGY)
-    return c.compress(content) + c.flush()
-
-
-def check_gzip_member(stream: bytes, content: bytes, level: int, exact=None):
-    eff = 6 if (level < 0 or level > 9) else level
-    xfl = 2 if eff >= 9 else (4 if eff <= 1 else 0)
-    assert stream[:10] == bytes([0x1F, 0x8B, 8, 0, 0, 0, 0, 0, xfl, 255])
-    crc, isize = struct.unpack_from("<II", stream, len(stream) - 8)
-    assert crc == zlib.crc32(content) and isize == len(content) & 0xFFFFFFFF
-    d = zlib.decompressobj(-15)
-    assert d.decompress(stream[10:-8]) == content and d.eof and not d.unused_data
-    if exact if exact is not None else eff >= 1:
-        # levels 1-9: byte-identical to zlib (gzip.rs:54-56 -> flate2 -> zlib deflate_fast / deflate_slow)
-        ref = zlib_raw(content, eff)
-        body = stream[10:-8]
-        if body != ref:
-            k = next((i for i in range(min(len(body), len(ref))) if body[i] != ref[i]), min(len(body), len(ref)))
-            raise AssertionError(f"gzip level {eff}: deflate body differs from zlib's at byte {k} "
-                                 f"(len {len(body)} vs {len(ref)})")
 
 
 def test_gzip_encode_doc_spec_exact():

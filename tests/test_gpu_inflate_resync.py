@@ -18,8 +18,8 @@ import zlib
 import numpy as np
 import pytest
 
-from deflate_kit import (DIST_EXTRA, LEN_EXTRA, Bits, _skewed_with_copies, _three_symbols, block_header, canon, deflate,
-                         gzip_wrap, sym)
+from deflate_kit import (Bits, _skewed_with_copies, _three_symbols, block_tokens, deflate, gzip_wrap, read_header,
+                         token)
 from golden_util import dtype_info
 from gpu_check import GUARD, check_many
 from zarr_amd import _native
@@ -42,43 +42,7 @@ def check_batch(streams, dt, n):
     return check_many("gzip", streams, dt, n, FLAG_SETS, guard=GUARD)
 
 
-# ---- token paths from any bit, over deflate_kit's reader ---------------------------------
-def read_header(br):
-    """Block header at br.p: (last, literal/length table, distance table); br at the first body bit."""
-    last, ll, dl = block_header(br)
-    return last, canon(ll), canon(dl)
-
-
-def token(br, lt, dt):
-    """One token from br.p, as a decoder that believes a token starts there
-    takes it: its symbol, br behind the token; None, br not moved, where the
-    bits are no code."""
-    p = br.p
-    s = sym(br, lt)
-    if s is None or s <= 256:
-        return s
-    if s <= 285:
-        br.p += LEN_EXTRA[s - 257]
-        d = sym(br, dt)
-        if d is not None and d <= 29:
-            br.p += DIST_EXTRA[d]
-            return s
-    br.p = p
-    return None
-
-
-def block_tokens(br, lt, dt):
-    """Reads a block's body to its end-of-block code: (token count, bit of that code)."""
-    n = 0
-    while True:
-        p = br.p
-        s = token(br, lt, dt)
-        assert s is not None
-        if s == 256:
-            return n, p
-        n += 1
-
-
+# ---- token paths from any bit (deflate_kit's reader) ---------------------------------------
 def first_block(raw):
     """(reader, tables, body start, bit of the end-of-block code, token count) of the first block."""
     br = Bits(raw)

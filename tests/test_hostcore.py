@@ -454,6 +454,24 @@ def host_deflate(b: bytes, level: int) -> bytes:
     return out.raw[:n]
 
 
+def host_deflate_seg(b: bytes, level: int, seg: int) -> bytes:
+    """The segment-parallel parse of dz_parse emulated serially (levels 4-9), any segment length."""
+    h = host()
+    h.zz_host_deflate_seg.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p,
+                                      ctypes.c_uint64]
+    h.zz_host_deflate_seg.restype = ctypes.c_int64
+    cap = len(b) + len(b) // 8 + 1024
+    out = ctypes.create_string_buffer(cap)
+    n = h.zz_host_deflate_seg(b, len(b), level, seg, out, cap)
+    assert n >= 0
+    return out.raw[:n]
+
+
+def gpu_seg(D: int) -> int:
+    """dz_parse's segment length (pinned against the kernel in test_gz_enc_cases_host.py)."""
+    return (((D + 63) // 64 + 31) & ~31) if D else 32
+
+
 def zlib_raw(b: bytes, level: int) -> bytes:
     c = zlib.compressobj(level, zlib.DEFLATED, -15, 8, zlib.Z_DEFAULT_STRATEGY)
     return c.compress(b) + c.flush()
@@ -465,7 +483,9 @@ def test_zlib_core_matches_zlib(level):
     the greedy parse building its chains as it goes) and deflate_slow (4-9:
     match search per position, lazy parse), then trees: byte-identical to the
     system zlib 1.2.11 (the library flate2 wraps, gzip.rs:54-56) on mixed
-    inputs, incl. window-slide and block-flush edges."""
+    inputs, incl. window-slide and block-flush edges.  At levels 4-9 the
+    segment emulation (the stitch dz_parse does) gives the same bytes at
+    segment lengths 32, 96 and the GPU's."""
     rng = np.random.default_rng(level)
     cases = [b"", b"a", b"abcabcabcabc", bytes(70000), rng.integers(0, 256, 20000, dtype=np.uint8).tobytes(),
              rng.integers(0, 4, 100000, dtype=np.uint8).tobytes(),
@@ -473,7 +493,11 @@ def test_zlib_core_matches_zlib(level):
              np.cumsum(rng.integers(-3, 4, 70000)).astype("<i2").tobytes(),
              (np.arange(60000) % 4096).astype("<i2").tobytes()]
     for b in cases:
-        assert host_deflate(b, level) == zlib_raw(b, level), (level, len(b))
+        ref = zlib_raw(b, level)
+        assert host_deflate(b, level) == ref, (level, len(b))
+        if level >= 4:
+            for seg in (32, 96, gpu_seg(len(b))):
+                assert host_deflate_seg(b, level, seg) == ref, (level, len(b), seg)
 
 
 def test_zlib_core_matches_zlib_quant():
