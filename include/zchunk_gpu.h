@@ -485,6 +485,95 @@ int zcg_write_regions_v(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table
                         void* const* d_chunk_table, const zcg_vbox* d_boxes, uint32_t n_boxes,
                         void* d_scratch, int32_t* d_status, void* stream);
 
+/* ---- many bounding boxes with a step per dimension in one call ------------
+ * The reference's slices hard-code step 1 (to_ndarray_slice, ndarray.rs:118-127):
+ * a caller who wants every k-th element (a preview, a pyramid level, a
+ * subsampled crop) reads the dense box and slices it.  zcg_read_regions_s is
+ * zcg_read_regions_v with a step per box and dimension: shape[d] is the number
+ * of SAMPLES, sample i along d is array index offset[d] + i*step[d], and the
+ * view holds the samples only.  The box's HULL is the dense box offset[d] ..
+ * offset[d] + (shape[d]-1)*step[d] + 1 per dimension (empty when a shape[d] is
+ * 0).  There is no strided write, and no negative step. */
+typedef struct zcg_sbox {
+    uint64_t offset[ZCG_MAX_DIMS];   /* first sample, per array dim               */
+    uint64_t shape[ZCG_MAX_DIMS];    /* samples per array dim                     */
+    uint64_t step[ZCG_MAX_DIMS];     /* >= 1, array elements between two samples  */
+    int64_t  strides[ZCG_MAX_DIMS];  /* its view's strides per array dim, elements */
+    void*    base;                   /* DEVICE element (0,..,0) of its view       */
+} zcg_sbox;
+
+/* Host code, no GPU and no context.  `r` gives ndim, array_shape and
+ * chunk_shape; r->bbox_offset and r->bbox_shape are ignored.
+ *  - zcg_region_s_chunks, for one box (offset, shape, step: host arrays of
+ *    ndim): lo / n receive the hull's zcg_region_grid range; `touched`, when
+ *    not NULL, receives n[0] + n[1] + ... + n[ndim-1] bytes, dimension-major,
+ *    byte j of dimension d being 1 where grid index lo[d] + j holds a sample
+ *    (a sample's array index lies in that chunk's nominal bounds), else 0.
+ *    The chunks a strided read TOUCHES are the product of these per-dimension
+ *    sets; the return value is their number: the product over d of the touched
+ *    counts, 0 when the box misses the array (lo, n and touched are still
+ *    filled per dimension).  A step of 0, which the read calls refuse,
+ *    returns 0 with lo = n = 0 and writes no byte of `touched`.
+ *  - zcg_regions_s_grid: the union of the boxes' hulls' zcg_region_grid ranges
+ *    (`offsets`, `shapes`, `steps`: host arrays of n_boxes*ndim, box-major);
+ *    the return value and lo / n are zcg_regions_v_grid's.  A box with a step
+ *    of 0 (which the read call refuses) adds nothing.
+ *  - zcg_regions_s_scratch_bytes: bytes of DEVICE working memory a call with
+ *    n_boxes boxes needs (d_scratch, 8-byte aligned); monotonic in n_boxes. */
+uint64_t zcg_region_s_chunks(const zcg_region* r, const uint64_t* offset, const uint64_t* shape,
+                             const uint64_t* step, uint64_t* lo, uint64_t* n, uint8_t* touched);
+uint64_t zcg_regions_s_grid(const zcg_region* r, const uint64_t* offsets, const uint64_t* shapes,
+                            const uint64_t* steps, uint32_t n_boxes, uint64_t* lo, uint64_t* n);
+uint64_t zcg_regions_s_scratch_bytes(uint32_t n_boxes);
+
+/* `r` gives ndim, elem_size, chunk_order, fill_missing, fill_value,
+ * array_shape and chunk_shape for every box.  r->bbox_shape[d] is the LARGEST
+ * SAMPLE COUNT ANY BOX OF THE CALL MAY HAVE along dimension d: the host checks
+ * it and sizes the launch from it without reading device memory.
+ * r->bbox_offset and r->out_strides are ignored.  The table arguments are
+ * zcg_read_regions'.  d_boxes (zcg_sbox) and d_status are DEVICE arrays of
+ * n_boxes entries; zcg_sbox.base is the box's output view.
+ *  - Per-box equivalence: for every box whose status is ZCG_OK, element i of
+ *    its view (per dimension) receives exactly what zcg_read_region writes to
+ *    element i*step of a dense view of the box's hull, for a zcg_region with
+ *    the hull's offset and shape and a table holding the same pointers over
+ *    the hull's own zcg_region_grid range: clipping to array_shape,
+ *    overhanging edge chunks read over their nominal extent, fill versus
+ *    untouched, NULL entries.  Only the sampled elements of the view are ever
+ *    written.
+ *  - Touched chunks: a chunk is touched when at least one sample's array index
+ *    lies in its nominal bounds and the chunk is inside the hull's
+ *    zcg_region_grid range (zcg_region_s_chunks).  A chunk inside the hull's
+ *    range that holds no sample is never read: its table entry is never
+ *    dereferenced and may hold anything.  A chunk inside the table but
+ *    outside the hull's range is never touched either.
+ *  - A box with shape[d] > r->bbox_shape[d] for some d, or with step[d] == 0,
+ *    gets ZCG_ERR_INVALID_INPUT; a box whose hull extent plus
+ *    chunk_shape[d] - 1 reaches 2^32 along some d (positions are 32-bit) gets
+ *    ZCG_ERR_UNSUPPORTED; a box whose hull's grid range is not inside the
+ *    table's range gets ZCG_ERR_INVALID_INPUT.  Nothing of such a box is
+ *    written, and the other boxes are unaffected.
+ *  - A box with a zero extent is ZCG_OK and writes nothing.  A box that visits
+ *    no chunk is ZCG_OK, and filled when fill_missing is set.
+ *  - Every box's status word is written, also for boxes that have no work.
+ *  - r->bbox_shape[d] + chunk_shape[d] - 1 >= 2^32 returns
+ *    ZCG_ERR_UNSUPPORTED; so does n_boxes x the bound's elements >= 2^62.
+ *  - n_boxes == 0 returns ZCG_OK and launches nothing.
+ *  - Asynchronous on `stream`: two launches (a plan kernel that checks every
+ *    box and writes the status words and a prefix sum of work units into
+ *    d_scratch, and the walk), whatever n_boxes, the sample counts and the
+ *    steps are.  The call allocates nothing and does not synchronize with the
+ *    host; its only working memory is d_scratch
+ *    (zcg_regions_s_scratch_bytes(n_boxes) bytes), which may be reused once the
+ *    call's kernels have run.  d_boxes is read when the kernels run, so the
+ *    call can be captured in a graph and a replay sees new offsets, sample
+ *    counts, STEPS, strides and bases, as long as the counts stay inside the
+ *    bound.  Work follows the sum of the boxes' SAMPLES, not their hulls.
+ *  - Output views of different boxes that overlap are the caller's business. */
+int zcg_read_regions_s(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+                       const void* const* d_chunk_table, const zcg_sbox* d_boxes, uint32_t n_boxes,
+                       void* d_scratch, int32_t* d_status, void* stream);
+
 /* ---- FilesystemHierarchy chunk files ---------------
  * The e2e path's two ends: chunk files read into pinned staging by a pool of
  * `io_threads` host threads (open + shared flock + read, as ReadableStore::get,
@@ -717,6 +806,39 @@ int zcg_store_write_boxes_v_device(zcg_ctx* ctx, const zcg_array_meta* meta, con
 int zcg_store_write_boxes_v(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
                             const uint64_t* box_shapes, const uint64_t* offsets, const void* const* ins,
                             uint32_t n_boxes, uint64_t slot_budget_bytes, uint32_t io_threads);
+
+/* ---- read_ndarray for many boxes with a step per dimension ----------------
+ * zcg_store_read_boxes_v[_device] for strided boxes: `box_shapes` holds the
+ * n_boxes*ndim SAMPLE COUNTS and `box_steps` the n_boxes*ndim steps (>= 1),
+ * box-major, as `offsets` does; box b's result is what the _v call gives for
+ * its hull, sliced [::step] per dimension.  Everything carries over from the _v
+ * calls word for word, with one difference: THE CHUNKS READ AND DECODED ARE THE
+ * UNION OF THE BOXES' TOUCHED CHUNKS (zcg_region_s_chunks), deduplicated, not
+ * the hulls' grid ranges.  A chunk in a hull's range that holds no sample is
+ * never opened or decoded, and its table entry stays NULL.
+ *  - The slot budget and the grouping count touched chunks only.
+ *  - The in-grid check (ZCG_ERR_INVALID_INPUT before any file is read) applies
+ *    to touched chunks only: an untouched chunk of a hull's range outside the
+ *    array's chunk grid is no error.
+ *  - The 2^24 limit applies to the chunk TABLE, which covers the union of the
+ *    hulls' grid ranges (per box and per group), touched or not ->
+ *    ZCG_ERR_UNSUPPORTED.
+ *  - A step of 0 -> ZCG_ERR_INVALID_INPUT; a hull extent + chunk extent - 1
+ *    >= 2^32 along a dimension -> ZCG_ERR_UNSUPPORTED; both before any file is
+ *    read.
+ *  - The _device form takes box i at the DEVICE view d_outs[i] with the strides
+ *    out_strides + i*ndim (NULL: dense in the chunk memory order, with the
+ *    box's sample counts); fill_missing as in zcg_region.
+ *  - The host form writes box i to the HOST buffer outs[i], dense in the chunk
+ *    memory order with its own sample counts, and filled where no chunk is.
+ * n_boxes = 1 with every step 1 is the reference's read_ndarray. */
+int zcg_store_read_boxes_s_device(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                                  const uint64_t* box_shapes, const uint64_t* box_steps, const int64_t* out_strides,
+                                  uint32_t fill_missing, const uint64_t* offsets, void* const* d_outs,
+                                  uint32_t n_boxes, uint64_t slot_budget_bytes, uint32_t io_threads);
+int zcg_store_read_boxes_s(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                           const uint64_t* box_shapes, const uint64_t* box_steps, const uint64_t* offsets,
+                           void* const* outs, uint32_t n_boxes, uint64_t slot_budget_bytes, uint32_t io_threads);
 
 #ifdef __cplusplus
 }

@@ -13,8 +13,9 @@ from .metadata import ArrayMetadata, u64_ceil_div
 from .chunk import (DefaultChunk, SliceDataChunk, VecDataChunk, ZarrIOError, check_array_type,
                     read_chunks_host)
 from .storage import FilesystemHierarchy, get_chunk_key
-from .region import (BoundingBox, read_ndarray, read_ndarrays, read_ndarrays_v, write_ndarray, write_ndarrays,
-                     write_ndarrays_v)
+from .region import (BoundingBox, assemble_regions_s, read_ndarray, read_ndarrays, read_ndarrays_s, read_ndarrays_v,
+                     region_s_chunks, regions_s_grid, regions_s_scratch_bytes, sboxes_tensor, write_ndarray,
+                     write_ndarrays, write_ndarrays_v)
 from ._native import NativeUnavailable
 
 __all__ = [
@@ -22,6 +23,7 @@ __all__ = [
     "ExtendedDataType", "FilesystemHierarchy", "GZIP_CODEC_ID", "Gzip", "Lz4", "MetadataError",
     "NATIVE_ENDIAN", "NativeUnavailable", "REFLECTED_TYPES", "Raw", "SliceDataChunk",
     "VecDataChunk", "Xz", "ZarrIOError", "check_array_type", "effective_type", "get_chunk_key",
-    "read_chunks_host", "read_ndarray", "read_ndarrays", "read_ndarrays_v", "u64_ceil_div", "write_ndarray",
+    "assemble_regions_s", "read_chunks_host", "read_ndarray", "read_ndarrays", "read_ndarrays_s", "read_ndarrays_v",
+    "region_s_chunks", "regions_s_grid", "regions_s_scratch_bytes", "sboxes_tensor", "u64_ceil_div", "write_ndarray",
     "write_ndarrays", "write_ndarrays_v", "zarr_type",
 ]

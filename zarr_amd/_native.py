@@ -56,6 +56,8 @@ EXPORTED_SYMBOLS = (
     "zcg_read_regions_v", "zcg_write_regions_v",
     "zcg_store_read_boxes_v_device", "zcg_store_read_boxes_v",
     "zcg_store_write_boxes_v_device", "zcg_store_write_boxes_v",
+    "zcg_region_s_chunks", "zcg_regions_s_grid", "zcg_regions_s_scratch_bytes", "zcg_read_regions_s",
+    "zcg_store_read_boxes_s_device", "zcg_store_read_boxes_s",
 )
 
 
@@ -107,6 +109,14 @@ class VBox(ctypes.Structure):
                 ("strides", ctypes.c_int64 * MAX_DIMS), ("base", ctypes.c_void_p)]
 
 
+class SBox(ctypes.Structure):
+    """zcg_sbox: one strided box of a batched read (offset, sample counts, steps and view strides per array dim,
+    DEVICE base of the view)."""
+    _fields_ = [("offset", ctypes.c_uint64 * MAX_DIMS), ("shape", ctypes.c_uint64 * MAX_DIMS),
+                ("step", ctypes.c_uint64 * MAX_DIMS), ("strides", ctypes.c_int64 * MAX_DIMS),
+                ("base", ctypes.c_void_p)]
+
+
 class ArrayMeta(ctypes.Structure):
     _fields_ = [("array", Array), ("ndim", ctypes.c_uint32), ("chunk_ndim", ctypes.c_uint32),
                 ("chunk_order", ctypes.c_uint32), ("dtype_kind", ctypes.c_uint32),
@@ -121,6 +131,7 @@ assert ctypes.sizeof(Compression) == 24 and ctypes.sizeof(Array) == 40
 assert ctypes.sizeof(Chunk) == 32
 assert ctypes.sizeof(Box) == 8 * MAX_DIMS + 8
 assert ctypes.sizeof(VBox) == 3 * 8 * MAX_DIMS + 8
+assert ctypes.sizeof(SBox) == 4 * 8 * MAX_DIMS + 8
 
 _lib = None
 _lock = threading.Lock()
@@ -246,6 +257,20 @@ def load_library(path: str = LIB_PATH):
         L.zcg_store_write_boxes_v.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
                                               vp, vp, vp, u32, u64, u32]
         L.zcg_store_write_boxes_v.restype = ctypes.c_int
+        L.zcg_region_s_chunks.argtypes = [ctypes.POINTER(Region), vp, vp, vp, vp, vp, vp]
+        L.zcg_region_s_chunks.restype = u64
+        L.zcg_regions_s_grid.argtypes = [ctypes.POINTER(Region), vp, vp, vp, u32, vp, vp]
+        L.zcg_regions_s_grid.restype = u64
+        L.zcg_regions_s_scratch_bytes.argtypes = [u32]
+        L.zcg_regions_s_scratch_bytes.restype = u64
+        L.zcg_read_regions_s.argtypes = [vp, ctypes.POINTER(Region), vp, vp, vp, vp, u32, vp, vp, vp]
+        L.zcg_read_regions_s.restype = ctypes.c_int
+        L.zcg_store_read_boxes_s_device.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
+                                                    vp, vp, vp, u32, vp, vp, u32, u64, u32]
+        L.zcg_store_read_boxes_s_device.restype = ctypes.c_int
+        L.zcg_store_read_boxes_s.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
+                                             vp, vp, vp, vp, u32, u64, u32]
+        L.zcg_store_read_boxes_s.restype = ctypes.c_int
         _lib = L
         return L
 

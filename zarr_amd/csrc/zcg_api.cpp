@@ -597,9 +597,18 @@ int zcg_write_region(zcg_ctx* ctx, const zcg_region* r, void* const* d_chunk_tab
     return region_call(ctx, r, (const void* const*)d_chunk_table, (void*)d_in, stream, 1);
 }
 
-// The union of the boxes' grid ranges; `shapes` NULL: every box has r->bbox_shape.
-static uint64_t regions_grid(const zcg_region* r, const uint64_t* offsets, const uint64_t* shapes, uint32_t n_boxes,
-                             uint64_t* lo, uint64_t* n) {
+// The hull of `cnt` samples `step` apart: (cnt - 1) * step + 1, saturating.
+static uint64_t hull_extent(uint64_t cnt, uint64_t step) {
+    if (cnt == 0) return 0;
+    const unsigned __int128 e = (unsigned __int128)(cnt - 1) * step + 1;
+    return e > ~0ull ? ~0ull : (uint64_t)e;
+}
+
+// The union of the boxes' grid ranges; `shapes` NULL: every box has
+// r->bbox_shape.  `steps` not NULL: shapes are sample counts, a box's range is
+// its hull's, and a box with a zero step adds nothing.
+static uint64_t regions_grid(const zcg_region* r, const uint64_t* offsets, const uint64_t* shapes,
+                             const uint64_t* steps, uint32_t n_boxes, uint64_t* lo, uint64_t* n) {
     if (!r || r->ndim < 1 || r->ndim > ZCG_MAX_DIMS) return 0;
     const uint32_t nd = r->ndim;
     uint64_t ulo[ZCG_MAX_DIMS] = {0}, uhi[ZCG_MAX_DIMS] = {0};
@@ -607,11 +616,19 @@ static uint64_t regions_grid(const zcg_region* r, const uint64_t* offsets, const
     zcg_region one = *r;
     for (uint32_t b = 0; b < n_boxes && offsets; b++) {
         uint64_t blo[ZCG_MAX_DIMS], bn[ZCG_MAX_DIMS];
+        bool stepped = true;
         for (uint32_t d = 0; d < nd; d++) {
             one.bbox_offset[d] = offsets[(size_t)b * nd + d];
             if (shapes) one.bbox_shape[d] = shapes[(size_t)b * nd + d];
+            if (steps) {
+                stepped &= steps[(size_t)b * nd + d] != 0;
+                one.bbox_shape[d] = hull_extent(one.bbox_shape[d], steps[(size_t)b * nd + d]);
+                // the end saturates (zcg_region_grid clips it to the array)
+                if (one.bbox_offset[d] + one.bbox_shape[d] < one.bbox_offset[d])
+                    one.bbox_shape[d] = ~0ull - one.bbox_offset[d];
+            }
         }
-        if (zcg_region_grid(&one, blo, bn) == 0) continue;  // visits no chunk
+        if (!stepped || zcg_region_grid(&one, blo, bn) == 0) continue;  // visits no chunk
         for (uint32_t d = 0; d < nd; d++) {
             ulo[d] = any ? std::min(ulo[d], blo[d]) : blo[d];
             uhi[d] = any ? std::max(uhi[d], blo[d] + bn[d]) : blo[d] + bn[d];
@@ -629,12 +646,65 @@ static uint64_t regions_grid(const zcg_region* r, const uint64_t* offsets, const
 
 uint64_t zcg_regions_grid(const zcg_region* r, const uint64_t* offsets, uint32_t n_boxes, uint64_t* lo,
                           uint64_t* n) {
-    return regions_grid(r, offsets, nullptr, n_boxes, lo, n);
+    return regions_grid(r, offsets, nullptr, nullptr, n_boxes, lo, n);
 }
 
 uint64_t zcg_regions_v_grid(const zcg_region* r, const uint64_t* offsets, const uint64_t* shapes, uint32_t n_boxes,
                             uint64_t* lo, uint64_t* n) {
-    return regions_grid(r, offsets, shapes, shapes ? n_boxes : 0, lo, n);
+    return regions_grid(r, offsets, shapes, nullptr, shapes ? n_boxes : 0, lo, n);
+}
+
+uint64_t zcg_regions_s_grid(const zcg_region* r, const uint64_t* offsets, const uint64_t* shapes,
+                            const uint64_t* steps, uint32_t n_boxes, uint64_t* lo, uint64_t* n) {
+    return regions_grid(r, offsets, shapes, steps, shapes && steps ? n_boxes : 0, lo, n);
+}
+
+uint64_t zcg_region_s_chunks(const zcg_region* r, const uint64_t* offset, const uint64_t* shape,
+                             const uint64_t* step, uint64_t* lo, uint64_t* n, uint8_t* touched) {
+    if (!r || r->ndim < 1 || r->ndim > ZCG_MAX_DIMS || !offset || !shape || !step) return 0;
+    const uint32_t nd = r->ndim;
+    bool stepped = true;
+    for (uint32_t d = 0; d < nd; d++) stepped &= step[d] != 0;
+    if (!stepped) {
+        for (uint32_t d = 0; d < nd; d++) {
+            if (lo) lo[d] = 0;
+            if (n) n[d] = 0;
+        }
+        return 0;
+    }
+    uint64_t glo[ZCG_MAX_DIMS], gn[ZCG_MAX_DIMS];
+    zcg_region one = *r;
+    for (uint32_t d = 0; d < nd; d++) {
+        one.bbox_offset[d] = offset[d];
+        one.bbox_shape[d] = hull_extent(shape[d], step[d]);
+        if (one.bbox_offset[d] + one.bbox_shape[d] < one.bbox_offset[d]) one.bbox_shape[d] = ~0ull - offset[d];
+    }
+    const uint64_t hull_chunks = zcg_region_grid(&one, glo, gn);  // per dimension, also when the product is 0
+    unsigned __int128 cnt = hull_chunks ? 1 : 0;
+    for (uint32_t d = 0; d < nd; d++) {
+        if (lo) lo[d] = glo[d];
+        if (n) n[d] = gn[d];
+        const uint64_t cs = r->chunk_shape[d] ? r->chunk_shape[d] : 1;
+        uint64_t hit;
+        if (step[d] <= cs && shape[d]) {
+            // consecutive samples are at most a chunk apart: no chunk between the first and the last is skipped
+            hit = gn[d];
+            if (touched) memset(touched, 1, (size_t)gn[d]);
+        } else {
+            // every sample has a chunk of its own: those below the range's end
+            const unsigned __int128 limit = (unsigned __int128)(glo[d] + gn[d]) * cs;
+            const unsigned __int128 below = limit > offset[d] ? (limit - offset[d] + step[d] - 1) / step[d] : 0;
+            hit = gn[d] ? (uint64_t)std::min<unsigned __int128>(below, shape[d]) : 0;
+            if (touched) {
+                memset(touched, 0, (size_t)gn[d]);
+                for (uint64_t i = 0; i < hit; i++) touched[(offset[d] + i * step[d]) / cs - glo[d]] = 1;
+            }
+        }
+        if (touched) touched += gn[d];
+        cnt *= hit;
+        if (cnt > ~0ull) cnt = ~0ull;
+    }
+    return (uint64_t)cnt;
 }
 
 static int regions_call(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
@@ -684,8 +754,12 @@ int zcg_write_regions(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_l
 
 uint64_t zcg_regions_v_scratch_bytes(uint32_t n_boxes) { return (regions_v_prefix_bytes(n_boxes) + 255) & ~255ull; }
 
+uint64_t zcg_regions_s_scratch_bytes(uint32_t n_boxes) { return zcg_regions_v_scratch_bytes(n_boxes); }
+
+// dir 0: zcg_read_regions_v, 1: zcg_write_regions_v (d_boxes: zcg_vbox); 2:
+// zcg_read_regions_s (d_boxes: zcg_sbox, the bound is on the sample counts)
 static int regions_v_call(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
-                          const void* const* d_chunk_table, const zcg_vbox* d_boxes, uint32_t n_boxes,
+                          const void* const* d_chunk_table, const void* d_boxes, uint32_t n_boxes,
                           void* d_scratch, int32_t* d_status, void* stream, uint32_t dir) {
     if (n_boxes == 0) return region_head(ctx, r);
     RegionWalk w;  // w.bs, w.total: the bound
@@ -695,7 +769,7 @@ static int regions_v_call(zcg_ctx* ctx, const zcg_region* r, const uint64_t* tab
                                "2^32 elements",
                                &w, &entries);
     if (rc != ZCG_OK) return rc;
-    if (dir) w.fill = 0;
+    if (dir == 1) w.fill = 0;
     BoxTable bt{};
     bt.nboxes = n_boxes;
     uint64_t total = 1;  // every extent is below 2^32: saturate at 2^63
@@ -719,8 +793,11 @@ static int regions_v_call(zcg_ctx* ctx, const zcg_region* r, const uint64_t* tab
     }
     (void)hipSetDevice(ctx->device);
     const hipError_t e =
-        launch_regions_v(w, bt, d_chunk_table, d_boxes, d_scratch, d_status, dir, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, e, "regions_v launch");
+        dir == 2 ? launch_regions_s(w, bt, d_chunk_table, (const zcg_sbox*)d_boxes, d_scratch, d_status,
+                                    (hipStream_t)stream)
+                 : launch_regions_v(w, bt, d_chunk_table, (const zcg_vbox*)d_boxes, d_scratch, d_status, dir,
+                                    (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, e, dir == 2 ? "regions_s launch" : "regions_v launch");
     return ZCG_OK;
 }
 
@@ -736,6 +813,13 @@ int zcg_write_regions_v(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table
                         int32_t* d_status, void* stream) {
     return regions_v_call(ctx, r, table_lo, table_n, (const void* const*)d_chunk_table, d_boxes, n_boxes, d_scratch,
                           d_status, stream, 1);
+}
+
+int zcg_read_regions_s(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+                       const void* const* d_chunk_table, const zcg_sbox* d_boxes, uint32_t n_boxes, void* d_scratch,
+                       int32_t* d_status, void* stream) {
+    return regions_v_call(ctx, r, table_lo, table_n, d_chunk_table, d_boxes, n_boxes, d_scratch, d_status, stream,
+                          2);
 }
 
 }  // extern "C"

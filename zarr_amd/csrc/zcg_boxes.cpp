@@ -17,6 +17,11 @@
 // drivers with the one-shape calls, which pass one shape for all boxes and
 // keep the one-shape kernels (zcg_read_regions / zcg_write_regions); boxes of
 // differing shapes go through zcg_read_regions_v / zcg_write_regions_v.
+//
+// The _s read calls add a step per box and dimension: the planner then takes a
+// box's chunks from zcg_region_s_chunks (the touched chunks, a product of
+// per-dimension index sets) instead of the hull's whole grid range, and the
+// boxes are assembled by zcg_read_regions_s.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -79,6 +84,7 @@ struct Plan {
     bool varied = false;                // a shape per box (the _v calls); r.bbox_shape is then their bound
     const uint64_t* shapes = nullptr;   // box b's shape: shapes + b * sstep
     const int64_t* strides = nullptr;   // varied, device views: box b's strides, strides + b * nd; NULL: dense
+    const uint64_t* steps = nullptr;    // the _s calls (varied): box b's steps, steps + b * nd; shapes are sample counts
     size_t sstep = 0;
     std::vector<uint64_t> at;           // byte offset of box b among the boxes back to back, dense (n_boxes + 1)
     uint64_t gstr[ZCG_MAX_DIMS];        // linear chunk keys over the array's grid
@@ -113,9 +119,12 @@ struct Plan {
 // varied == false: every box has the shape box_shape (ndim) and, as a device
 // view, the strides `strides` (ndim); true: box_shape and strides hold
 // n_boxes * ndim entries, box-major, and NULL strides mean dense views.
-// cover == true (write): Group::read_first is filled in.
+// cover == true (write): Group::read_first is filled in.  box_steps (varied,
+// read): n_boxes * ndim steps, box_shape then holds sample counts and a box's
+// chunks are the touched ones; NULL: dense boxes.
 int plan_boxes(zcg_ctx* ctx, const std::string& what, const zcg_array_meta* meta, const char* root, const char* path,
-               const uint64_t* box_shape, const int64_t* strides, bool varied, uint32_t fill_missing,
+               const uint64_t* box_shape, const uint64_t* box_steps, const int64_t* strides, bool varied,
+               uint32_t fill_missing,
                const uint64_t* offsets, const void* const* bufs, uint32_t n_boxes, uint64_t slot_budget_bytes,
                bool host, bool cover, Plan& P) {
     if (!ctx || !meta || !root || !path || (!box_shape && !(varied && n_boxes == 0)) ||
@@ -147,6 +156,7 @@ int plan_boxes(zcg_ctx* ctx, const std::string& what, const zcg_array_meta* meta
     P.shapes = box_shape;
     P.sstep = varied ? nd : 0;
     P.strides = varied && !host ? strides : nullptr;
+    P.steps = box_steps;
     memset(&r, 0, sizeof r);
     r.ndim = nd;
     r.elem_size = es;
@@ -214,6 +224,8 @@ int plan_boxes(zcg_ctx* ctx, const std::string& what, const zcg_array_meta* meta
             }
             groups.push_back(std::move(cur));
         };
+        std::vector<uint8_t> touched;
+        std::vector<uint64_t> cell[ZCG_MAX_DIMS];  // strided: the touched grid indices per dimension
         for (uint32_t b = 0; b < n_boxes; b++) {
             uint64_t lo[ZCG_MAX_DIMS], n[ZCG_MAX_DIMS], pos[ZCG_MAX_DIMS];
             zcg_region rb = r;  // this box alone
@@ -221,27 +233,67 @@ int plan_boxes(zcg_ctx* ctx, const std::string& what, const zcg_array_meta* meta
                 rb.bbox_offset[d] = offsets[(size_t)b * nd + d];
                 rb.bbox_shape[d] = P.shape_of(b)[d];
             }
-            const uint64_t cnt = zcg_region_grid(&rb, lo, n);
+            // cnt chunks to read, out of a grid range of `range` chunks; chunk i is
+            // at lo[d] + i_d, or for a strided box at cell[d][i_d], i_d < m[d]
+            uint64_t cnt, range, m[ZCG_MAX_DIMS];
+            if (box_steps) {
+                const uint64_t* stp = box_steps + (size_t)b * nd;
+                for (uint32_t d = 0; d < nd; d++) {
+                    const uint64_t c = rb.bbox_shape[d];
+                    if (stp[d] == 0) {
+                        ctx_set_error(ctx, what + ": box " + std::to_string(b) + " has a step of 0");
+                        return ZCG_ERR_INVALID_INPUT;
+                    }
+                    if (c > 1 && (stp[d] >= (1ull << 32) || c > (1ull << 32) ||
+                                  (c - 1) * stp[d] + rb.chunk_shape[d] >= (1ull << 32))) {
+                        ctx_set_error(ctx, what + ": box " + std::to_string(b) +
+                                               ": hull extent + chunk extent along a dimension must stay below 2^32");
+                        return ZCG_ERR_UNSUPPORTED;
+                    }
+                }
+                cnt = zcg_region_s_chunks(&rb, rb.bbox_offset, rb.bbox_shape, stp, lo, n, nullptr);
+                range = cnt ? 1 : 0;
+                for (uint32_t d = 0; cnt && d < nd; d++)
+                    range = n[d] > BOXES_MAX_TABLE || range * n[d] > BOXES_MAX_TABLE ? BOXES_MAX_TABLE + 1 : range * n[d];
+                if (cnt && range <= BOXES_MAX_TABLE) {
+                    uint64_t sum = 0;
+                    for (uint32_t d = 0; d < nd; d++) sum += n[d];
+                    touched.assign(sum, 0);
+                    zcg_region_s_chunks(&rb, rb.bbox_offset, rb.bbox_shape, stp, lo, n, touched.data());
+                    const uint8_t* tp = touched.data();
+                    for (uint32_t d = 0; d < nd; d++) {
+                        cell[d].clear();
+                        for (uint64_t j = 0; j < n[d]; j++)
+                            if (tp[j]) cell[d].push_back(lo[d] + j);
+                        tp += n[d];
+                        m[d] = cell[d].size();
+                    }
+                }
+            } else {
+                cnt = range = zcg_region_grid(&rb, lo, n);
+                for (uint32_t d = 0; d < nd; d++) m[d] = n[d];
+            }
+            if (range > BOXES_MAX_TABLE) {
+                ctx_set_error(ctx, what + ": a chunk table above 2^24 entries is not supported");
+                return ZCG_ERR_UNSUPPORTED;
+            }
+            auto at = [&](uint32_t d, uint64_t i) { return box_steps ? cell[d][i] : lo[d] + i; };
             for (uint32_t d = 0; cnt && d < nd; d++)
-                if (lo[d] + n[d] > extent[d]) {
-                    for (uint32_t k = 0; k < nd; k++) pos[k] = lo[k] + n[k] - 1;
+                if (at(d, m[d] - 1) >= extent[d]) {
+                    for (uint32_t k = 0; k < nd; k++) pos[k] = at(k, m[k] - 1);
                     ctx_set_error(ctx, what + ": box " + std::to_string(b) + " visits chunk " + pos_text(pos, nd) +
                                            " outside the array's chunk grid");
                     return ZCG_ERR_INVALID_INPUT;
                 }
-            if (cnt > BOXES_MAX_TABLE) {
-                ctx_set_error(ctx, what + ": a chunk table above 2^24 entries is not supported");
-                return ZCG_ERR_UNSUPPORTED;
-            }
             auto visit = [&]() {
                 fresh.clear();
                 for (uint64_t i = 0; i < cnt; i++) {
                     uint64_t rem = i, key = 0;
                     bool part = false;
                     for (int d = (int)nd - 1; d >= 0; d--) {
-                        const uint64_t c = lo[d] + rem % n[d];
+                        const uint64_t c = at((uint32_t)d, rem % m[d]);
                         key += c * gstr[d];
-                        rem /= n[d];
+                        rem /= m[d];
                         if (cover) {  // write_bb == nom_chunk_bb (ndarray.rs:327), per dimension
                             const uint64_t cs = rb.chunk_shape[d], o = rb.bbox_offset[d], o1 = o + rb.bbox_shape[d];
                             part |= c * cs < o || c * cs + cs > (o1 < o ? ~0ull : o1);
@@ -268,6 +320,9 @@ int plan_boxes(zcg_ctx* ctx, const std::string& what, const zcg_array_meta* meta
     for (size_t g = 0; g < groups.size(); g++) {
         const Group& G = groups[g];
         P.gentries[g] =
+            box_steps ? zcg_regions_s_grid(&r, offsets + (size_t)G.b0 * nd, box_shape + (size_t)G.b0 * nd,
+                                           box_steps + (size_t)G.b0 * nd, G.b1 - G.b0, &P.glo[g * ZCG_MAX_DIMS],
+                                           &P.gn[g * ZCG_MAX_DIMS]) :
             varied ? zcg_regions_v_grid(&r, offsets + (size_t)G.b0 * nd, box_shape + (size_t)G.b0 * nd, G.b1 - G.b0,
                                         &P.glo[g * ZCG_MAX_DIMS], &P.gn[g * ZCG_MAX_DIMS])
                    : zcg_regions_grid(&r, offsets + (size_t)G.b0 * nd, G.b1 - G.b0, &P.glo[g * ZCG_MAX_DIMS],
@@ -337,7 +392,9 @@ int chunk_failed(zcg_ctx* ctx, const std::string& what, const Plan& P, uint64_t 
 // The records of boxes b0 .. b0 + nb as the region kernels take them: zcg_box
 // for one shape, zcg_vbox (shape and strides per box) for varied shapes.  Box
 // b's view is bufs[b], or, host == true, its place in the dense staging buffer.
-size_t record_bytes(const Plan& P) { return P.varied ? sizeof(zcg_vbox) : sizeof(zcg_box); }
+size_t record_bytes(const Plan& P) {
+    return P.steps ? sizeof(zcg_sbox) : P.varied ? sizeof(zcg_vbox) : sizeof(zcg_box);
+}
 
 std::vector<uint8_t> box_records(const Plan& P, const uint64_t* offsets, const void* const* bufs, void* staging,
                                  uint32_t b0, uint32_t nb, bool host) {
@@ -345,7 +402,16 @@ std::vector<uint8_t> box_records(const Plan& P, const uint64_t* offsets, const v
     for (uint32_t i = 0; i < nb; i++) {
         const uint32_t b = b0 + i;
         void* view = host ? (void*)((uint8_t*)staging + (P.at[b] - P.at[b0])) : (void*)bufs[b];
-        if (P.varied) {
+        if (P.steps) {
+            zcg_sbox& x = ((zcg_sbox*)recs.data())[i];
+            for (uint32_t d = 0; d < P.nd; d++) {
+                x.offset[d] = offsets[(size_t)b * P.nd + d];
+                x.shape[d] = P.shape_of(b)[d];
+                x.step[d] = P.steps[(size_t)b * P.nd + d];
+            }
+            P.strides_of(b, x.strides);
+            x.base = view;
+        } else if (P.varied) {
             zcg_vbox& x = ((zcg_vbox*)recs.data())[i];
             for (uint32_t d = 0; d < P.nd; d++) {
                 x.offset[d] = offsets[(size_t)b * P.nd + d];
@@ -367,6 +433,9 @@ std::vector<uint8_t> box_records(const Plan& P, const uint64_t* offsets, const v
 // shapes (d_scratch: zcg_regions_v_scratch_bytes(count) bytes).
 int regions_launch(zcg_ctx* ctx, const Plan& P, const uint64_t* lo, const uint64_t* n, void* d_table, void* d_recs,
                    uint32_t first, uint32_t count, void* d_scratch, int32_t* d_status, hipStream_t s, uint32_t dir) {
+    if (P.steps)
+        return zcg_read_regions_s(ctx, &P.r, lo, n, (const void* const*)d_table, (const zcg_sbox*)d_recs + first, count,
+                                  d_scratch, d_status + first, (void*)s);
     if (P.varied) {
         const zcg_vbox* bx = (const zcg_vbox*)d_recs + first;
         return dir ? zcg_write_regions_v(ctx, &P.r, lo, n, (void* const*)d_table, bx, count, d_scratch,
@@ -384,14 +453,15 @@ int regions_launch(zcg_ctx* ctx, const Plan& P, const uint64_t* lo, const uint64
 // order with fill (read_ndarray); else device views with the caller's strides.
 // varied: plan_boxes' (a shape, and as a device view strides, per box).
 int read_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
-               const uint64_t* box_shape, const int64_t* out_strides, bool varied, uint32_t fill_missing,
+               const uint64_t* box_shape, const uint64_t* box_steps, const int64_t* out_strides, bool varied,
+               uint32_t fill_missing,
                const uint64_t* offsets, void* const* outs, uint32_t n_boxes, uint64_t slot_budget_bytes,
                uint32_t io_threads, bool host) {
     const std::string what = "read_boxes";
     Plan P;
     // 1. before any file is read
-    const int prc = plan_boxes(ctx, what, meta, root, path, box_shape, out_strides, varied, fill_missing, offsets,
-                               outs, n_boxes, slot_budget_bytes, host, false, P);
+    const int prc = plan_boxes(ctx, what, meta, root, path, box_shape, box_steps, out_strides, varied, fill_missing,
+                               offsets, outs, n_boxes, slot_budget_bytes, host, false, P);
     if (prc != ZCG_OK) return prc;
     if (P.nothing || P.at[n_boxes] == 0) return ZCG_OK;
 
@@ -490,8 +560,8 @@ int write_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, cons
     const std::string what = "write_boxes";
     Plan P;
     // 1. before any file is read or written
-    const int prc = plan_boxes(ctx, what, meta, root, path, box_shape, in_strides, varied, 0, offsets, ins, n_boxes,
-                               slot_budget_bytes, host, true, P);
+    const int prc = plan_boxes(ctx, what, meta, root, path, box_shape, nullptr, in_strides, varied, 0, offsets, ins,
+                               n_boxes, slot_budget_bytes, host, true, P);
     if (prc != ZCG_OK) return prc;
     if (P.nothing || P.at[n_boxes] == 0) return ZCG_OK;
     const zcg_region& r = P.r;
@@ -734,14 +804,14 @@ extern "C" int zcg_store_read_boxes_device(zcg_ctx* ctx, const zcg_array_meta* m
                                            const char* path, const uint64_t* box_shape, const int64_t* out_strides,
                                            uint32_t fill_missing, const uint64_t* offsets, void* const* d_outs,
                                            uint32_t n_boxes, uint64_t slot_budget_bytes, uint32_t io_threads) {
-    return read_boxes(ctx, meta, root, path, box_shape, out_strides, false, fill_missing, offsets, d_outs, n_boxes,
+    return read_boxes(ctx, meta, root, path, box_shape, nullptr, out_strides, false, fill_missing, offsets, d_outs, n_boxes,
                       slot_budget_bytes, io_threads, false);
 }
 
 extern "C" int zcg_store_read_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
                                     const uint64_t* box_shape, const uint64_t* offsets, void* const* outs,
                                     uint32_t n_boxes, uint64_t slot_budget_bytes, uint32_t io_threads) {
-    return read_boxes(ctx, meta, root, path, box_shape, nullptr, false, 1, offsets, outs, n_boxes, slot_budget_bytes,
+    return read_boxes(ctx, meta, root, path, box_shape, nullptr, nullptr, false, 1, offsets, outs, n_boxes, slot_budget_bytes,
                       io_threads, true);
 }
 
@@ -750,14 +820,14 @@ extern "C" int zcg_store_read_boxes_v_device(zcg_ctx* ctx, const zcg_array_meta*
                                              const int64_t* out_strides, uint32_t fill_missing,
                                              const uint64_t* offsets, void* const* d_outs, uint32_t n_boxes,
                                              uint64_t slot_budget_bytes, uint32_t io_threads) {
-    return read_boxes(ctx, meta, root, path, box_shapes, out_strides, true, fill_missing, offsets, d_outs, n_boxes,
+    return read_boxes(ctx, meta, root, path, box_shapes, nullptr, out_strides, true, fill_missing, offsets, d_outs, n_boxes,
                       slot_budget_bytes, io_threads, false);
 }
 
 extern "C" int zcg_store_read_boxes_v(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
                                       const uint64_t* box_shapes, const uint64_t* offsets, void* const* outs,
                                       uint32_t n_boxes, uint64_t slot_budget_bytes, uint32_t io_threads) {
-    return read_boxes(ctx, meta, root, path, box_shapes, nullptr, true, 1, offsets, outs, n_boxes, slot_budget_bytes,
+    return read_boxes(ctx, meta, root, path, box_shapes, nullptr, nullptr, true, 1, offsets, outs, n_boxes, slot_budget_bytes,
                       io_threads, true);
 }
 
@@ -775,4 +845,38 @@ extern "C" int zcg_store_write_boxes_v(zcg_ctx* ctx, const zcg_array_meta* meta,
                                        uint32_t n_boxes, uint64_t slot_budget_bytes, uint32_t io_threads) {
     return write_boxes(ctx, meta, root, path, box_shapes, nullptr, true, offsets, ins, n_boxes, slot_budget_bytes,
                        io_threads, true);
+}
+
+// Every step is 1 and no box is empty: the strided call is then the _v call,
+// chunk for chunk and error for error, and takes its kernels (the dense walk
+// of zcg_region_v.hip is the faster one at step 1: profiles/boxes_s_bench.json).
+// An empty box keeps the strided plan, which unlike the _v plan never checks a
+// chunk that holds no sample.
+static bool all_dense(const zcg_array_meta* meta, const uint64_t* box_shapes, const uint64_t* box_steps,
+                      uint32_t n_boxes) {
+    if (!meta || !box_shapes || !box_steps || meta->ndim < 1 || meta->ndim > ZCG_MAX_DIMS) return false;
+    for (size_t i = 0; i < (size_t)n_boxes * meta->ndim; i++)
+        if (box_steps[i] != 1 || box_shapes[i] == 0) return false;
+    return n_boxes != 0;
+}
+
+extern "C" int zcg_store_read_boxes_s_device(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root,
+                                             const char* path, const uint64_t* box_shapes, const uint64_t* box_steps,
+                                             const int64_t* out_strides, uint32_t fill_missing,
+                                             const uint64_t* offsets, void* const* d_outs, uint32_t n_boxes,
+                                             uint64_t slot_budget_bytes, uint32_t io_threads) {
+    if (!box_steps && n_boxes) return ZCG_ERR_INVALID_INPUT;
+    if (all_dense(meta, box_shapes, box_steps, n_boxes)) box_steps = nullptr;
+    return read_boxes(ctx, meta, root, path, box_shapes, box_steps, out_strides, true, fill_missing, offsets, d_outs,
+                      n_boxes, slot_budget_bytes, io_threads, false);
+}
+
+extern "C" int zcg_store_read_boxes_s(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                                      const uint64_t* box_shapes, const uint64_t* box_steps, const uint64_t* offsets,
+                                      void* const* outs, uint32_t n_boxes, uint64_t slot_budget_bytes,
+                                      uint32_t io_threads) {
+    if (!box_steps && n_boxes) return ZCG_ERR_INVALID_INPUT;
+    if (all_dense(meta, box_shapes, box_steps, n_boxes)) box_steps = nullptr;
+    return read_boxes(ctx, meta, root, path, box_shapes, box_steps, nullptr, true, 1, offsets, outs, n_boxes,
+                      slot_budget_bytes, io_threads, true);
 }

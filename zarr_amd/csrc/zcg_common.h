@@ -407,6 +407,10 @@ uint64_t regions_v_prefix_bytes(uint32_t nboxes);
 hipError_t launch_regions_v(const RegionWalk& w, const BoxTable& bt, const void* const* d_table,
                             const zcg_vbox* d_boxes, void* d_prefix, int32_t* d_status, uint32_t dir,
                             hipStream_t s);
+// Boxes with a step per dimension (zcg_region_s.hip): launch_regions_v's
+// arguments, read direction only; w.bs bounds the sample counts.
+hipError_t launch_regions_s(const RegionWalk& w, const BoxTable& bt, const void* const* d_table,
+                            const zcg_sbox* d_boxes, void* d_prefix, int32_t* d_status, hipStream_t s);
 // m device slots of D bytes (d_slots: DEVICE array of their bases, each a
 // multiple of `es`), filled with the element `fillv`
 hipError_t launch_slot_fill(void* const* d_slots, uint32_t m, uint64_t D, uint32_t es, uint64_t fillv,

@@ -1,0 +1,207 @@
+// zcg_region_s.hip — region assembly for many boxes that each have their own
+// sample count, view and a step per dimension (zcg_read_regions_s): sample i of
+// a box along dimension d is array index offset[d] + i*step[d].  The reference
+// hard-codes step 1 in its slices (ndarray.rs:118-127); a caller who wants
+// every k-th element reads the dense hull and slices it.  Per box the values
+// are those zcg_read_region writes to element i*step of a dense view of the
+// hull.  The plan / prefix scheme is zcg_region_v.hip's; the kernels live in a
+// translation unit of their own, so the code objects of zcg_region.hip and
+// zcg_region_v.hip do not change with them.
+#include <hip/hip_runtime.h>
+
+#include "zcg_common.h"
+#include "zcg_region_walk.h"
+#include "zcg_region_walk_s.h"
+
+namespace zcg {
+
+namespace {
+
+constexpr u32 RS_PLAN_T = 1024;      // threads of the plan kernel's one workgroup
+constexpr u32 RS_WAVES = RG_T / 64;  // row pieces per work unit
+constexpr u32 RS_GRID = 32768;       // cap of the walk's grid
+
+template <bool UNI>
+__device__ __forceinline__ u64 uni(u64 x) { return UNI ? ru64(x) : x; }
+
+struct SBoxFate {
+    i32 status;   // ZCG_OK: the box is walked (if it has work)
+    bool visits;  // its hull visits a chunk
+};
+
+// The terms of box b: vbox_terms (zcg_region_v.hip) over the box's hull, the
+// box's sample counts in wb.bs / wb.total, and its steps in st.  The step of a
+// dimension with fewer than two samples is never used and kept as 1.
+template <bool UNI>
+__device__ __forceinline__ SBoxFate sbox_terms(const RegionWalk& w, const BoxTable& bt,
+                                               const u8* const* __restrict__ table,
+                                               const zcg_sbox* __restrict__ boxes, u64 b, RegionWalk& wb,
+                                               BoxTerms& t, Steps& st) {
+    const zcg_sbox* bx = boxes + b;
+    wb = w;
+    u64 base = 0, total = 1;
+    bool inside = true, visits = true, bounded = true, stepped = true, near = true;
+#pragma unroll
+    for (u32 k = 0; k < ZCG_MAX_DIMS; k++) {
+        t.orr[k] = 0;
+        t.gn[k] = 0;
+        wb.bs[k] = 0;
+        wb.ostr[k] = 0;
+        st.st[k] = 1;
+        if (k >= w.nd) continue;
+        const u32 d = bt.dim[k];
+        const u64 off = uni<UNI>(bx->offset[d]);
+        const u64 cnt = uni<UNI>(bx->shape[d]);
+        const u64 step = uni<UNI>(bx->step[d]);
+        stepped &= step != 0;
+        bounded &= cnt <= w.bs[k];
+        // the hull's extent: (cnt - 1) * step + 1.  cnt <= the bound < 2^32 for a
+        // box that is walked, so the product is exact once step < 2^32
+        const u64 cs = w.cs[k];
+        const bool wide = cnt > 1 && step >= (1ull << 32);
+        const u64 c1 = cnt > 1 ? (cnt - 1) & 0xFFFFFFFFull : 0;
+        const u64 ext = cnt ? c1 * (wide ? 1 : step) + 1 : 0;
+        near &= !wide && ext + cs - 1 < (1ull << 32);
+        // zcg_region_grid's range of the hull (see box_terms)
+        const u64 lo = off / cs;
+        const u64 orr = off - lo * cs;
+        const u64 oe = off + ext < off ? ~0ull : off + ext;
+        const u64 end = oe < bt.as[k] ? oe : bt.as[k];
+        const u64 s = end > off ? end - off : 0;
+        const u32 span = (u32)orr + (u32)s, nq = span / w.cs[k];
+        const u32 n = nq + (span != nq * w.cs[k] ? 1u : 0u);
+        t.orr[k] = (u32)orr;
+        t.gn[k] = n;
+        visits &= n != 0;
+        inside &= lo >= bt.tlo[k] && lo - bt.tlo[k] + n <= bt.tn[k];
+        base += (lo - bt.tlo[k]) * w.tstr[k];
+        wb.bs[k] = (u32)cnt;
+        wb.ostr[k] = (i64)uni<UNI>((u64)bx->strides[d]);
+        st.st[k] = cnt > 1 ? (u32)step : 1u;
+        total *= cnt & 0xFFFFFFFFull;
+    }
+    wb.total = total;
+    t.out = (u8*)(uintptr_t)uni<UNI>((u64)(uintptr_t)bx->base);
+    i32 status = ZCG_OK;
+    if (!stepped || !bounded) status = ZCG_ERR_INVALID_INPUT;
+    else if (!near) status = ZCG_ERR_UNSUPPORTED;
+    // a box with a zero extent has no element to place: it is in order wherever the table is
+    else if (!(inside || !visits || total == 0)) status = ZCG_ERR_INVALID_INPUT;
+    const bool use = status == ZCG_OK && visits && inside;
+    t.table = table + (use ? base : 0);
+    return SBoxFate{status, status == ZCG_OK && visits};
+}
+
+__device__ __forceinline__ bool sbox_rows(const RegionWalk& wb) { return wb.bs[0] >= 32u * wb.V; }
+__device__ __forceinline__ u64 sbox_row_units(const RegionWalk& wb) { return wb.total / wb.bs[0] * row_pieces(wb); }
+
+// The plan: regions_v_plan_kernel's, with work counted in output elements.
+__global__ __launch_bounds__(RS_PLAN_T) void regions_s_plan_kernel(RegionWalk w, BoxTable bt,
+                                                                   const u8* const* __restrict__ table,
+                                                                   const zcg_sbox* __restrict__ boxes,
+                                                                   u64* __restrict__ prefix,
+                                                                   i32* __restrict__ status) {
+    __shared__ u64 wsum[RS_PLAN_T / 64];
+    const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    u64 carry = 0;
+    for (u64 b0 = 0; b0 < bt.nboxes; b0 += RS_PLAN_T) {
+        const u64 b = b0 + threadIdx.x;
+        u64 units = 0;
+        if (b < bt.nboxes) {
+            RegionWalk wb;
+            BoxTerms t;
+            Steps st;
+            const SBoxFate f = sbox_terms<false>(w, bt, table, boxes, b, wb, t, st);
+            status[b] = f.status;
+            if (f.status == ZCG_OK && wb.total && (f.visits || w.fill))
+                units = sbox_rows(wb) ? (sbox_row_units(wb) + RS_WAVES - 1) / RS_WAVES
+                                      : (wb.total + (u64)RG_T * wb.V - 1) / ((u64)RG_T * wb.V);
+        }
+        u64 x = units;  // inclusive scan over the wave
+#pragma unroll
+        for (u32 o = 1; o < 64; o <<= 1) {
+            const u64 y = __shfl_up((unsigned long long)x, o, 64);
+            if (lane >= o) x += y;
+        }
+        if (lane == 63) wsum[wv] = x;
+        __syncthreads();
+        u64 before = carry, all = 0;
+#pragma unroll
+        for (u32 i = 0; i < RS_PLAN_T / 64; i++) {
+            if (i < wv) before += wsum[i];
+            all += wsum[i];
+        }
+        if (b < bt.nboxes) prefix[b] = before + x - units;
+        carry += all;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) prefix[bt.nboxes] = carry;
+}
+
+__global__ __launch_bounds__(RG_T) void regions_s_kernel(RegionWalk w, BoxTable bt,
+                                                         const u8* const* __restrict__ table,
+                                                         const zcg_sbox* __restrict__ boxes,
+                                                         const u64* __restrict__ prefix) {
+    const u64 n = bt.nboxes;
+    const u64 all = ru64(prefix[n]);
+    const u64 per = (all + gridDim.x - 1) / gridDim.x;
+    u64 unit = (u64)blockIdx.x * per;
+    const u64 last = unit + per < all ? unit + per : all;
+    if (unit >= last) return;
+    // the box of the first unit: prefix[b] <= unit < prefix[b + 1]
+    u64 b = 0, hi = n;
+    while (hi - b > 1) {
+        const u64 mid = (b + hi) >> 1;
+        if (ru64(prefix[mid]) <= unit) b = mid;
+        else hi = mid;
+    }
+    const u32 wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // any readable, 8-byte aligned device address: where a sample that has no
+    // source points its load (the gather keeps every load unconditional)
+    const u8* safe = (const u8*)boxes;
+    while (unit < last) {
+        u64 pe;
+        while ((pe = ru64(prefix[b + 1])) <= unit) b++;  // prefix[n] = all > unit ends it
+        const u64 pb = ru64(prefix[b]);
+        RegionWalk wb;
+        BoxTerms t;
+        Steps st;
+        sbox_terms<true>(w, bt, table, boxes, b, wb, t, st);
+        const u64 end = pe < last ? pe : last;
+        if (sbox_rows(wb)) {
+            const u32 ppr = row_pieces(wb);
+            const u64 nwu = sbox_row_units(wb);
+            for (; unit < end; unit++) {
+                const u64 wu = (unit - pb) * RS_WAVES + wv;
+                if (wu >= nwu) continue;
+                const u64 row = wu / ppr;
+                if (st.st[0] == 1) walk_row_piece_s(wb, t, st, row, (u32)(wu - row * ppr));
+                else gather_row_piece(wb, t, st, row, (u32)(wu - row * ppr), safe);
+            }
+        } else if (st.st[0] == 1) {
+            for (; unit < end; unit++) walk_tile_s(wb, t, st, unit - pb);
+        } else {
+            for (; unit < end; unit++) gather_tile(wb, t, st, unit - pb, safe);
+        }
+    }
+}
+
+}  // namespace
+
+// Two launches whatever the boxes (launch_regions_v's shape): the plan, and
+// the walk on a grid sized from the bound of the sample counts.
+hipError_t launch_regions_s(const RegionWalk& w, const BoxTable& bt, const void* const* d_table,
+                            const zcg_sbox* d_boxes, void* d_prefix, int32_t* d_status, hipStream_t s) {
+    if (bt.nboxes == 0) return hipSuccess;
+    hipLaunchKernelGGL(regions_s_plan_kernel, dim3(1), dim3(RS_PLAN_T), 0, s, w, bt, (const u8* const*)d_table,
+                       d_boxes, (u64*)d_prefix, d_status);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || w.total == 0) return e;  // a zero extent in the bound: no box has work
+    const u64 per_box = (w.total + (u64)RG_T * w.V - 1) / ((u64)RG_T * w.V);
+    const u64 units = per_box * bt.nboxes;
+    hipLaunchKernelGGL(regions_s_kernel, dim3((u32)(units < RS_GRID ? units : RS_GRID)), dim3(RG_T), 0, s, w, bt,
+                       (const u8* const*)d_table, d_boxes, (const u64*)d_prefix);
+    return hipGetLastError();
+}
+
+}  // namespace zcg

@@ -555,6 +555,166 @@ def write_ndarrays_v(hier, path_name: str, meta: ArrayMetadata, offsets, arrays,
         raise ZarrIOError(_native.STATUS_NAMES.get(r, str(r)), f"write_boxes: {ctx.last_error()}")
 
 
+def sboxes_tensor(offsets, shapes, steps, strides, bases, device: int = 0):
+    """Device uint8 tensor of _native.SBox records (zcg_sbox): per box its
+    offset, sample counts, steps and view strides (elements) per array dim and
+    the device address of element (0, ..., 0) of its view."""
+    import torch
+    B = len(offsets)
+    arr = (_native.SBox * max(B, 1))()
+    for b in range(B):
+        for d in range(len(offsets[b])):
+            arr[b].offset[d] = int(offsets[b][d])
+            arr[b].shape[d] = int(shapes[b][d])
+            arr[b].step[d] = int(steps[b][d])
+            arr[b].strides[d] = int(strides[b][d])
+        arr[b].base = int(bases[b])
+    raw = np.frombuffer(bytes(arr), np.uint8)[: B * ctypes.sizeof(_native.SBox)].copy()
+    return torch.from_numpy(raw).to(torch.device("cuda", device))
+
+
+def regions_s_scratch_bytes(n_boxes: int) -> int:
+    """zcg_regions_s_scratch_bytes: device working memory of one _s call."""
+    return int(_native.load_library().zcg_regions_s_scratch_bytes(int(n_boxes)))
+
+
+def regions_s_grid(meta: ArrayMetadata, offsets, shapes, steps):
+    """zcg_regions_s_grid (host code, no GPU): the union of the grid ranges of
+    the boxes' hulls (`shapes`: sample counts, `steps`: B x ndim) -> (lo, n)."""
+    L = _native.load_library()
+    nd = meta.get_ndim()
+    r = _region(meta, BoundingBox([0] * nd, _bound(shapes, nd)), 1, False, 0, [0] * nd)
+    offs = np.ascontiguousarray(np.array(offsets, dtype=np.uint64).reshape(-1, nd))
+    shp = np.ascontiguousarray(np.array(shapes, dtype=np.uint64).reshape(-1, nd))
+    stp = np.ascontiguousarray(np.array(steps, dtype=np.uint64).reshape(-1, nd))
+    lo = (ctypes.c_uint64 * _native.MAX_DIMS)()
+    n = (ctypes.c_uint64 * _native.MAX_DIMS)()
+    L.zcg_regions_s_grid(ctypes.byref(r), offs.ctypes.data, shp.ctypes.data, stp.ctypes.data, offs.shape[0],
+                         ctypes.addressof(lo), ctypes.addressof(n))
+    return [int(lo[d]) for d in range(nd)], [int(n[d]) for d in range(nd)]
+
+
+def region_s_chunks(meta: ArrayMetadata, offset, shape, step, want_touched: bool = True):
+    """zcg_region_s_chunks (host code, no GPU) for one strided box -> (lo, n,
+    touched, count): the hull's grid range, per dimension a list of n[d] 0/1
+    flags (1: grid index lo[d] + j holds a sample; None without want_touched),
+    and the number of touched chunks (the product of the touched counts)."""
+    L = _native.load_library()
+    nd = meta.get_ndim()
+    r = _region(meta, BoundingBox([0] * nd, [0] * nd), 1, False, 0, [0] * nd)
+    off = (ctypes.c_uint64 * _native.MAX_DIMS)(*[int(x) for x in offset])
+    shp = (ctypes.c_uint64 * _native.MAX_DIMS)(*[int(x) for x in shape])
+    stp = (ctypes.c_uint64 * _native.MAX_DIMS)(*[int(x) for x in step])
+    lo = (ctypes.c_uint64 * _native.MAX_DIMS)()
+    n = (ctypes.c_uint64 * _native.MAX_DIMS)()
+    args = (ctypes.byref(r), ctypes.addressof(off), ctypes.addressof(shp), ctypes.addressof(stp),
+            ctypes.addressof(lo), ctypes.addressof(n))
+    count = int(L.zcg_region_s_chunks(*args, None))
+    lo_l, n_l = [int(lo[d]) for d in range(nd)], [int(n[d]) for d in range(nd)]
+    if not want_touched:
+        return lo_l, n_l, None, count
+    flags = np.zeros(max(sum(n_l), 1), np.uint8)
+    count = int(L.zcg_region_s_chunks(*args, flags.ctypes.data))
+    at = np.concatenate([[0], np.cumsum(n_l)]).astype(int)
+    return lo_l, n_l, [flags[at[d]:at[d + 1]].tolist() for d in range(nd)], count
+
+
+def assemble_regions_s(meta: ArrayMetadata, bound: Sequence[int], es: int, table, table_lo, table_n, boxes, status,
+                       fill: bool, fill_value: int, device: int = 0, stream=None, scratch=None) -> None:
+    """Device-level call for many strided boxes (zcg_read_regions_s):
+    assemble_regions_v with `boxes` = device tensor of _native.SBox records
+    (sboxes_tensor), each with its own sample counts, steps and view, and
+    `bound` = the largest sample count per dimension any box may have.  Table
+    entries of chunks that hold no sample are never read.  `scratch` = device
+    tensor of regions_s_scratch_bytes(B) bytes (None: allocated here, which a
+    captured call must not do).  Asynchronous."""
+    ctx = _native.context(device)
+    nd = meta.get_ndim()
+    r = _region(meta, BoundingBox([0] * nd, bound), es, fill, fill_value, [0] * nd)
+    lo = (ctypes.c_uint64 * _native.MAX_DIMS)(*[int(x) for x in table_lo])
+    n = (ctypes.c_uint64 * _native.MAX_DIMS)(*[int(x) for x in table_n])
+    n_boxes = boxes.numel() * boxes.element_size() // ctypes.sizeof(_native.SBox) if boxes is not None else 0
+    if n_boxes and scratch is None:
+        import torch
+        scratch = torch.empty(regions_s_scratch_bytes(n_boxes), dtype=torch.uint8, device=boxes.device)
+    st = ctx.lib.zcg_read_regions_s(ctx.handle, ctypes.byref(r), ctypes.addressof(lo), ctypes.addressof(n),
+                                    table.data_ptr() if table is not None else None,
+                                    boxes.data_ptr() if n_boxes else None, n_boxes,
+                                    scratch.data_ptr() if scratch is not None else None,
+                                    status.data_ptr() if status is not None else None,
+                                    _stream_handle(stream, device))
+    _raise_status(st, ctx, "read_regions_s")
+
+
+def _steps_arg(steps, B: int, nd: int) -> np.ndarray:
+    """`steps` as a B x ndim uint64 array: one step vector for all boxes, or one
+    per box; every step >= 1."""
+    try:
+        a = np.array(steps, dtype=object)
+        if a.ndim == 1 and a.shape[0] == nd:
+            a = np.broadcast_to(a, (B, nd))
+        if a.shape != (B, nd):
+            raise ValueError
+        vals = [[int(x) for x in row] for row in a]
+    except (ValueError, TypeError):
+        raise ZarrIOError("InvalidInput", f"steps must hold {nd} entries, or {B} x {nd}") from None
+    if any(x < 1 for row in vals for x in row):
+        raise ZarrIOError("InvalidInput", "every step must be at least 1")
+    return np.ascontiguousarray(np.array(vals, dtype=np.uint64).reshape(B, nd))
+
+
+def read_ndarrays_s(hier, path_name: str, meta: ArrayMetadata, boxes: Sequence[BoundingBox], steps, t,
+                    device: int = 0, as_tensor: bool = False, flags: int = 0, slot_budget_bytes: int = 0):
+    """read_ndarray for many strided boxes in one native call
+    (zcg_store_read_boxes_s[_device]): boxes[b].shape is the number of samples,
+    sample i along d is array index offset[d] + i * step[d]; `steps` is B x ndim,
+    or one step vector for all boxes.  The result is a list of arrays whose [b]
+    equals read_ndarray(..., hull_b, t)[::step], where hull_b is the dense box
+    offset .. offset + (shape - 1) * step + 1.  Only the chunks that hold a
+    sample are read and decoded, each once.  With as_tensor the result is what
+    read_ndarrays_v returns: (uint8 device tensor of the boxes back to back,
+    byte offset per box, element strides per box)."""
+    check_array_type(t, meta)
+    nd = meta.get_ndim()
+    for bb in boxes:
+        if len(bb.offset) != nd:
+            raise ZarrIOError("InvalidData", "Wrong number of dimensions")
+    B = len(boxes)
+    stp = _steps_arg(steps, B, nd)
+    import torch
+    dt = np.dtype(t).newbyteorder("=")
+    es = dt.itemsize
+    order = "F" if meta.chunk_memory_layout == "F" else "C"
+    offs = np.ascontiguousarray(np.array([bb.offset for bb in boxes], dtype=np.uint64).reshape(-1, nd))
+    shp = np.ascontiguousarray(np.array([bb.shape for bb in boxes], dtype=np.uint64).reshape(-1, nd))
+    strides = [_strides(bb.shape, order) for bb in boxes]
+    at = [0]
+    for bb in boxes:
+        at.append(at[-1] + int(np.prod(bb.shape, dtype=object)) * es)
+    am = _native_meta(meta, flags)
+    ctx = _native.context(device)
+    root, path = os.fsencode(hier.base_path), path_name.encode()
+    if as_tensor:
+        out = torch.empty(max(at[-1], 1), dtype=torch.uint8, device=torch.device("cuda", device))
+        outs = (ctypes.c_void_p * max(B, 1))(*[out.data_ptr() + at[b] for b in range(B)])
+        r = ctx.lib.zcg_store_read_boxes_s_device(ctx.handle, ctypes.byref(am), root, path, shp.ctypes.data,
+                                                  stp.ctypes.data, None, 1, offs.ctypes.data, ctypes.addressof(outs),
+                                                  B, slot_budget_bytes, 16)
+    else:
+        host = np.empty(max(at[-1], 1), np.uint8)
+        outs = (ctypes.c_void_p * max(B, 1))(*[host.ctypes.data + at[b] for b in range(B)])
+        r = ctx.lib.zcg_store_read_boxes_s(ctx.handle, ctypes.byref(am), root, path, shp.ctypes.data,
+                                           stp.ctypes.data, offs.ctypes.data, ctypes.addressof(outs), B,
+                                           slot_budget_bytes, 16)
+    if r != _native.OK:
+        raise ZarrIOError(_native.STATUS_NAMES.get(r, str(r)), f"read_boxes: {ctx.last_error()}")
+    if as_tensor:
+        return out[: at[-1]], at[:-1], strides
+    return [np.ndarray(tuple(bb.shape), dtype=dt, buffer=host, offset=at[b],
+                       strides=tuple(s * es for s in strides[b])).copy(order=order)
+            for b, bb in enumerate(boxes)]
+
+
 def read_ndarray_into(hier, path_name: str, meta: ArrayMetadata, bbox: BoundingBox, arr: np.ndarray, t,
                       device: int = 0, flags: int = 0) -> None:
     """ZarrNdarrayReader::read_ndarray_into (ndarray.rs:176-268): elements
