@@ -2,7 +2,8 @@
 """C2-shaped gzip batch through the one-wave-per-chunk inflate kernel: parity
 of every chunk against its input, HIP-event time of the default kernel vs the
 256-lane round kernel (ZCG_FLAG_INFLATE_BLOCK_PAR), and the wave kernel's
-debug counters (ZCG_FLAG_DEBUG_COUNTERS).  Usage: iw_stats.py [n_chunks]"""
+debug counters (ZCG_FLAG_DEBUG_COUNTERS).  Usage: iw_stats.py [n_chunks] [--wave-only]
+(--wave-only leaves the 256-lane kernel out: the A/B runs of the wave kernel)"""
 import ctypes, json, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,7 +14,9 @@ from zarr_amd import ArrayMetadata, Gzip
 from zarr_amd.batch import BatchCodec, PackedStreams
 from zarr_amd import _native
 
-n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
+argv = [a for a in sys.argv[1:] if a != "--wave-only"]
+wave_only = "--wave-only" in sys.argv[1:]
+n = int(argv[0]) if argv else 4096
 pool = 64
 vals = [quant_chunk(i) for i in range(pool)]
 streams = [gzip_flate2(v.tobytes(), 6) for v in vals]
@@ -49,7 +52,7 @@ def timed(flags, reps=5):
     return round(min(ts), 3), round(float(np.median(ts)), 3)
 
 
-for tag, fl in (("wave", _native.FLAG_INFLATE_WAVE), ("blockpar", _native.FLAG_INFLATE_BLOCK_PAR)):
+for tag, fl in (("wave", _native.FLAG_INFLATE_WAVE), ("blockpar", _native.FLAG_INFLATE_BLOCK_PAR))[:1 if wave_only else 2]:
     packed.dst.zero_()
     mn, med = timed(fl)
     check(tag)
@@ -59,7 +62,7 @@ for tag, fl in (("wave", _native.FLAG_INFLATE_WAVE), ("blockpar", _native.FLAG_I
 L = _native.load_library()
 fn = L.zcg__debug_inflate_wave_counters
 fn.argtypes = [ctypes.c_void_p, ctypes.c_int]
-out = np.zeros(32, np.uint64)
+out = np.zeros(40, np.uint64)  # (IW_NDBG; a library from before the stage slots fills 32)
 fn(out.ctypes.data, 1)
 codec.decode(meta, packed, flags=_native.FLAG_DEBUG_COUNTERS | _native.FLAG_INFLATE_WAVE)
 torch.cuda.synchronize()
@@ -69,7 +72,7 @@ names = {0: "rounds", 1: "blocks", 2: "stages", 3: "groups", 4: "p1_lane_it", 5:
          13: "cyc_chain", 14: "cyc_classify", 15: "cyc_far", 16: "cyc_near", 17: "cyc_place", 18: "cyc_commit",
          19: "cyc_total", 20: "far_iters", 21: "near_batches", 22: "near_passes", 23: "near_straddle_batches", 24: "cyc_hdr_tables", 25: "cyc_refetch", 26: "cyc_eob", 27: "cyc_hdr_walk",
          28: "p2_wave_it", 29: "far_batches", 30: "p1_steady_it",
-         31: "far_batches_after_first"}
+         31: "far_batches_after_first", 32: "cyc_stage_setup", 33: "cyc_tables", 34: "table_reloads"}
 d = {v: int(out[k]) for k, v in names.items()}
 res["per_chunk"] = {k: round(v / packed.n, 1) for k, v in d.items()}
 # lane efficiency of a pass: lane-steps used / (64 lanes x 8 steps x outer steps issued)

@@ -46,8 +46,14 @@
 
 // A/B knobs: stage entries, tokens per lane list, waves per SIMD the register
 // budget targets, far-byte loads in flight per lane
+// ZIW_S: entries of a stage whose near descriptors carry 15-bit distances
+// (byte-swapped dtypes, fewer than 16 bytes of room; every stage before the
+// ring grew).  ZIW_SW: entries of the ring, the stage of every other case.
 #ifndef ZIW_S
 #define ZIW_S 2048
+#endif
+#ifndef ZIW_SW
+#define ZIW_SW 4096
 #endif
 #ifndef ZIW_TCAP
 #define ZIW_TCAP 768
@@ -65,8 +71,7 @@
 
 namespace zcg {
 
-constexpr u32 IW_S = ZIW_S;            // stage ring entries: 64 lane blocks of IW_BLK
-constexpr u32 IW_BLK = IW_S / 64;
+constexpr u32 IW_S = ZIW_SW;           // stage ring entries (a stage holds up to IW_S - 16 bytes)
 constexpr u32 IW_TCAP = ZIW_TCAP;
 constexpr u32 IW_GK = 3;       // token groups in flight in the L phase (named slots)  // far-byte loads in flight per lane (gather)
 constexpr u32 IW_SEGMIN = 128;   // bits per lane segment
@@ -96,7 +101,19 @@ constexpr u32 IW_MARKW = ZIW_MARKW;  // bitmap words kept per segment (the rest 
 constexpr u32 IW_MWORDS = IW_MARKW + IW_MWIN;  // mark words per segment (bitmap, u32; the last window may spill past IW_MARKW)
 static_assert(IW_MARKW + IW_MWIN <= IW_MWORDS, "mark window inside the bitmap");
 constexpr u32 IW_EST0 = 64 * 3072;  // first block's body estimate (zlib-6 blocks: ~195 Kbit)
-static_assert(IW_S == 2048 && IW_BLK == 32, "the L phase keeps one 32-entry block per lane in registers");
+static_assert(IW_S >= 2048 && IW_S % 512 == 0, "the ring is cleared by one 16-byte store per lane and trip");
+// A near part's descriptor (st.mk) carries offset | (d - 1) << bits | slot << 26.
+// A stage with 16-byte source pieces (wide) keeps only near parts whose source
+// lies inside it, d <= o < IW_S: IW_OBITS bits each.  A stage without them
+// (byte-swapped dtypes, fewer than 16 bytes of room) reads straddling sources
+// of any distance: 15 bits for d - 1, so its capacity stays at IW_SN - 16 bytes
+// and its offsets at 11 bits.
+constexpr u32 IW_OBITS = IW_S <= 2048 ? 11 : IW_S <= 4096 ? 12 : 13;
+constexpr u32 IW_SN = ZIW_S;
+constexpr u32 IW_OBITS_N = 11;
+static_assert(IW_S <= (1u << IW_OBITS) && 2 * IW_OBITS <= 26, "near descriptor: offset, d - 1 below the slot (wide stage)");
+static_assert(IW_SN <= IW_S && IW_SN <= (1u << IW_OBITS_N) && IW_OBITS_N + 15 <= 26,
+              "near descriptor: offset, d - 1 <= 32 767 below the slot (narrow stage)");
 
 // (token word: zcg_inflate_word.h; this kernel's markers carry their bit length)
 
@@ -119,8 +136,8 @@ constexpr u32 W_LCAP = 852;
 constexpr int W_DB = 8;
 constexpr u32 W_DCAP = 432;  // >= enough(30, 8, 15) = 402
 
-constexpr u32 IW_NDBG = 32;
-__device__ unsigned long long g_iw_dbg[32];
+constexpr u32 IW_NDBG = 40;
+__device__ unsigned long long g_iw_dbg[IW_NDBG];
 // IWD_P1_WIT / IWD_P2_WIT: outer iterations (8 steps each) the wave issued in
 // pass 1 / pass 2; with the lane sums IWD_P1_IT / IWD_P2_IT they give a pass's
 // lane efficiency, lane-steps used / (64 * 8 * outer iterations).
@@ -128,25 +145,36 @@ __device__ unsigned long long g_iw_dbg[32];
 enum { IWD_ROUNDS, IWD_BLOCKS, IWD_STAGES, IWD_GROUPS, IWD_P1_IT, IWD_P2_IT, IWD_CHAIN, IWD_P1_WIT, IWD_CAPS,
        IWD_NOEOB, IWT_HDR, IWT_P1, IWT_P2, IWT_CHAIN, IWT_CLASSIFY, IWT_FAR, IWT_NEAR, IWT_PLACE,
        IWT_COMMIT, IWT_TOTAL, IWD_FARIT, IWD_NBATCH, IWD_NPASS, IWD_NSTRAD, IWT_HTAB, IWT_REFETCH, IWT_EOB, IWT_HWALK,
-       IWD_P2_WIT, IWD_FARB, IWD_P1_STEADY, IWD_FARB2 /* far batches after a group's first */ };
-static_assert(IWD_FARB2 < IW_NDBG && IW_NDBG <= 32, "debug slots");
+       IWD_P2_WIT, IWD_FARB, IWD_P1_STEADY, IWD_FARB2 /* far batches after a group's first */,
+       IWT_SETUP /* a stage's ring clear and first placement */, IWT_TABS /* table save and reloads */,
+       IWD_RELOADS };
+static_assert(IWD_RELOADS < IW_NDBG, "debug slots");
 
+// The Huffman tables are read by the headers, the H round and the look-ahead
+// only; the L phase's stage ring lies over them and over the H round's state.
+// A Huffman block's token-ready tables are saved to the chunk's workspace slot
+// once (iw_tab_save) and loaded back where they are read again after an L
+// phase (iw_tab_load).
 struct IwLds {
-    u32 ltab[W_LCAP];
-    u32 dtab[W_DCAP];
     union {
-        struct {  // block headers and the look-ahead (wave-uniform reader)
-            HuffLds lh, dh;
-            u8 lens[320];
-            u32 bcache[BI_CACHE_WORDS];
-            u32 hwin[130];  // 512 stream bytes from the code-length codes on (dynamic header)
-        } h;
-        struct Hr {    // H round: marked extent (bits) of each segment, staged tokens, mark windows
-            u32 mlim[64];
-            u32 tst[2 * IW_K][64];  // ring of two aligned list blocks (slot = token index % 8)
-            u32 mwin[IW_MWIN][64];
-            u32 em[IW_EMW][64];     // each segment's first IW_EMW mark words (pass 2 reads them here)
-        } hr;
+        struct {
+            u32 ltab[W_LCAP];
+            u32 dtab[W_DCAP];
+            union {
+                struct {  // block headers and the look-ahead (wave-uniform reader)
+                    HuffLds lh, dh;
+                    u8 lens[320];
+                    u32 bcache[BI_CACHE_WORDS];
+                    u32 hwin[130];  // 512 stream bytes from the code-length codes on (dynamic header)
+                } h;
+                struct {       // H round: marked extent (bits) of each segment, staged tokens, mark windows
+                    u32 mlim[64];
+                    u32 tst[2 * IW_K][64];  // ring of two aligned list blocks (slot = token index % 8)
+                    u32 mwin[IW_MWIN][64];
+                    u32 em[IW_EMW][64];     // each segment's first IW_EMW mark words (pass 2 reads them here)
+                } hr;
+            } u;
+        };
         struct {       // L phase: the stage ring, near-token descriptors and batch markers
             u16 ptr[IW_S];
             u64 fd[64];  // far parts of the group by rank: source byte | (ring entry | length << 16) << 32
@@ -154,10 +182,14 @@ struct IwLds {
             // part's first byte in the batch, 0 elsewhere (cleared per batch)
             u32 mk[64];
         } st;
-    } u;
+    };
     u32 dbgc[IW_NDBG];
 };
 static_assert(sizeof(IwLds) + 32 <= 10240, "16 chunks per CU");
+constexpr u32 IW_TAB_WORDS = W_LCAP + W_DCAP;  // both tables, contiguous: saved and loaded as 16-byte vectors
+static_assert(offsetof(IwLds, dtab) == offsetof(IwLds, ltab) + 4 * W_LCAP && offsetof(IwLds, ltab) % 16 == 0 &&
+                  IW_TAB_WORDS % 4 == 0,
+              "table save area");
 
 // wave-local ordering point for LDS (and the compiler): a wave's LDS
 // operations are performed in issue order, so a fence at wavefront scope is
@@ -274,6 +306,29 @@ __device__ void iw_tab_serial(IwLds& L) {
     for (u32 i = lane; i < W_DCAP; i += 64) L.dtab[i] = iw_d_serial(L.dtab[i]);
     wsync();
 }
+// Both tables to / from the chunk's workspace slot, as the H round reads them
+// (IW_TAB_WORDS / 4 = 321 vectors: five 16-byte accesses per lane and a tail).
+// The save reads the tables before anything of the L phase is written (LDS
+// operations of a wave are performed in issue order); the load is complete,
+// for every lane, before its caller reads a table entry.
+// Global memory: the load reads what this wave's own save stored.  Between a
+// save and any load lies at least one stage, and every stage that emits ends
+// in iw_commit's __syncthreads(), which waits for all of the wave's vector
+// memory operations (vmcnt 0); the H round before the first stage has its own.
+// So the stores are done, and were written through this CU's L1, before the
+// load is issued (the token lists are read back on the same terms).
+__device__ void iw_tab_save(const IwLds& L, gu32* gt) {
+    const u32 lane = (u32)lane_id();
+    const u32x4* t = (const u32x4*)L.ltab;
+    for (u32 i = lane; i < IW_TAB_WORDS / 4; i += 64) *(gu32x4*)(gt + 4 * i) = t[i];
+}
+__device__ void iw_tab_load(IwLds& L, const gu32* gt) {
+    const u32 lane = (u32)lane_id();
+    u32x4* t = (u32x4*)L.ltab;
+    wsync();  // (the stage's last LDS reads come first)
+    for (u32 i = lane; i < IW_TAB_WORDS / 4; i += 64) t[i] = *(const gu32x4*)(gt + 4 * i);
+    wsync();
+}
 
 // Decode one token from >= 48 valid bits with the token-ready tables: both
 // table lookups always run, so lanes holding different token kinds do not
@@ -339,7 +394,7 @@ __device__ __forceinline__ u32 iw_pos(const gu32* gl, u32 lm, u32 j, u32 seg0) {
 __device__ void iw_commit(IwLds& L, u8* dst, u64 from, u64 to, DType t) {
     wsync();
     const u64 base = from & ~15ull;
-    stage_commit<64>(L.u.st.ptr, dst, from, to, t, (u32)lane_id(), [base](u64 q) -> u32 { return (u32)(q - base); });
+    stage_commit<64>(L.st.ptr, dst, from, to, t, (u32)lane_id(), [base](u64 q) -> u32 { return (u32)(q - base); });
     // the next stage's far reads come back through this CU's L1/L2: wait
     // for the stores (same-CU stores refresh the L1)
     __syncthreads();
@@ -513,7 +568,8 @@ __device__ __attribute__((always_inline)) int read_dynamic_wave(BitIn& b, u8* le
 constexpr u32 IW_NSLOT_MAX = 8192;
 constexpr u64 IW_LIST_WORDS = 64ull * IW_TSTR;              // token lists of a slot (u32)
 constexpr u64 IW_MARK_WORDS = 64ull * IW_MWORDS;            // token-start bitmaps of a slot (u32)
-constexpr u64 IW_SLOT_WORDS = IW_LIST_WORDS + IW_MARK_WORDS;
+constexpr u64 IW_SLOT_WORDS = IW_LIST_WORDS + IW_MARK_WORDS + IW_TAB_WORDS;  // + the block's saved tables
+static_assert(IW_LIST_WORDS % 4 == 0 && IW_MARK_WORDS % 4 == 0 && IW_SLOT_WORDS % 4 == 0, "16-byte aligned slot areas");
 constexpr u64 IW_OWNER_BYTES = IW_NSLOT_MAX * 4;
 
 // ---- H round ------------------------------------------------------------------------------------
@@ -822,11 +878,13 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
     gu32* const gl = pools + (u64)slot * IW_SLOT_WORDS;                 // token lists (iw_ta layout)
     gu32* const marks = gl + IW_LIST_WORDS;                             // token-start bitmaps [lane][IW_MWORDS]
     gu32* const mk = marks + (u64)lane * IW_MWORDS;
+    gu32* const gtab = marks + IW_MARK_WORDS;                           // the Huffman block's token-ready tables
 
     BitIn b;
     bi_init(b, ds, n_ds, L.u.h.bcache);
     u64 P = 0;
     bool last = false, boundary = false, after_stored = false;
+    bool tab_lds = false;  // the current Huffman block's tables are in LDS (no stage has overwritten them)
     int r = R_OK;
     u32 est = IW_EST0;
     if (dbg) {
@@ -853,6 +911,11 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
             iw_tab_wave(L);
         }
         IW_T(IWT_HDR);
+        if (r == R_OK && type != 0) {  // ... and a copy for after the L phase, whose ring lies over them
+            iw_tab_save(L, gtab);
+            tab_lds = true;
+            IW_T(IWT_TABS);
+        }
         if (r != R_OK) break;
         IW_ADD(IWD_BLOCKS, 1);
         wsync();
@@ -861,7 +924,8 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
             // (a piece of at most IW_S - 16 bytes never wraps the ring; the fence
             // after a commit orders its stage reads before the next piece's stores)
             u64 in_end = 0;
-            r = inf_stored_copy<64>(m, hdr_end >> 3 /* byte aligned after LEN/NLEN */, slen, P, D, IW_S - 16, L.u.st.ptr, lane,
+            tab_lds = false;
+            r = inf_stored_copy<64>(m, hdr_end >> 3 /* byte aligned after LEN/NLEN */, slen, P, D, IW_S - 16, L.st.ptr, lane,
                                     [](u64 P0, u32 i) -> u32 { return (u32)(P0 & 15) + i; },
                                     [&](u64 from, u64 to) { iw_commit(L, dst, from, to, tw); wsync(); }, &in_end, &boundary);
             if (r != R_OK) break;
@@ -880,12 +944,18 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
         seg = seg < IW_SEGMIN ? IW_SEGMIN : seg > IW_SEGMAX ? IW_SEGMAX : seg;
         while (!block_end && !final_cut && r == R_OK && P < D) {
             // ================= H round: coarse speculative Huffman decode =================
+            if (!tab_lds) {  // a further round of the block: the stages before it took the tables' place
+                iw_tab_load(L, gtab);
+                tab_lds = true;
+                IW_ADD(IWD_RELOADS, 1);
+                IW_T(IWT_TABS);
+            }
             const IwRound hr = iw_h_round(L, R0, seg, total_bits, vbase, nvec, a0b, gl, marks, mk, dbg, t_last);
             const u32 p = hr.p, ncm = hr.ncm, chL = hr.chL, chS = hr.chS, chE = hr.chE, endq = hr.endq;
 
             // ================= L phase: the chain's tokens, one stage at a time =========
-            // Stage: output [S, S + emit) in the ring; lane l owns the 32-entry
-            // block at absolute B0 + 32 l, B0 = S & ~31 (64 blocks = the ring).
+            // Stage: output [S, S + emit) in the ring, position q at entry
+            // q - (S & ~15) (iw_commit); every token writes its own entries.
             u32 cm = 0, cj = 0;  // cursor: chain member, token index in its list
             // lane's token at the cursor + lane (a member's list may end inside a group)
             auto mL = [&](u32 m) -> u32 { return (u32)__builtin_amdgcn_readlane((int)chL, (int)m); };
@@ -979,19 +1049,30 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
             while (!round_done && r == R_OK) {
                 const u64 S = P;
                 const u64 room = D - P;
-                const u32 capS = IW_S - 16;  // (S & 15) + cap <= IW_S: the stage never wraps the ring
+                // 16-byte source pieces: native byte order, and every piece of
+                // a far token ends before S + 16 <= D
+                const bool wide_ok = !tw.swap && room >= 16;
+                // Capacity and near descriptor split, chosen once per stage
+                // (wave-uniform): a wide stage fills the ring, a narrow one
+                // keeps room for 15-bit distances (IW_OBITS above).
+                // (S & 15) + cap <= IW_S: the stage never wraps the ring
+                const u32 capS = (wide_ok ? IW_S : IW_SN) - 16;
+                const u32 dsh = wide_ok ? IW_OBITS : IW_OBITS_N;  // d - 1 from this bit of a near descriptor
+                const u32 omask = (1u << dsh) - 1u;
                 const u32 cap = room < capS ? (u32)room : capS;
                 const bool fin = (u64)cap == room;
+                tab_lds = false;
                 // Token-granular stage.  The ring is cleared, then every kept
-                // token writes its own entries: a literal its final byte; a FAR
-                // match (whole source before the stage) its final bytes, copied
-                // from the committed output by 16-byte pieces, one aligned quad
-                // of entries OR-ed in per source dword; a NEAR match one pointer
-                // per byte (to the byte d before it), resolved in ordered
-                // batches of 64 near bytes by pointer jumping.  Sources always
-                // lie before their byte, so a batch only waits on itself.
+                // token writes its own entries: a literal its final byte; the
+                // FAR part of a match (the first bytes, whose source lies before
+                // the stage) its final bytes, copied from the committed output
+                // by 16-byte pieces and stored exactly; the NEAR part (source
+                // inside the stage) one pointer per byte (to the byte d before
+                // it), resolved in ordered batches of 64 near bytes by pointer
+                // jumping.  Sources always lie before their byte, so a batch
+                // only waits on itself.
                 {
-                    u32x4* z = (u32x4*)L.u.st.ptr;
+                    u32x4* z = (u32x4*)L.st.ptr;
 #pragma unroll
                     for (u32 i = 0; i < IW_S / 512; i++) z[lane + 64 * i] = u32x4{0u, 0u, 0u, 0u};
                 }
@@ -1002,9 +1083,6 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
                 u32 why = 0;       // 1 final cut, 2 marker / round end, 3 capacity
                 u32 mcode = 0;
                 const gu8* gd = (const gu8*)dst;
-                // 16-byte source pieces: native byte order, and every piece of
-                // a far token ends before S + 16 <= D
-                const bool wide_ok = !tw.swap && room >= 16;
                 const u32 S32 = (u32)S;  // (D < 2^32)
                 const u32 s0 = S32 & 15u;  // ring entry of the stage's first byte
                 struct Tk {
@@ -1048,24 +1126,24 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
                     // unsigned max scan over the cleared slots hands every lane
                     // its part's descriptor.
                     for (u32 n0 = 0; n0 < pn_NB; n0 += 64) {
-                        L.u.st.mk[lane] = 0;
+                        L.st.mk[lane] = 0;
                         wsync();
                         if (pn_nla && pn_na < n0 + 64 && pn_na + pn_nla > n0) {
                             const u32 sl = pn_na > n0 ? pn_na - n0 : 0u;
-                            L.u.st.mk[sl] = (sl << 26) | pn_dsa;
+                            L.st.mk[sl] = (sl << 26) | pn_dsa;
                         }
                         if (pn_nlb && pn_nb < n0 + 64 && pn_nb + pn_nlb > n0) {
                             const u32 sl = pn_nb > n0 ? pn_nb - n0 : 0u;
-                            L.u.st.mk[sl] = (sl << 26) | pn_dsb;
+                            L.st.mk[sl] = (sl << 26) | pn_dsb;
                         }
                         wsync();
-                        const u32 dsc = iw_incl_umax(L.u.st.mk[lane]) & 0x3FFFFFFu;
+                        const u32 dsc = iw_incl_umax(L.st.mk[lane]) & 0x3FFFFFFu;
                         const u32 i = n0 + lane;
                         bool done = i >= pn_NB, strad = false;
                         u32 pos = 0, cur = 0;
                         if (!done) {
-                            const u32 p = (dsc & 0x7FFu) + i;
-                            const u32 d = (dsc >> 11) + 1u;
+                            const u32 p = (dsc & omask) + i;
+                            const u32 d = (dsc >> dsh) + 1u;
                             pos = s0 + p;
                             if (p >= d) cur = s0 + p - d;
                             else cur = IE_VAL | (u32)gd[swap_pos32(S32 + p - d, tw)];  // before the stage (!wide_ok only)
@@ -1074,10 +1152,10 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
                             // read precedes this batch's writes, and an entry of this
                             // batch still reads as a pointer (zero or older), so only
                             // final values are taken
-                            const u32 v0 = cur >= IE_VAL ? cur : (u32)L.u.st.ptr[cur];
+                            const u32 v0 = cur >= IE_VAL ? cur : (u32)L.st.ptr[cur];
                             done = v0 >= IE_VAL;
                             if (done) cur = v0;
-                            L.u.st.ptr[pos] = (u16)cur;
+                            L.st.ptr[pos] = (u16)cur;
                         }
                         wsync();
                         IW_ADD(IWD_NBATCH, 1);
@@ -1089,10 +1167,10 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
                                 break;
                             }
                             u32 v = 0;
-                            if (!done) v = L.u.st.ptr[cur];
+                            if (!done) v = L.st.ptr[cur];
                             wsync();
                             if (!done) {
-                                L.u.st.ptr[pos] = (u16)v;
+                                L.st.ptr[pos] = (u16)v;
                                 cur = v;
                                 done = v >= IE_VAL;
                             }
@@ -1124,10 +1202,10 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
                         why = 3;
                         return true;
                     }
-                    IW_T(IWT_PLACE);
+                    IW_T(emitted ? IWT_PLACE : IWT_SETUP);  // (a stage's first group: with the ring clear before it)
                     const Tk A = classify(ta, oa, la, ka), B = classify(tb, ob, lb, kb);
-                    if (A.kind == 1u) L.u.st.ptr[s0 + A.o] = (u16)(IE_VAL | A.d);
-                    if (B.kind == 1u) L.u.st.ptr[s0 + B.o] = (u16)(IE_VAL | B.d);
+                    if (A.kind == 1u) L.st.ptr[s0 + A.o] = (u16)(IE_VAL | A.d);
+                    if (B.kind == 1u) L.st.ptr[s0 + B.o] = (u16)(IE_VAL | B.d);
                     IW_T(IWT_CLASSIFY);
                     // far parts, compacted one per lane (rank in token order):
                     // 16-byte source pieces from the part's first source byte,
@@ -1151,11 +1229,11 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
                         auto far_batch = [&](u32 f0, auto with_prefetch) {
                             IW_ADD(IWD_FARB, 1);
                             if (f0) IW_ADD(IWD_FARB2, 1);
-                            if (fA && rkA - f0 < 64u) L.u.st.fd[rkA - f0] = fdesc(A);
-                            if (fB && rkB - f0 < 64u) L.u.st.fd[rkB - f0] = fdesc(B);
+                            if (fA && rkA - f0 < 64u) L.st.fd[rkA - f0] = fdesc(A);
+                            if (fB && rkB - f0 < 64u) L.st.fd[rkB - f0] = fdesc(B);
                             wsync();
                             const bool fl = f0 + lane < NF;
-                            const u64 fdw = L.u.st.fd[lane];
+                            const u64 fdw = L.st.fd[lane];
                             const u32 src = (u32)fdw, hi = (u32)(fdw >> 32);
                             const u32 qi = hi & 0xFFFFu, e = hi >> 16;
                             const u32 np = (e + 15) >> 4;
@@ -1179,9 +1257,9 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
                             if (fl) {
                                 auto piece = [&](const u32x4& V, u32 p) {
                                     const u32 b0 = 16 * p;  // < e
-                                    iw_put(L.u.st.ptr + qi + b0, e - b0, ie_lo(V.x), ie_hi(V.x), ie_lo(V.y), ie_hi(V.y));
+                                    iw_put(L.st.ptr + qi + b0, e - b0, ie_lo(V.x), ie_hi(V.x), ie_lo(V.y), ie_hi(V.y));
                                     if (e > b0 + 8)
-                                        iw_put(L.u.st.ptr + qi + b0 + 8, e - b0 - 8, ie_lo(V.z), ie_hi(V.z), ie_lo(V.w),
+                                        iw_put(L.st.ptr + qi + b0 + 8, e - b0 - 8, ie_lo(V.z), ie_hi(V.z), ie_lo(V.w),
                                                ie_hi(V.w));
                                 };
                                 piece(V0, 0);
@@ -1211,8 +1289,9 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
                     const u32 nincl = iw_incl_scan(nps);
                     const u32 na = nincl - nps, nb = na + nla;
                     const u32 NB = (u32)__builtin_amdgcn_readlane((int)nincl, 63);
-                    // a part's descriptor: (its first offset - its first near index) | (d - 1) << 11
-                    const u32 dsa = (noa - na) | ((A.d - 1u) << 11), dsb = (nob - nb) | ((B.d - 1u) << 11);
+                    // a part's descriptor: (its first offset - its first near index) | (d - 1) << dsh
+                    // (read only where the token has a near part: d - 1 then fits below the slot)
+                    const u32 dsa = (noa - na) | ((A.d - 1u) << dsh), dsb = (nob - nb) | ((B.d - 1u) << dsh);
                     pn_nla = nla;
                     pn_nlb = nlb;
                     pn_na = na;
@@ -1314,7 +1393,14 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
     if (r == R_OK && P >= D && boundary) {
         b.cbase = ~0ull;
         wsync();
-        if (!after_stored) iw_tab_serial(L);
+        if (!after_stored) {
+            if (!tab_lds) {  // (always: the output filled in a stage)
+                iw_tab_load(L, gtab);
+                IW_ADD(IWD_RELOADS, 1);
+            }
+            iw_tab_serial(L);
+            IW_T(IWT_TABS);
+        }
     }
     // (under the verify flag the records sit between the owner words and the pools)
     st = inf_close<W_LB, W_LCAP, W_DB, W_DCAP>(b, m, r, P, D, boundary, last, after_stored, L.u.h.lens, &L.u.h.lh, L.ltab,
@@ -1336,10 +1422,10 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
 }
 
 extern "C" int zcg__debug_inflate_wave_counters(unsigned long long* out, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_iw_dbg), sizeof(unsigned long long) * 32) != hipSuccess)
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_iw_dbg), sizeof(unsigned long long) * IW_NDBG) != hipSuccess)
         return -1;
     if (reset) {
-        unsigned long long z[32] = {0};
+        unsigned long long z[IW_NDBG] = {0};
         if (hipMemcpyToSymbol(HIP_SYMBOL(g_iw_dbg), z, sizeof(z)) != hipSuccess) return -1;
     }
     return 0;
@@ -1357,8 +1443,14 @@ static u32 iw_nslot(uint32_t n) {
     return (u32)ns;
 }
 
+#if ZIW_SW != 4096
+#define IW_CFG_SW ",SW=" ZCG_STR(ZIW_SW)
+#else
+#define IW_CFG_SW ""
+#endif
 const char* cfg_inflate_wave() {
-    return "inflate_wave:S=" ZCG_STR(ZIW_S) ",TCAP=" ZCG_STR(ZIW_TCAP) ",WPE=" ZCG_STR(ZIW_WPE)
+    // (the ring's size is named only in a build that overrides it: the product build's string is the parent's)
+    return "inflate_wave:S=" ZCG_STR(ZIW_S) IW_CFG_SW ",TCAP=" ZCG_STR(ZIW_TCAP) ",WPE=" ZCG_STR(ZIW_WPE)
            ",EST_PCT=" ZCG_STR(ZIW_EST_PCT) ",MARKW=" ZCG_STR(ZIW_MARKW) ",G=" ZCG_STR(ZIW_G) ",DBG=" ZCG_STR(ZIW_DBG);
 }
 
