@@ -493,7 +493,9 @@ int zcg_write_regions_v(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table
  * of SAMPLES, sample i along d is array index offset[d] + i*step[d], and the
  * view holds the samples only.  The box's HULL is the dense box offset[d] ..
  * offset[d] + (shape[d]-1)*step[d] + 1 per dimension (empty when a shape[d] is
- * 0).  There is no strided write, and no negative step. */
+ * 0).  zcg_write_regions_s is the inverse: the view's samples go to those
+ * array indices and nothing between them is written.  There is no negative
+ * step. */
 typedef struct zcg_sbox {
     uint64_t offset[ZCG_MAX_DIMS];   /* first sample, per array dim               */
     uint64_t shape[ZCG_MAX_DIMS];    /* samples per array dim                     */
@@ -573,6 +575,74 @@ uint64_t zcg_regions_s_scratch_bytes(uint32_t n_boxes);
 int zcg_read_regions_s(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
                        const void* const* d_chunk_table, const zcg_sbox* d_boxes, uint32_t n_boxes,
                        void* d_scratch, int32_t* d_status, void* stream);
+
+/* The strided scatter.  The arguments are zcg_read_regions_s' (r->bbox_shape
+ * bounds the SAMPLE COUNTS; d_scratch is zcg_regions_s_scratch_bytes(n_boxes)
+ * bytes), with two differences: zcg_sbox.base is the box's INPUT view, which
+ * is only read, and fill_missing and fill_value are ignored.
+ *  - Per box: sample i of the view (per dimension) goes to array index
+ *    offset + i*step.  For a box whose status is ZCG_OK every sample is written
+ *    whole at its chunk-local position, in the chunk's memory order, if its
+ *    array index lies in a chunk that is touched (zcg_region_s_chunks), inside
+ *    the hull's zcg_region_grid range, and not NULL in the table.  The overhang
+ *    of an edge chunk beyond array_shape is written; a sample beyond the hull's
+ *    grid range (the hull is clipped to array_shape) is dropped.
+ *  - No other byte of any slot is written: not the bytes of a u8 array between
+ *    two samples at step 2, not the 8 bytes next to a written u64.  No store is
+ *    wider than an element unless every byte it covers is a sample's.
+ *  - A chunk that is untouched, or outside the box's hull range, is never
+ *    dereferenced: its table entry may hold anything.
+ *  - Equivalently: the slots end up as after zcg_read_region of the hull into
+ *    a scratch array, scratch[::step] = view, and zcg_write_region of the hull,
+ *    restricted to touched chunks whose entry is not NULL.
+ *  - Status words are zcg_read_regions_s': a box with shape[d] >
+ *    r->bbox_shape[d] or step[d] == 0 gets ZCG_ERR_INVALID_INPUT; a hull extent
+ *    plus chunk_shape[d] - 1 that reaches 2^32 gets ZCG_ERR_UNSUPPORTED; a hull
+ *    whose grid range is not inside the table's range gets
+ *    ZCG_ERR_INVALID_INPUT.  Nothing of such a box is written, and the other
+ *    boxes are unaffected.  Every box's status word is written.
+ *  - A box with a zero extent, or one that visits no chunk, is ZCG_OK and
+ *    writes nothing.
+ *  - The call-level returns are zcg_read_regions_s': r->bbox_shape[d] +
+ *    chunk_shape[d] - 1 >= 2^32 and n_boxes x the bound's elements >= 2^62
+ *    return ZCG_ERR_UNSUPPORTED; n_boxes == 0 returns ZCG_OK and launches
+ *    nothing.
+ *  - Asynchronous on `stream`: two launches whatever the boxes (the plan, and
+ *    the walk), no allocation, no synchronization with the host.  d_boxes is
+ *    read when the kernels run, so a captured graph replays with new offsets,
+ *    sample counts, STEPS, strides and bases inside the bound.  Work follows
+ *    the sum of the boxes' SAMPLES, not their hulls.
+ *  - Overlapping boxes: zcg_write_regions' rule.  A sample two boxes share ends
+ *    up with one of the values, whole; which box wins is unspecified.  Callers
+ *    who need "the later box wins" split the call with zcg_regions_s_waves and
+ *    launch the waves in order on one stream (each with its own part of
+ *    d_status; d_scratch may be shared). */
+int zcg_write_regions_s(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+                        void* const* d_chunk_table, const zcg_sbox* d_boxes, uint32_t n_boxes,
+                        void* d_scratch, int32_t* d_status, void* stream);
+
+/* zcg_regions_v_waves for strided boxes (`shapes`: sample counts, `steps`:
+ * n_boxes*ndim, box-major); host code, no GPU and no context.  Greedy and
+ * consecutive, exactly as zcg_regions_v_waves: box b opens a new wave if and
+ * only if it intersects a box of the current wave.
+ *  - Two strided boxes intersect if and only if, in every dimension, the
+ *    progressions {o1 + i*s1, i < c1} and {o2 + j*s2, j < c2} share an index.
+ *    The test is exact (o2 - o1 divisible by gcd(s1, s2), and the least common
+ *    index at or above max(o1, o2) not past either last sample), done as a
+ *    congruence in 128-bit arithmetic without a loop over samples.  Even and
+ *    odd planes of one hull therefore land in ONE wave.
+ *  - If a hull end (offset + (count-1)*step + 1) of either box passes 2^64-1
+ *    along some dimension, the pair is compared by the interval test of the
+ *    hulls with saturated ends instead: conservative, and still ordered.
+ *  - A box with a step of 0 or a zero extent intersects nothing.  The step of
+ *    a dimension with a count of 1 is irrelevant.
+ *  - With every step 1 the result is zcg_regions_v_waves'.
+ *  - Boxes are hashed into cells by their hulls, as zcg_regions_v_waves does by
+ *    their extents: the cell holds the largest hull (r->bbox_shape is not
+ *    used), and the cost degrades in the same way.
+ * Returns the number of waves; 0 for n_boxes == 0 or a NULL argument. */
+uint32_t zcg_regions_s_waves(const zcg_region* r, const uint64_t* offsets, const uint64_t* shapes,
+                             const uint64_t* steps, uint32_t n_boxes, uint32_t* wave_of);
 
 /* ---- FilesystemHierarchy chunk files ---------------
  * The e2e path's two ends: chunk files read into pinned staging by a pool of
@@ -839,6 +909,50 @@ int zcg_store_read_boxes_s_device(zcg_ctx* ctx, const zcg_array_meta* meta, cons
 int zcg_store_read_boxes_s(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
                            const uint64_t* box_shapes, const uint64_t* box_steps, const uint64_t* offsets,
                            void* const* outs, uint32_t n_boxes, uint64_t slot_budget_bytes, uint32_t io_threads);
+
+/* ---- write_ndarray for many boxes with a step per dimension ----------------
+ * zcg_store_write_boxes_v[_device] for strided boxes (a[o::k] = x in one call):
+ * `box_shapes` holds the n_boxes*ndim SAMPLE COUNTS and `box_steps` the
+ * n_boxes*ndim steps (>= 1), box-major, as `offsets` does.  The store ends up
+ * as if, for box 0, 1, ... in order, the box's hull had been read
+ * (read_ndarray, filled), the samples overlaid on it, and the hull's TOUCHED
+ * chunks written by write_ndarray.  Everything carries over from the _v write
+ * calls word for word, with the read side's _s differences:
+ *  - The chunks read, encoded and written are the union of the boxes' touched
+ *    chunks (zcg_region_s_chunks), each once per group.  A chunk of a hull's
+ *    range that holds no sample is never opened, created, decoded or rewritten.
+ *  - Chunks read first: take the lowest-numbered box that touches the chunk.
+ *    The file is not read if and only if, along every dimension, every index of
+ *    the chunk's nominal bounds is a sample of that box: that needs a step of 1
+ *    (or a chunk extent of 1) and the run of samples across the chunk.  A
+ *    corrupt old file is then harmless.  Otherwise the file is read and
+ *    decoded, and an absent file makes the slot start as fill value.
+ *  - The slot budget, the grouping and the in-grid check (ZCG_ERR_INVALID_INPUT
+ *    before any file is touched) count touched chunks only.
+ *  - The 2^24 limit applies to the chunk TABLE, which covers the union of the
+ *    hulls' grid ranges -> ZCG_ERR_UNSUPPORTED.
+ *  - A step of 0 -> ZCG_ERR_INVALID_INPUT; a hull extent + chunk extent - 1
+ *    >= 2^32 along a dimension -> ZCG_ERR_UNSUPPORTED; both before any file is
+ *    touched.
+ *  - Order: inside a group the boxes are scattered by zcg_write_regions_s in
+ *    the waves of zcg_regions_s_waves, in order on one stream: a later box wins
+ *    every sample it shares with an earlier one, and interleaved boxes (even
+ *    and odd planes) share a wave.
+ *  - A call whose steps are all 1 and that has no empty box takes the _v plan
+ *    and kernels, chunk for chunk and error for error.
+ *  - The _device form takes box i from the DEVICE view d_ins[i] with the
+ *    strides in_strides + i*ndim (NULL: dense in the chunk memory order, with
+ *    the box's sample counts).  The host form takes box i from the HOST buffer
+ *    ins[i], dense in the chunk memory order with its own sample counts.
+ * n_boxes = 1 with every step 1 is the reference's write_ndarray. */
+int zcg_store_write_boxes_s_device(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                                   const uint64_t* box_shapes, const uint64_t* box_steps, const int64_t* in_strides,
+                                   const uint64_t* offsets, const void* const* d_ins, uint32_t n_boxes,
+                                   uint64_t slot_budget_bytes, uint32_t io_threads);
+int zcg_store_write_boxes_s(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                            const uint64_t* box_shapes, const uint64_t* box_steps, const uint64_t* offsets,
+                            const void* const* ins, uint32_t n_boxes, uint64_t slot_budget_bytes,
+                            uint32_t io_threads);
 
 #ifdef __cplusplus
 }

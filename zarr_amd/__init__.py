@@ -14,8 +14,8 @@ from .chunk import (DefaultChunk, SliceDataChunk, VecDataChunk, ZarrIOError, che
                     read_chunks_host)
 from .storage import FilesystemHierarchy, get_chunk_key
 from .region import (BoundingBox, assemble_regions_s, read_ndarray, read_ndarrays, read_ndarrays_s, read_ndarrays_v,
-                     region_s_chunks, regions_s_grid, regions_s_scratch_bytes, sboxes_tensor, write_ndarray,
-                     write_ndarrays, write_ndarrays_v)
+                     region_s_chunks, regions_s_grid, regions_s_scratch_bytes, regions_s_waves, sboxes_tensor,
+                     scatter_regions_s, write_ndarray, write_ndarrays, write_ndarrays_s, write_ndarrays_v)
 from ._native import NativeUnavailable
 
 __all__ = [
@@ -24,6 +24,7 @@ __all__ = [
     "NATIVE_ENDIAN", "NativeUnavailable", "REFLECTED_TYPES", "Raw", "SliceDataChunk",
     "VecDataChunk", "Xz", "ZarrIOError", "check_array_type", "effective_type", "get_chunk_key",
     "assemble_regions_s", "read_chunks_host", "read_ndarray", "read_ndarrays", "read_ndarrays_s", "read_ndarrays_v",
-    "region_s_chunks", "regions_s_grid", "regions_s_scratch_bytes", "sboxes_tensor", "u64_ceil_div", "write_ndarray",
-    "write_ndarrays", "write_ndarrays_v", "zarr_type",
+    "region_s_chunks", "regions_s_grid", "regions_s_scratch_bytes", "regions_s_waves", "sboxes_tensor",
+    "scatter_regions_s", "u64_ceil_div", "write_ndarray", "write_ndarrays", "write_ndarrays_s", "write_ndarrays_v",
+    "zarr_type",
 ]

@@ -58,6 +58,7 @@ EXPORTED_SYMBOLS = (
     "zcg_store_write_boxes_v_device", "zcg_store_write_boxes_v",
     "zcg_region_s_chunks", "zcg_regions_s_grid", "zcg_regions_s_scratch_bytes", "zcg_read_regions_s",
     "zcg_store_read_boxes_s_device", "zcg_store_read_boxes_s",
+    "zcg_write_regions_s", "zcg_regions_s_waves", "zcg_store_write_boxes_s_device", "zcg_store_write_boxes_s",
 )
 
 
@@ -271,6 +272,16 @@ def load_library(path: str = LIB_PATH):
         L.zcg_store_read_boxes_s.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
                                              vp, vp, vp, vp, u32, u64, u32]
         L.zcg_store_read_boxes_s.restype = ctypes.c_int
+        L.zcg_write_regions_s.argtypes = [vp, ctypes.POINTER(Region), vp, vp, vp, vp, u32, vp, vp, vp]
+        L.zcg_write_regions_s.restype = ctypes.c_int
+        L.zcg_regions_s_waves.argtypes = [ctypes.POINTER(Region), vp, vp, vp, u32, vp]
+        L.zcg_regions_s_waves.restype = u32
+        L.zcg_store_write_boxes_s_device.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
+                                                     vp, vp, vp, vp, vp, u32, u64, u32]
+        L.zcg_store_write_boxes_s_device.restype = ctypes.c_int
+        L.zcg_store_write_boxes_s.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
+                                              vp, vp, vp, vp, u32, u64, u32]
+        L.zcg_store_write_boxes_s.restype = ctypes.c_int
         _lib = L
         return L
 

@@ -757,7 +757,8 @@ uint64_t zcg_regions_v_scratch_bytes(uint32_t n_boxes) { return (regions_v_prefi
 uint64_t zcg_regions_s_scratch_bytes(uint32_t n_boxes) { return zcg_regions_v_scratch_bytes(n_boxes); }
 
 // dir 0: zcg_read_regions_v, 1: zcg_write_regions_v (d_boxes: zcg_vbox); 2:
-// zcg_read_regions_s (d_boxes: zcg_sbox, the bound is on the sample counts)
+// zcg_read_regions_s, 3: zcg_write_regions_s (d_boxes: zcg_sbox, the bound is
+// on the sample counts)
 static int regions_v_call(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
                           const void* const* d_chunk_table, const void* d_boxes, uint32_t n_boxes,
                           void* d_scratch, int32_t* d_status, void* stream, uint32_t dir) {
@@ -769,7 +770,7 @@ static int regions_v_call(zcg_ctx* ctx, const zcg_region* r, const uint64_t* tab
                                "2^32 elements",
                                &w, &entries);
     if (rc != ZCG_OK) return rc;
-    if (dir == 1) w.fill = 0;
+    if (dir == 1 || dir == 3) w.fill = 0;
     BoxTable bt{};
     bt.nboxes = n_boxes;
     uint64_t total = 1;  // every extent is below 2^32: saturate at 2^63
@@ -793,11 +794,13 @@ static int regions_v_call(zcg_ctx* ctx, const zcg_region* r, const uint64_t* tab
     }
     (void)hipSetDevice(ctx->device);
     const hipError_t e =
+        dir == 3 ? launch_regions_sw(w, bt, (void* const*)d_chunk_table, (const zcg_sbox*)d_boxes, d_scratch,
+                                     d_status, (hipStream_t)stream) :
         dir == 2 ? launch_regions_s(w, bt, d_chunk_table, (const zcg_sbox*)d_boxes, d_scratch, d_status,
                                     (hipStream_t)stream)
                  : launch_regions_v(w, bt, d_chunk_table, (const zcg_vbox*)d_boxes, d_scratch, d_status, dir,
                                     (hipStream_t)stream);
-    if (e != hipSuccess) return fail(ctx, e, dir == 2 ? "regions_s launch" : "regions_v launch");
+    if (e != hipSuccess) return fail(ctx, e, dir >= 2 ? "regions_s launch" : "regions_v launch");
     return ZCG_OK;
 }
 
@@ -820,6 +823,13 @@ int zcg_read_regions_s(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_
                        int32_t* d_status, void* stream) {
     return regions_v_call(ctx, r, table_lo, table_n, d_chunk_table, d_boxes, n_boxes, d_scratch, d_status, stream,
                           2);
+}
+
+int zcg_write_regions_s(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+                        void* const* d_chunk_table, const zcg_sbox* d_boxes, uint32_t n_boxes, void* d_scratch,
+                        int32_t* d_status, void* stream) {
+    return regions_v_call(ctx, r, table_lo, table_n, (const void* const*)d_chunk_table, d_boxes, n_boxes, d_scratch,
+                          d_status, stream, 3);
 }
 
 }  // extern "C"

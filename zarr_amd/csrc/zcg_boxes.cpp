@@ -18,10 +18,13 @@
 // keep the one-shape kernels (zcg_read_regions / zcg_write_regions); boxes of
 // differing shapes go through zcg_read_regions_v / zcg_write_regions_v.
 //
-// The _s read calls add a step per box and dimension: the planner then takes a
+// The _s calls add a step per box and dimension: the planner then takes a
 // box's chunks from zcg_region_s_chunks (the touched chunks, a product of
 // per-dimension index sets) instead of the hull's whole grid range, and the
-// boxes are assembled by zcg_read_regions_s.
+// boxes are assembled by zcg_read_regions_s or scattered by
+// zcg_write_regions_s in the waves of zcg_regions_s_waves.  On the write side
+// a touched chunk is read first unless its first box covers it sample by
+// sample (step 1, or a chunk extent of 1, along every dimension).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -112,6 +115,42 @@ struct Plan {
     }
 };
 
+// What the box calls refuse from `meta` alone, and what the strided calls
+// refuse from one box's sample counts and steps alone.  `say` receives the
+// message; plan_boxes and the context-free check of the strided write entries
+// (strided_write_args) both go through these, so the rules exist once.
+template <class Say>
+int meta_args_status(const std::string& what, const zcg_array_meta* meta, Say say) {
+    if (meta->ndim != meta->chunk_ndim) {
+        say(what + ": shape and chunk_shape differ in their number of dimensions");
+        return ZCG_ERR_INVALID_DATA;
+    }
+    if (meta->ndim < 1 || meta->ndim > ZCG_MAX_DIMS) return ZCG_ERR_INVALID_INPUT;
+    if (meta->dtype_kind == ZCG_DT_RAW) {
+        say(what + ": raw (rN) element types have no ndarray form");
+        return ZCG_ERR_INVALID_INPUT;
+    }
+    return ZCG_OK;
+}
+
+template <class Say>
+int sbox_args_status(const std::string& what, uint32_t b, uint32_t nd, const uint64_t* counts, const uint64_t* stp,
+                     const uint64_t* chunk_shape, Say say) {
+    for (uint32_t d = 0; d < nd; d++) {
+        const uint64_t c = counts[d];
+        if (stp[d] == 0) {
+            say(what + ": box " + std::to_string(b) + " has a step of 0");
+            return ZCG_ERR_INVALID_INPUT;
+        }
+        if (c > 1 && (stp[d] >= (1ull << 32) || c > (1ull << 32) || (c - 1) * stp[d] + chunk_shape[d] >= (1ull << 32))) {
+            say(what + ": box " + std::to_string(b) +
+                ": hull extent + chunk extent along a dimension must stay below 2^32");
+            return ZCG_ERR_UNSUPPORTED;
+        }
+    }
+    return ZCG_OK;
+}
+
 // Argument checks, the in-bounds check of every visited chunk (the reference
 // panics at storage.rs:217) and the grouping under the slot budget.  `what`
 // prefixes the messages.  host == true: boxes are host buffers, each dense in
@@ -119,8 +158,8 @@ struct Plan {
 // varied == false: every box has the shape box_shape (ndim) and, as a device
 // view, the strides `strides` (ndim); true: box_shape and strides hold
 // n_boxes * ndim entries, box-major, and NULL strides mean dense views.
-// cover == true (write): Group::read_first is filled in.  box_steps (varied,
-// read): n_boxes * ndim steps, box_shape then holds sample counts and a box's
+// cover == true (write): Group::read_first is filled in.  box_steps (varied):
+// n_boxes * ndim steps, box_shape then holds sample counts and a box's
 // chunks are the touched ones; NULL: dense boxes.
 int plan_boxes(zcg_ctx* ctx, const std::string& what, const zcg_array_meta* meta, const char* root, const char* path,
                const uint64_t* box_shape, const uint64_t* box_steps, const int64_t* strides, bool varied,
@@ -131,16 +170,10 @@ int plan_boxes(zcg_ctx* ctx, const std::string& what, const zcg_array_meta* meta
         (!host && !strides && !varied))
         return ZCG_ERR_INVALID_INPUT;
     if (n_boxes && (!offsets || !bufs)) return ZCG_ERR_INVALID_INPUT;
-    if (meta->ndim != meta->chunk_ndim) {
-        ctx_set_error(ctx, what + ": shape and chunk_shape differ in their number of dimensions");
-        return ZCG_ERR_INVALID_DATA;
-    }
+    auto say = [&](const std::string& e) { ctx_set_error(ctx, e); };
+    const int mrc = meta_args_status(what, meta, say);
+    if (mrc != ZCG_OK) return mrc;
     const uint32_t nd = meta->ndim;
-    if (nd < 1 || nd > ZCG_MAX_DIMS) return ZCG_ERR_INVALID_INPUT;
-    if (meta->dtype_kind == ZCG_DT_RAW) {
-        ctx_set_error(ctx, what + ": raw (rN) element types have no ndarray form");
-        return ZCG_ERR_INVALID_INPUT;
-    }
     const uint32_t es = meta->array.dtype.elem_size;
     if (es != 1 && es != 2 && es != 4 && es != 8) return ZCG_ERR_INVALID_INPUT;
     P.nd = nd;
@@ -238,19 +271,8 @@ int plan_boxes(zcg_ctx* ctx, const std::string& what, const zcg_array_meta* meta
             uint64_t cnt, range, m[ZCG_MAX_DIMS];
             if (box_steps) {
                 const uint64_t* stp = box_steps + (size_t)b * nd;
-                for (uint32_t d = 0; d < nd; d++) {
-                    const uint64_t c = rb.bbox_shape[d];
-                    if (stp[d] == 0) {
-                        ctx_set_error(ctx, what + ": box " + std::to_string(b) + " has a step of 0");
-                        return ZCG_ERR_INVALID_INPUT;
-                    }
-                    if (c > 1 && (stp[d] >= (1ull << 32) || c > (1ull << 32) ||
-                                  (c - 1) * stp[d] + rb.chunk_shape[d] >= (1ull << 32))) {
-                        ctx_set_error(ctx, what + ": box " + std::to_string(b) +
-                                               ": hull extent + chunk extent along a dimension must stay below 2^32");
-                        return ZCG_ERR_UNSUPPORTED;
-                    }
-                }
+                const int brc = sbox_args_status(what, b, nd, rb.bbox_shape, stp, rb.chunk_shape, say);
+                if (brc != ZCG_OK) return brc;
                 cnt = zcg_region_s_chunks(&rb, rb.bbox_offset, rb.bbox_shape, stp, lo, n, nullptr);
                 range = cnt ? 1 : 0;
                 for (uint32_t d = 0; cnt && d < nd; d++)
@@ -296,7 +318,12 @@ int plan_boxes(zcg_ctx* ctx, const std::string& what, const zcg_array_meta* meta
                         rem /= m[d];
                         if (cover) {  // write_bb == nom_chunk_bb (ndarray.rs:327), per dimension
                             const uint64_t cs = rb.chunk_shape[d], o = rb.bbox_offset[d], o1 = o + rb.bbox_shape[d];
-                            part |= c * cs < o || c * cs + cs > (o1 < o ? ~0ull : o1);
+                            // strided: every index of the chunk's nominal bounds must be a sample.  A
+                            // touched chunk of extent 1 is its one sample; a wider one needs step 1
+                            // (a lone sample has none) and the run of samples across it
+                            const uint64_t stp = box_steps && rb.bbox_shape[d] > 1 ? box_steps[(size_t)b * nd + d] : 1;
+                            const bool unit = box_steps && cs == 1;
+                            part |= !unit && (stp != 1 || c * cs < o || c * cs + cs > (o1 < o ? ~0ull : o1));
                         }
                     }
                     if (seen.emplace(key, part ? 1 : 0).second) fresh.push_back(key);
@@ -433,9 +460,13 @@ std::vector<uint8_t> box_records(const Plan& P, const uint64_t* offsets, const v
 // shapes (d_scratch: zcg_regions_v_scratch_bytes(count) bytes).
 int regions_launch(zcg_ctx* ctx, const Plan& P, const uint64_t* lo, const uint64_t* n, void* d_table, void* d_recs,
                    uint32_t first, uint32_t count, void* d_scratch, int32_t* d_status, hipStream_t s, uint32_t dir) {
-    if (P.steps)
-        return zcg_read_regions_s(ctx, &P.r, lo, n, (const void* const*)d_table, (const zcg_sbox*)d_recs + first, count,
-                                  d_scratch, d_status + first, (void*)s);
+    if (P.steps) {
+        const zcg_sbox* bx = (const zcg_sbox*)d_recs + first;
+        return dir ? zcg_write_regions_s(ctx, &P.r, lo, n, (void* const*)d_table, bx, count, d_scratch,
+                                         d_status + first, (void*)s)
+                   : zcg_read_regions_s(ctx, &P.r, lo, n, (const void* const*)d_table, bx, count, d_scratch,
+                                        d_status + first, (void*)s);
+    }
     if (P.varied) {
         const zcg_vbox* bx = (const zcg_vbox*)d_recs + first;
         return dir ? zcg_write_regions_v(ctx, &P.r, lo, n, (void* const*)d_table, bx, count, d_scratch,
@@ -552,15 +583,16 @@ int read_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const
 // slots of chunks whose first visiting box is partial are read (or, absent,
 // prefilled); the boxes are scattered wave by wave; every slot is encoded and
 // written.  host == true: ins are host buffers, dense in the chunk memory
-// order.  varied: plan_boxes'.
+// order.  varied, box_steps: plan_boxes'.
 int write_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
-                const uint64_t* box_shape, const int64_t* in_strides, bool varied, const uint64_t* offsets,
+                const uint64_t* box_shape, const uint64_t* box_steps, const int64_t* in_strides, bool varied,
+                const uint64_t* offsets,
                 const void* const* ins, uint32_t n_boxes, uint64_t slot_budget_bytes, uint32_t io_threads,
                 bool host) {
     const std::string what = "write_boxes";
     Plan P;
     // 1. before any file is read or written
-    const int prc = plan_boxes(ctx, what, meta, root, path, box_shape, nullptr, in_strides, varied, 0, offsets, ins,
+    const int prc = plan_boxes(ctx, what, meta, root, path, box_shape, box_steps, in_strides, varied, 0, offsets, ins,
                                n_boxes, slot_budget_bytes, host, true, P);
     if (prc != ZCG_OK) return prc;
     if (P.nothing || P.at[n_boxes] == 0) return ZCG_OK;
@@ -657,7 +689,10 @@ int write_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, cons
 
         // 4. the scatter, wave by wave: a later box wins what it shares with an earlier one
         wave_of.resize(nb);
-        if (P.varied)
+        if (P.steps)
+            zcg_regions_s_waves(&r, offsets + (size_t)G.b0 * nd, box_shape + (size_t)G.b0 * nd,
+                                box_steps + (size_t)G.b0 * nd, nb, wave_of.data());
+        else if (P.varied)
             zcg_regions_v_waves(&r, offsets + (size_t)G.b0 * nd, box_shape + (size_t)G.b0 * nd, nb, wave_of.data());
         else
             zcg_regions_waves(&r, offsets + (size_t)G.b0 * nd, nb, wave_of.data());
@@ -698,13 +733,78 @@ struct CellRange {
     uint64_t lo, hi;
 };
 
-// zcg_regions_waves and zcg_regions_v_waves: box b's shape is shapes + b * sstep
-// (sstep 0: one shape for all).
+typedef unsigned __int128 u128;
+
+// Do the progressions {o1 + i*s1, i < c1} and {o2 + j*s2, j < c2} share an
+// index?  c1, c2 >= 1, s1, s2 >= 1, and both last samples are below 2^64.
+// Exact, by the congruence x = o1 (mod s1), x = o2 (mod s2): solvable iff
+// gcd(s1, s2) divides o2 - o1; the least solution at or above max(o1, o2) must
+// not pass either last sample.  No loop over samples.
+bool progressions_meet(uint64_t o1, uint64_t c1, uint64_t s1, uint64_t o2, uint64_t c2, uint64_t s2) {
+    if (c1 < 2) s1 = 1;  // the step of a lone sample is irrelevant
+    if (c2 < 2) s2 = 1;
+    if (o1 > o2) { std::swap(o1, o2); std::swap(c1, c2); std::swap(s1, s2); }
+    const u128 last1 = (u128)o1 + (u128)(c1 - 1) * s1, last2 = (u128)o2 + (u128)(c2 - 1) * s2;
+    const u128 last = std::min(last1, last2);
+    if (o2 > last) return false;
+    uint64_t g = s1, h = s2;
+    while (h) { const uint64_t t = g % h; g = h; h = t; }
+    const uint64_t diff = o2 - o1;
+    if (diff % g) return false;
+    // x = o1 + s1*k with (s1/g)*k = diff/g (mod m), m = s2/g: k = (diff/g) * inverse of s1/g mod m
+    const uint64_t m = s2 / g, a = (s1 / g) % m;
+    uint64_t k = 0;
+    if (m > 1) {
+        __int128 t0 = 0, t1 = 1;  // extended Euclid: t1 * a = r1 (mod m)
+        uint64_t r0 = m, r1 = a;
+        while (r1 > 1) {
+            const uint64_t q = r0 / r1, r2 = r0 - q * r1;
+            const __int128 t2 = t0 - (__int128)q * t1;
+            r0 = r1; r1 = r2; t0 = t1; t1 = t2;
+        }
+        const uint64_t inv = (uint64_t)(((t1 % (__int128)m) + m) % m);  // gcd(a, m) = 1, so r1 ends at 1
+        k = (uint64_t)((u128)((diff / g) % m) * inv % m);
+    }
+    u128 x = (u128)o1 + (u128)s1 * k;  // the least solution at or above o1; the next ones are lcm apart
+    if (x < o2) {
+        const u128 lcm = (u128)(s1 / g) * s2, need = (u128)o2 - x;
+        if (lcm > last) return false;  // the next solution is past every sample
+        x += (need + lcm - 1) / lcm * lcm;
+    }
+    return x <= last;
+}
+
+// zcg_regions_waves, zcg_regions_v_waves and zcg_regions_s_waves: box b's
+// shape is shapes + b * sstep (sstep 0: one shape for all); steps (n_boxes *
+// ndim, or NULL): shapes are sample counts and two boxes intersect when their
+// progressions do.  Cells and hashing go by the hulls.
 uint32_t regions_waves(const zcg_region* r, const uint64_t* offsets, const uint64_t* shapes, size_t sstep,
-                       uint32_t n_boxes, uint32_t* wave_of) {
+                       const uint64_t* steps, uint32_t n_boxes, uint32_t* wave_of) {
     if (!r || !offsets || !shapes || !wave_of || n_boxes == 0) return 0;
     const uint32_t nd = r->ndim;
     if (nd < 1 || nd > ZCG_MAX_DIMS) return 0;
+    // strided: the hulls' extents (saturating) stand in for the shapes below;
+    // a box with a step of 0 gets a zero extent and intersects nothing
+    const uint64_t* counts = shapes;
+    std::vector<uint64_t> hulls;
+    std::vector<uint8_t> over;  // per box: a hull end passes 2^64
+    if (steps) {
+        hulls.assign((size_t)n_boxes * nd, 0);
+        over.assign(n_boxes, 0);
+        for (uint32_t b = 0; b < n_boxes; b++) {
+            bool stepped = true;
+            for (uint32_t d = 0; d < nd; d++) stepped &= steps[(size_t)b * nd + d] != 0;
+            for (uint32_t d = 0; stepped && d < nd; d++) {
+                const size_t i = (size_t)b * nd + d;
+                const uint64_t c = counts[i];
+                const u128 e = c ? (u128)(c - 1) * (c > 1 ? steps[i] : 1) + 1 : 0;
+                hulls[i] = e > ~0ull ? ~0ull : (uint64_t)e;
+                if (e + offsets[i] > ~0ull) over[b] = 1;
+            }
+        }
+        shapes = hulls.data();
+        sstep = nd;
+    }
     // Cells: per dimension the smallest multiple of the chunk extent that holds
     // the largest box extent (r->bbox_shape, unless a box exceeds it), so a box
     // lies in at most two cells per dimension and two boxes that intersect
@@ -712,7 +812,7 @@ uint32_t regions_waves(const zcg_region* r, const uint64_t* offsets, const uint6
     // are registered in one of its cells.
     uint64_t cell[ZCG_MAX_DIMS];
     for (uint32_t d = 0; d < nd; d++) {
-        uint64_t bs = sstep ? r->bbox_shape[d] : shapes[d];
+        uint64_t bs = steps ? 0 : sstep ? r->bbox_shape[d] : shapes[d];
         for (uint32_t b = 0; sstep && b < n_boxes; b++) bs = std::max(bs, shapes[(size_t)b * sstep + d]);
         const uint64_t cs = r->chunk_shape[d] ? r->chunk_shape[d] : 1;
         const uint64_t k = std::max<uint64_t>(bs / cs + (bs % cs ? 1 : 0), 1);
@@ -758,8 +858,11 @@ uint32_t regions_waves(const zcg_region* r, const uint64_t* offsets, const uint6
             for (uint32_t a : it->second) {
                 const uint64_t* oa = offsets + (size_t)a * nd;
                 bool meet = true;
+                const bool exact = steps && !over[a] && !over[b];  // else the (saturated) hulls' intervals
                 for (uint32_t d = 0; d < nd && meet; d++)
-                    meet = std::max(oa[d], ob[d]) < std::min(end_of(a, d), end_of(b, d));
+                    meet = exact ? progressions_meet(oa[d], counts[(size_t)a * nd + d], steps[(size_t)a * nd + d],
+                                                     ob[d], counts[(size_t)b * nd + d], steps[(size_t)b * nd + d])
+                                 : std::max(oa[d], ob[d]) < std::min(end_of(a, d), end_of(b, d));
                 if (meet) { hit = true; break; }
             }
         }
@@ -777,26 +880,32 @@ uint32_t regions_waves(const zcg_region* r, const uint64_t* offsets, const uint6
 
 extern "C" uint32_t zcg_regions_waves(const zcg_region* r, const uint64_t* offsets, uint32_t n_boxes,
                                       uint32_t* wave_of) {
-    return regions_waves(r, offsets, r ? r->bbox_shape : nullptr, 0, n_boxes, wave_of);
+    return regions_waves(r, offsets, r ? r->bbox_shape : nullptr, 0, nullptr, n_boxes, wave_of);
 }
 
 extern "C" uint32_t zcg_regions_v_waves(const zcg_region* r, const uint64_t* offsets, const uint64_t* shapes,
                                         uint32_t n_boxes, uint32_t* wave_of) {
-    return regions_waves(r, offsets, shapes, r ? r->ndim : 0, n_boxes, wave_of);
+    return regions_waves(r, offsets, shapes, r ? r->ndim : 0, nullptr, n_boxes, wave_of);
+}
+
+extern "C" uint32_t zcg_regions_s_waves(const zcg_region* r, const uint64_t* offsets, const uint64_t* shapes,
+                                        const uint64_t* steps, uint32_t n_boxes, uint32_t* wave_of) {
+    if (!steps) return 0;
+    return regions_waves(r, offsets, shapes, r ? r->ndim : 0, steps, n_boxes, wave_of);
 }
 
 extern "C" int zcg_store_write_boxes_device(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root,
                                             const char* path, const uint64_t* box_shape, const int64_t* in_strides,
                                             const uint64_t* offsets, const void* const* d_ins, uint32_t n_boxes,
                                             uint64_t slot_budget_bytes, uint32_t io_threads) {
-    return write_boxes(ctx, meta, root, path, box_shape, in_strides, false, offsets, d_ins, n_boxes,
+    return write_boxes(ctx, meta, root, path, box_shape, nullptr, in_strides, false, offsets, d_ins, n_boxes,
                        slot_budget_bytes, io_threads, false);
 }
 
 extern "C" int zcg_store_write_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
                                      const uint64_t* box_shape, const uint64_t* offsets, const void* const* ins,
                                      uint32_t n_boxes, uint64_t slot_budget_bytes, uint32_t io_threads) {
-    return write_boxes(ctx, meta, root, path, box_shape, nullptr, false, offsets, ins, n_boxes, slot_budget_bytes,
+    return write_boxes(ctx, meta, root, path, box_shape, nullptr, nullptr, false, offsets, ins, n_boxes, slot_budget_bytes,
                        io_threads, true);
 }
 
@@ -836,14 +945,14 @@ extern "C" int zcg_store_write_boxes_v_device(zcg_ctx* ctx, const zcg_array_meta
                                               const int64_t* in_strides, const uint64_t* offsets,
                                               const void* const* d_ins, uint32_t n_boxes,
                                               uint64_t slot_budget_bytes, uint32_t io_threads) {
-    return write_boxes(ctx, meta, root, path, box_shapes, in_strides, true, offsets, d_ins, n_boxes,
+    return write_boxes(ctx, meta, root, path, box_shapes, nullptr, in_strides, true, offsets, d_ins, n_boxes,
                        slot_budget_bytes, io_threads, false);
 }
 
 extern "C" int zcg_store_write_boxes_v(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
                                        const uint64_t* box_shapes, const uint64_t* offsets, const void* const* ins,
                                        uint32_t n_boxes, uint64_t slot_budget_bytes, uint32_t io_threads) {
-    return write_boxes(ctx, meta, root, path, box_shapes, nullptr, true, offsets, ins, n_boxes, slot_budget_bytes,
+    return write_boxes(ctx, meta, root, path, box_shapes, nullptr, nullptr, true, offsets, ins, n_boxes, slot_budget_bytes,
                        io_threads, true);
 }
 
@@ -879,4 +988,42 @@ extern "C" int zcg_store_read_boxes_s(zcg_ctx* ctx, const zcg_array_meta* meta, 
     if (all_dense(meta, box_shapes, box_steps, n_boxes)) box_steps = nullptr;
     return read_boxes(ctx, meta, root, path, box_shapes, box_steps, nullptr, true, 1, offsets, outs, n_boxes,
                       slot_budget_bytes, io_threads, true);
+}
+
+// What the strided write calls refuse from their arguments alone, by
+// plan_boxes' own checks but without needing a context: a caller (or a test)
+// learns of them on a machine without a GPU.  ZCG_OK: go on.
+static int strided_write_args(zcg_ctx* ctx, const zcg_array_meta* meta, const uint64_t* box_shapes,
+                              const uint64_t* box_steps, uint32_t n_boxes) {
+    const std::string what = "write_boxes";
+    auto say = [&](const std::string& e) { if (ctx) ctx_set_error(ctx, e); };
+    if (!meta || (n_boxes && (!box_shapes || !box_steps))) return ZCG_ERR_INVALID_INPUT;
+    int rc = meta_args_status(what, meta, say);
+    const uint32_t nd = meta->ndim;
+    for (uint32_t b = 0; rc == ZCG_OK && b < n_boxes; b++)
+        rc = sbox_args_status(what, b, nd, box_shapes + (size_t)b * nd, box_steps + (size_t)b * nd, meta->chunk_shape, say);
+    return rc;
+}
+
+extern "C" int zcg_store_write_boxes_s_device(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root,
+                                              const char* path, const uint64_t* box_shapes, const uint64_t* box_steps,
+                                              const int64_t* in_strides, const uint64_t* offsets,
+                                              const void* const* d_ins, uint32_t n_boxes,
+                                              uint64_t slot_budget_bytes, uint32_t io_threads) {
+    const int arc = strided_write_args(ctx, meta, box_shapes, box_steps, n_boxes);
+    if (arc != ZCG_OK) return arc;
+    if (all_dense(meta, box_shapes, box_steps, n_boxes)) box_steps = nullptr;
+    return write_boxes(ctx, meta, root, path, box_shapes, box_steps, in_strides, true, offsets, d_ins, n_boxes,
+                       slot_budget_bytes, io_threads, false);
+}
+
+extern "C" int zcg_store_write_boxes_s(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                                       const uint64_t* box_shapes, const uint64_t* box_steps, const uint64_t* offsets,
+                                       const void* const* ins, uint32_t n_boxes, uint64_t slot_budget_bytes,
+                                       uint32_t io_threads) {
+    const int arc = strided_write_args(ctx, meta, box_shapes, box_steps, n_boxes);
+    if (arc != ZCG_OK) return arc;
+    if (all_dense(meta, box_shapes, box_steps, n_boxes)) box_steps = nullptr;
+    return write_boxes(ctx, meta, root, path, box_shapes, box_steps, nullptr, true, offsets, ins, n_boxes,
+                       slot_budget_bytes, io_threads, true);
 }

@@ -411,6 +411,12 @@ hipError_t launch_regions_v(const RegionWalk& w, const BoxTable& bt, const void*
 // arguments, read direction only; w.bs bounds the sample counts.
 hipError_t launch_regions_s(const RegionWalk& w, const BoxTable& bt, const void* const* d_table,
                             const zcg_sbox* d_boxes, void* d_prefix, int32_t* d_status, hipStream_t s);
+// its plan launch alone (status words and the prefix sum of work units), and
+// the write direction (zcg_region_sw.hip), which plans with w.fill == 0
+hipError_t launch_regions_s_plan(const RegionWalk& w, const BoxTable& bt, const void* const* d_table,
+                                 const zcg_sbox* d_boxes, void* d_prefix, int32_t* d_status, hipStream_t s);
+hipError_t launch_regions_sw(const RegionWalk& w, const BoxTable& bt, void* const* d_table, const zcg_sbox* d_boxes,
+                             void* d_prefix, int32_t* d_status, hipStream_t s);
 // m device slots of D bytes (d_slots: DEVICE array of their bases, each a
 // multiple of `es`), filled with the element `fillv`
 hipError_t launch_slot_fill(void* const* d_slots, uint32_t m, uint64_t D, uint32_t es, uint64_t fillv,

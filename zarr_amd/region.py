@@ -619,15 +619,8 @@ def region_s_chunks(meta: ArrayMetadata, offset, shape, step, want_touched: bool
     return lo_l, n_l, [flags[at[d]:at[d + 1]].tolist() for d in range(nd)], count
 
 
-def assemble_regions_s(meta: ArrayMetadata, bound: Sequence[int], es: int, table, table_lo, table_n, boxes, status,
-                       fill: bool, fill_value: int, device: int = 0, stream=None, scratch=None) -> None:
-    """Device-level call for many strided boxes (zcg_read_regions_s):
-    assemble_regions_v with `boxes` = device tensor of _native.SBox records
-    (sboxes_tensor), each with its own sample counts, steps and view, and
-    `bound` = the largest sample count per dimension any box may have.  Table
-    entries of chunks that hold no sample are never read.  `scratch` = device
-    tensor of regions_s_scratch_bytes(B) bytes (None: allocated here, which a
-    captured call must not do).  Asynchronous."""
+def _regions_s(name: str, meta: ArrayMetadata, bound, es, table, table_lo, table_n, boxes, status, scratch, fill,
+               fill_value, device, stream) -> None:
     ctx = _native.context(device)
     nd = meta.get_ndim()
     r = _region(meta, BoundingBox([0] * nd, bound), es, fill, fill_value, [0] * nd)
@@ -637,13 +630,55 @@ def assemble_regions_s(meta: ArrayMetadata, bound: Sequence[int], es: int, table
     if n_boxes and scratch is None:
         import torch
         scratch = torch.empty(regions_s_scratch_bytes(n_boxes), dtype=torch.uint8, device=boxes.device)
-    st = ctx.lib.zcg_read_regions_s(ctx.handle, ctypes.byref(r), ctypes.addressof(lo), ctypes.addressof(n),
-                                    table.data_ptr() if table is not None else None,
-                                    boxes.data_ptr() if n_boxes else None, n_boxes,
-                                    scratch.data_ptr() if scratch is not None else None,
-                                    status.data_ptr() if status is not None else None,
-                                    _stream_handle(stream, device))
-    _raise_status(st, ctx, "read_regions_s")
+    st = getattr(ctx.lib, name)(ctx.handle, ctypes.byref(r), ctypes.addressof(lo), ctypes.addressof(n),
+                                table.data_ptr() if table is not None else None,
+                                boxes.data_ptr() if n_boxes else None, n_boxes,
+                                scratch.data_ptr() if scratch is not None else None,
+                                status.data_ptr() if status is not None else None, _stream_handle(stream, device))
+    _raise_status(st, ctx, name[4:])
+
+
+def assemble_regions_s(meta: ArrayMetadata, bound: Sequence[int], es: int, table, table_lo, table_n, boxes, status,
+                       fill: bool, fill_value: int, device: int = 0, stream=None, scratch=None) -> None:
+    """Device-level call for many strided boxes (zcg_read_regions_s):
+    assemble_regions_v with `boxes` = device tensor of _native.SBox records
+    (sboxes_tensor), each with its own sample counts, steps and view, and
+    `bound` = the largest sample count per dimension any box may have.  Table
+    entries of chunks that hold no sample are never read.  `scratch` = device
+    tensor of regions_s_scratch_bytes(B) bytes (None: allocated here, which a
+    captured call must not do).  Asynchronous."""
+    _regions_s("zcg_read_regions_s", meta, bound, es, table, table_lo, table_n, boxes, status, scratch, fill,
+               fill_value, device, stream)
+
+
+def scatter_regions_s(meta: ArrayMetadata, bound: Sequence[int], es: int, table, table_lo, table_n, boxes, status,
+                      scratch=None, device: int = 0, stream=None) -> None:
+    """Device-level inverse of assemble_regions_s (zcg_write_regions_s): sample
+    i of every box's view is written to array index offset + i * step in the
+    chunk slots of `table`, and no other byte of a slot is.  Table entries of
+    chunks that hold no sample are never read.  Boxes of one call that share a
+    sample leave either value; split the call with regions_s_waves where the
+    later box must win.  `scratch` as for assemble_regions_s.  Asynchronous."""
+    _regions_s("zcg_write_regions_s", meta, bound, es, table, table_lo, table_n, boxes, status, scratch, False, 0,
+               device, stream)
+
+
+def regions_s_waves(meta: ArrayMetadata, offsets, shapes, steps):
+    """zcg_regions_s_waves (host code, no GPU): regions_v_waves for strided
+    boxes (`shapes`: sample counts, `steps`: B x ndim) -> (number of waves,
+    wave index per box).  Two boxes intersect only where they share a sample,
+    so interleaved boxes (even and odd planes) stay in one wave."""
+    L = _native.load_library()
+    nd = meta.get_ndim()
+    r = _region(meta, BoundingBox([0] * nd, [0] * nd), 1, False, 0, [0] * nd)
+    offs = np.ascontiguousarray(np.array(offsets, dtype=np.uint64).reshape(-1, nd))
+    shp = np.ascontiguousarray(np.array(shapes, dtype=np.uint64).reshape(-1, nd))
+    stp = np.ascontiguousarray(np.array(steps, dtype=np.uint64).reshape(-1, nd))
+    B = offs.shape[0]
+    wave_of = np.zeros(max(B, 1), np.uint32)
+    n = L.zcg_regions_s_waves(ctypes.byref(r), offs.ctypes.data, shp.ctypes.data, stp.ctypes.data, B,
+                              wave_of.ctypes.data)
+    return int(n), [int(w) for w in wave_of[:B]]
 
 
 def _steps_arg(steps, B: int, nd: int) -> np.ndarray:
@@ -713,6 +748,79 @@ def read_ndarrays_s(hier, path_name: str, meta: ArrayMetadata, boxes: Sequence[B
     return [np.ndarray(tuple(bb.shape), dtype=dt, buffer=host, offset=at[b],
                        strides=tuple(s * es for s in strides[b])).copy(order=order)
             for b, bb in enumerate(boxes)]
+
+
+def _check_hulls(meta: ArrayMetadata, shp: np.ndarray, stp: np.ndarray) -> None:
+    """The native calls' limit, raised before a context is needed: positions in
+    a hull are 32-bit."""
+    for b in range(shp.shape[0]):
+        for d, cs in enumerate(meta.chunk_shape):
+            c, k = int(shp[b, d]), int(stp[b, d])
+            if c > 1 and (c - 1) * k + int(cs) >= 1 << 32:
+                raise ZarrIOError("Unsupported", f"box {b}: hull extent + chunk extent along a dimension must stay "
+                                                 "below 2^32")
+
+
+def write_ndarrays_s(hier, path_name: str, meta: ArrayMetadata, offsets, steps, arrays, device: int = 0,
+                     slot_budget_bytes: int = 0, flags: int = 0) -> None:
+    """a[offset::step] = array for many boxes in one native call
+    (zcg_store_write_boxes_s[_device]): element i of arrays[b] along d goes to
+    array index offsets[b][d] + i * step[d]; `steps` is B x ndim, or one step
+    vector for all boxes, and an array's shape is its box's sample counts.  The
+    store ends up as if, box by box in order, the hull had been read, the
+    samples overlaid and the hull's touched chunks written (a later box wins a
+    shared sample), but only the chunks that hold a sample are read, encoded
+    and written, each once.  `arrays` is a sequence of numpy arrays (the host
+    call) or of device tensors (the device call; any strides, the dtype's item
+    size must be the array's).  `flags`: decode flags for the chunks that are
+    read first."""
+    nd = meta.get_ndim()
+    arrays = list(arrays)
+    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64).reshape(-1, nd))
+    B = offs.shape[0]
+    if len(arrays) != B:
+        raise ZarrIOError("InvalidData", "Bounding boxes and arrays differ in number")
+    stp = _steps_arg(steps, B, nd)
+    tensor_in = B > 0 and all(not isinstance(a, np.ndarray) and hasattr(a, "data_ptr") for a in arrays)
+    order = "F" if meta.chunk_memory_layout == "F" else "C"
+    root, path = os.fsencode(hier.base_path), path_name.encode()
+    if tensor_in:
+        dt = np.dtype(meta.effective_type().numpy_dtype()).newbyteorder("=")
+        check_array_type(dt, meta)
+        for a in arrays:
+            if a.dim() != nd:
+                raise ZarrIOError("InvalidData", "Wrong number of dimensions")
+            if a.element_size() != dt.itemsize:
+                raise ZarrIOError("InvalidData", "Tensor and array differ in their element size")
+        shp = np.ascontiguousarray(np.array([list(a.shape) for a in arrays], dtype=np.uint64).reshape(-1, nd))
+        istr = np.ascontiguousarray(np.array([list(a.stride()) for a in arrays], dtype=np.int64).reshape(-1, nd))
+        _check_hulls(meta, shp, stp)
+        am = _native_meta(meta, flags)
+        ctx = _native.context(device)
+        ins = (ctypes.c_void_p * max(B, 1))(*[a.data_ptr() for a in arrays])
+        r = ctx.lib.zcg_store_write_boxes_s_device(ctx.handle, ctypes.byref(am), root, path, shp.ctypes.data,
+                                                   stp.ctypes.data, istr.ctypes.data, offs.ctypes.data,
+                                                   ctypes.addressof(ins), B, slot_budget_bytes, 16)
+    else:
+        arrays = [np.asarray(a) for a in arrays]
+        dense = []
+        for a in arrays:
+            if a.ndim != nd:
+                raise ZarrIOError("InvalidData", "Wrong number of dimensions")
+            dt = a.dtype.newbyteorder("=")
+            check_array_type(dt, meta)
+            # dense in the chunk memory order
+            dense.append(np.ascontiguousarray(a.astype(dt, copy=False).T if order == "F" else a.astype(dt, copy=False)))
+        shp = np.ascontiguousarray(np.array([a.shape for a in arrays], dtype=np.uint64).reshape(-1, nd))
+        _check_hulls(meta, shp, stp)
+        am = _native_meta(meta, flags)
+        ctx = _native.context(device)
+        ins = (ctypes.c_void_p * max(B, 1))(*[a.ctypes.data if a.size else 0 for a in dense])
+        r = ctx.lib.zcg_store_write_boxes_s(ctx.handle, ctypes.byref(am), root, path, shp.ctypes.data,
+                                            stp.ctypes.data, offs.ctypes.data, ctypes.addressof(ins), B,
+                                            slot_budget_bytes, 16)
+    if r != _native.OK:
+        raise ZarrIOError(_native.STATUS_NAMES.get(r, str(r)), f"write_boxes: {ctx.last_error()}")
 
 
 def read_ndarray_into(hier, path_name: str, meta: ArrayMetadata, bbox: BoundingBox, arr: np.ndarray, t,
