@@ -136,8 +136,9 @@ def check_many(codec, streams, dt, n, flags=0, param=None, guard=0, want=None, e
 
 
 # ---- encode: one zcg_encode_batch call, and the gzip member check ---------------------------------
-def encode_batch(meta, arrays, cap_extra=0):
-    """zcg_encode_batch over device buffers; returns (status, [bytes])."""
+def encode_batch(meta, arrays, cap_extra=0, src_lens=None):
+    """zcg_encode_batch over device buffers; returns (status, [bytes]).
+    `src_lens`: {chunk index: src_len} for descriptors that say less than D."""
     import torch
     from zarr_amd.batch import BatchCodec, make_encode_batch
     codec = BatchCodec(0)
@@ -152,6 +153,11 @@ def encode_batch(meta, arrays, cap_extra=0):
                                                        n, cap, "cuda:0")
         d = desc.cpu().numpy().view(np.uint64).reshape(n, 4).copy()
         d[:, 1] = 0
+        desc = torch.from_numpy(d.view(np.int64)).to("cuda:0")
+    if src_lens:
+        d = desc.cpu().numpy().view(np.uint64).reshape(n, 4).copy()
+        for i, v in src_lens.items():
+            d[i, 1] = v
         desc = torch.from_numpy(d.view(np.int64)).to("cuda:0")
     codec.encode(meta, desc, n, out_len, status)
     torch.cuda.synchronize()
