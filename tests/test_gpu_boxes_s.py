@@ -82,7 +82,9 @@ def mixed_case(seed):
     and the chunk extent plus 1; for ndim > 1 a tile-walk box (fast count 3V+1,
     fast step 2) of more than one tile; a zero-extent box between two others; a
     box partly and a box wholly outside the array; a duplicate of an earlier
-    box."""
+    box; for ndim > 1 a tile-walk box of the dense walk (fast count 31V-1, fast
+    step 1, every slow dimension every second index) of more than one tile,
+    whose rows of 496 - es bytes make the 16-byte pieces cross row ends."""
     rng = np.random.default_rng(47000 + seed)
     es = [1, 2, 4, 8][seed % 4]
     order = "F" if seed % 3 == 1 else "C"
@@ -104,7 +106,7 @@ def mixed_case(seed):
     shape, cs = dims(aslow, afast), dims(cslow, cfast)
     fd = fast_dim(nd, order)
 
-    def box(fast, fstep, off_fast=None, slow=None):
+    def box(fast, fstep, off_fast=None, slow=None, slow_steps=None):
         scnt, sstep = [], []
         for a, c in zip(aslow, cslow):
             k = int(rng.integers(1, min(3, a) + 1))
@@ -114,7 +116,7 @@ def mixed_case(seed):
             scnt.append(k)
             sstep.append(s)
         if slow is not None:
-            scnt, sstep = list(slow), [1] * len(slow)
+            scnt, sstep = list(slow), list(slow_steps) if slow_steps is not None else [1] * len(slow)
         cnt, stp = dims(scnt, fast), dims(sstep, fstep)
         hull = hull_of(cnt, stp)
         assert hull[fd] <= afast
@@ -141,6 +143,10 @@ def mixed_case(seed):
     woff[d] = (shape[d] // cs[d] + 2) * cs[d]  # wholly outside, at a chunk boundary: it visits no chunk
     boxes.append((woff, wcnt, wstp))
     boxes.append(tuple(list(x) for x in boxes[2]))  # a duplicate, into its own output
+    if nd > 1:  # after the duplicate: the boxes above keep their draws
+        boxes.append(box(31 * V - 1, 1, slow=[(a + 1) // 2 for a in aslow], slow_steps=[2] * len(aslow)))
+        if nd < 8:
+            assert int(np.prod(boxes[-1][1])) * es > 4096
     offsets, counts, steps = [b[0] for b in boxes], [b[1] for b in boxes], [b[2] for b in boxes]
     absent = 0.25 if seed % 2 == 0 else 0.0
     return rng, es, order, shape, cs, offsets, counts, steps, absent

@@ -84,7 +84,7 @@ __device__ __forceinline__ void box_status(i32* status, u64 b, bool in_table, bo
 
 // Short box rows: a workgroup per tile (walk_tile).
 __global__ __launch_bounds__(RG_T) void region_kernel(RegionWalk w, BoxTerms t, u64 ntiles, u32 dir) {
-    for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) walk_tile(w, t, tile, dir);
+    for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) walk_tile(w, t, Dense{}, tile, dir);
 }
 
 // Long box rows: a wave per (row, row piece) (walk_row_piece).
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(RG_T) void region_rows_kernel(RegionWalk w, BoxTerm
     const u32 ppr = row_pieces(w);
     for (u64 unit = ru64(wid); unit < nunits; unit += nwaves) {
         const u64 row = unit / ppr;
-        walk_row_piece<1>(w, t, row, (u32)(unit - row * ppr), dir);
+        walk_row_piece<1>(w, t, Dense{}, row, (u32)(unit - row * ppr), dir);
     }
 }
 
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(RG_T) void regions_kernel(RegionWalk w, BoxTable bt
         BoxTerms t;
         const bool in_table = box_terms(w, bt, table, boxes, b, t);
         box_status(status, b, in_table, tile == 0 && threadIdx.x == 0);
-        if (in_table) walk_tile(w, t, tile, DIR);
+        if (in_table) walk_tile(w, t, Dense{}, tile, DIR);
     }
 }
 
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(RG_T) void regions_rows_kernel(RegionWalk w, BoxTab
         box_status(status, b, in_table, ub == 0 && (threadIdx.x & 63) == 0);
         if (!in_table) continue;
         const u64 row = ub / ppr;
-        walk_row_piece<ZCG_MAX_DIMS>(w, t, row, (u32)(ub - row * ppr), DIR);
+        walk_row_piece<ZCG_MAX_DIMS>(w, t, Dense{}, row, (u32)(ub - row * ppr), DIR);
     }
 }
 

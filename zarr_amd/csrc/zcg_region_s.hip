@@ -4,30 +4,32 @@
 // hard-codes step 1 in its slices (ndarray.rs:118-127); a caller who wants
 // every k-th element reads the dense hull and slices it.  Per box the values
 // are those zcg_read_region writes to element i*step of a dense view of the
-// hull.  The plan / prefix scheme is zcg_region_v.hip's; the kernels live in a
-// translation unit of their own, so the code objects of zcg_region.hip and
-// zcg_region_v.hip do not change with them.
+// hull.  The box terms, the plan / prefix scheme and the unit loop are
+// zcg_region_plan.h's; a box with fast step 1 goes through the dense walk
+// (zcg_region_walk.h), any other through the gather (zcg_region_walk_s.h).
+// The kernels live in a translation unit of their own.
 #include <hip/hip_runtime.h>
 
 #include "zcg_common.h"
 #include "zcg_region_walk.h"
 #include "zcg_region_walk_s.h"
-#include "zcg_region_sbox.h"
+#include "zcg_region_plan.h"
 
 namespace zcg {
 
 namespace {
 
-// The plan: regions_v_plan_kernel's, with work counted in output elements.
-__global__ __launch_bounds__(RS_PLAN_T) void regions_s_plan_kernel(RegionWalk w, BoxTable bt,
+// The plan: regions_v_plan_kernel's (zcg_region_v.hip), with sbox_terms and
+// work counted in output elements.
+__global__ __launch_bounds__(RP_PLAN_T) void regions_s_plan_kernel(RegionWalk w, BoxTable bt,
                                                                    const u8* const* __restrict__ table,
                                                                    const zcg_sbox* __restrict__ boxes,
                                                                    u64* __restrict__ prefix,
                                                                    i32* __restrict__ status) {
-    __shared__ u64 wsum[RS_PLAN_T / 64];
+    __shared__ u64 wsum[RP_PLAN_T / 64];
     const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     u64 carry = 0;
-    for (u64 b0 = 0; b0 < bt.nboxes; b0 += RS_PLAN_T) {
+    for (u64 b0 = 0; b0 < bt.nboxes; b0 += RP_PLAN_T) {
         const u64 b = b0 + threadIdx.x;
         u64 units = 0;
         if (b < bt.nboxes) {
@@ -36,9 +38,7 @@ __global__ __launch_bounds__(RS_PLAN_T) void regions_s_plan_kernel(RegionWalk w,
             Steps st;
             const SBoxFate f = sbox_terms<false>(w, bt, table, boxes, b, wb, t, st);
             status[b] = f.status;
-            if (f.status == ZCG_OK && wb.total && (f.visits || w.fill))
-                units = sbox_rows(wb) ? (sbox_row_units(wb) + RS_WAVES - 1) / RS_WAVES
-                                      : (wb.total + (u64)RG_T * wb.V - 1) / ((u64)RG_T * wb.V);
+            if (f.status == ZCG_OK && wb.total && (f.visits || w.fill)) units = box_units(wb);
         }
         u64 x = units;  // inclusive scan over the wave
 #pragma unroll
@@ -50,7 +50,7 @@ __global__ __launch_bounds__(RS_PLAN_T) void regions_s_plan_kernel(RegionWalk w,
         __syncthreads();
         u64 before = carry, all = 0;
 #pragma unroll
-        for (u32 i = 0; i < RS_PLAN_T / 64; i++) {
+        for (u32 i = 0; i < RP_PLAN_T / 64; i++) {
             if (i < wv) before += wsum[i];
             all += wsum[i];
         }
@@ -65,48 +65,26 @@ __global__ __launch_bounds__(RG_T) void regions_s_kernel(RegionWalk w, BoxTable 
                                                          const u8* const* __restrict__ table,
                                                          const zcg_sbox* __restrict__ boxes,
                                                          const u64* __restrict__ prefix) {
-    const u64 n = bt.nboxes;
-    const u64 all = ru64(prefix[n]);
-    const u64 per = (all + gridDim.x - 1) / gridDim.x;
-    u64 unit = (u64)blockIdx.x * per;
-    const u64 last = unit + per < all ? unit + per : all;
-    if (unit >= last) return;
-    // the box of the first unit: prefix[b] <= unit < prefix[b + 1]
-    u64 b = 0, hi = n;
-    while (hi - b > 1) {
-        const u64 mid = (b + hi) >> 1;
-        if (ru64(prefix[mid]) <= unit) b = mid;
-        else hi = mid;
-    }
-    const u32 wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // any readable, 8-byte aligned device address: where a sample that has no
     // source points its load (the gather keeps every load unconditional)
     const u8* safe = (const u8*)boxes;
-    while (unit < last) {
-        u64 pe;
-        while ((pe = ru64(prefix[b + 1])) <= unit) b++;  // prefix[n] = all > unit ends it
-        const u64 pb = ru64(prefix[b]);
-        RegionWalk wb;
-        BoxTerms t;
-        Steps st;
-        sbox_terms<true>(w, bt, table, boxes, b, wb, t, st);
-        const u64 end = pe < last ? pe : last;
-        if (sbox_rows(wb)) {
-            const u32 ppr = row_pieces(wb);
-            const u64 nwu = sbox_row_units(wb);
-            for (; unit < end; unit++) {
-                const u64 wu = (unit - pb) * RS_WAVES + wv;
-                if (wu >= nwu) continue;
-                const u64 row = wu / ppr;
-                if (st.st[0] == 1) walk_row_piece_s(wb, t, st, row, (u32)(wu - row * ppr));
-                else gather_row_piece(wb, t, st, row, (u32)(wu - row * ppr), safe);
+    walk_units(
+        bt.nboxes, prefix,
+        [&](u64 b) {
+            WalkBox<Steps> x;
+            sbox_terms<true>(w, bt, table, boxes, b, x.w, x.t, x.s);
+            return x;
+        },
+        [safe](const WalkBox<Steps>& x, bool rows, u64 at, u32 piece) {
+            if (x.s.st[0] == 1) {
+                if (rows) walk_row_piece<ZCG_MAX_DIMS>(x.w, x.t, x.s, at, piece, 0);
+                else walk_tile(x.w, x.t, x.s, at, 0);
+            } else if (rows) {
+                gather_row_piece(x.w, x.t, x.s, at, piece, safe);
+            } else {
+                gather_tile(x.w, x.t, x.s, at, safe);
             }
-        } else if (st.st[0] == 1) {
-            for (; unit < end; unit++) walk_tile_s(wb, t, st, unit - pb);
-        } else {
-            for (; unit < end; unit++) gather_tile(wb, t, st, unit - pb, safe);
-        }
-    }
+        });
 }
 
 }  // namespace
@@ -116,7 +94,7 @@ __global__ __launch_bounds__(RG_T) void regions_s_kernel(RegionWalk w, BoxTable 
 // the scatter's rule too (zcg_region_sw.hip).
 hipError_t launch_regions_s_plan(const RegionWalk& w, const BoxTable& bt, const void* const* d_table,
                                  const zcg_sbox* d_boxes, void* d_prefix, int32_t* d_status, hipStream_t s) {
-    hipLaunchKernelGGL(regions_s_plan_kernel, dim3(1), dim3(RS_PLAN_T), 0, s, w, bt, (const u8* const*)d_table,
+    hipLaunchKernelGGL(regions_s_plan_kernel, dim3(1), dim3(RP_PLAN_T), 0, s, w, bt, (const u8* const*)d_table,
                        d_boxes, (u64*)d_prefix, d_status);
     return hipGetLastError();
 }
@@ -128,9 +106,7 @@ hipError_t launch_regions_s(const RegionWalk& w, const BoxTable& bt, const void*
     if (bt.nboxes == 0) return hipSuccess;
     hipError_t e = launch_regions_s_plan(w, bt, d_table, d_boxes, d_prefix, d_status, s);
     if (e != hipSuccess || w.total == 0) return e;  // a zero extent in the bound: no box has work
-    const u64 per_box = (w.total + (u64)RG_T * w.V - 1) / ((u64)RG_T * w.V);
-    const u64 units = per_box * bt.nboxes;
-    hipLaunchKernelGGL(regions_s_kernel, dim3((u32)(units < RS_GRID ? units : RS_GRID)), dim3(RG_T), 0, s, w, bt,
+    hipLaunchKernelGGL(regions_s_kernel, dim3(walk_grid(w, bt.nboxes)), dim3(RG_T), 0, s, w, bt,
                        (const u8* const*)d_table, d_boxes, (const u64*)d_prefix);
     return hipGetLastError();
 }

@@ -1,34 +1,20 @@
 // zcg_region_v.hip — region assembly and scatter for many boxes that each have
 // their own shape and view (zcg_read_regions_v, zcg_write_regions_v): the
 // reference's read_ndarray / write_ndarray (ndarray.rs:153-385) take any
-// BoundingBox per call.  The walk is zcg_region_walk.h's, the per-box semantics
-// are those of zcg_region.hip's kernels.  The kernels live in a translation
-// unit of their own, so the code object that holds zcg_region.hip's kernels
-// does not change with them.
+// BoundingBox per call.  The walk is zcg_region_walk.h's, the constants and
+// the unit counts zcg_region_plan.h's, the per-box semantics are those of
+// zcg_region.hip's kernels.  The kernels live in a translation unit of their
+// own, so the code object that holds zcg_region.hip's kernels does not change
+// with them.
 #include <hip/hip_runtime.h>
 
 #include "zcg_common.h"
 #include "zcg_region_walk.h"
+#include "zcg_region_plan.h"
 
 namespace zcg {
 
 namespace {
-
-// Work follows the sum of the boxes' sizes: a plan kernel checks every box,
-// writes its status word and an exclusive prefix sum of the boxes' work units;
-// the walk kernel's workgroups each take a consecutive run of units, find the
-// box of the first one by a scalar binary search in the prefix array and step
-// to the next box as the run crosses its end.  A work unit is workgroup-sized
-// whatever the box: one tile (walk_tile) of a box with short rows, or four
-// consecutive row pieces (walk_row_piece, one per wave) of a box with long
-// rows — launch_shape's rule, applied per box.
-
-constexpr u32 RV_PLAN_T = 1024;      // threads of the plan kernel's one workgroup
-constexpr u32 RV_WAVES = RG_T / 64;  // row pieces per work unit
-constexpr u32 RV_GRID = 32768;       // cap of the walk's grid
-
-template <bool UNI>
-__device__ __forceinline__ u64 uni(u64 x) { return UNI ? ru64(x) : x; }
 
 struct VBoxFate {
     bool ok;      // inside the bound, and its grid range inside the table (or it has no element or visits no chunk)
@@ -84,25 +70,22 @@ __device__ __forceinline__ VBoxFate vbox_terms(const RegionWalk& w, const BoxTab
     return VBoxFate{bounded && (inside || !visits || total == 0), visits};
 }
 
-__device__ __forceinline__ bool vbox_rows(const RegionWalk& wb) { return wb.bs[0] >= 32u * wb.V; }
-
-// wave-sized units of a box with long rows
-__device__ __forceinline__ u64 vbox_row_units(const RegionWalk& wb) { return wb.total / wb.bs[0] * row_pieces(wb); }
-
 // The plan: status[b] and prefix[b] = work units of the boxes before b, for
 // every box; prefix[nboxes] = all units.  A box has no unit when it is
 // refused, has a zero extent, or visits no chunk and is not to be filled.  One
-// workgroup walks the boxes RV_PLAN_T at a time (a lane per box) and carries
-// the running sum.
-__global__ __launch_bounds__(RV_PLAN_T) void regions_v_plan_kernel(RegionWalk w, BoxTable bt,
+// workgroup walks the boxes RP_PLAN_T at a time (a lane per box) and carries
+// the running sum.  regions_s_plan_kernel (zcg_region_s.hip) repeats the scan
+// with its own terms: as a shared function it costs this kernel two waves per
+// SIMD of occupancy.
+__global__ __launch_bounds__(RP_PLAN_T) void regions_v_plan_kernel(RegionWalk w, BoxTable bt,
                                                                    const u8* const* __restrict__ table,
                                                                    const zcg_vbox* __restrict__ boxes,
                                                                    u64* __restrict__ prefix,
                                                                    i32* __restrict__ status) {
-    __shared__ u64 wsum[RV_PLAN_T / 64];
+    __shared__ u64 wsum[RP_PLAN_T / 64];
     const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     u64 carry = 0;
-    for (u64 b0 = 0; b0 < bt.nboxes; b0 += RV_PLAN_T) {
+    for (u64 b0 = 0; b0 < bt.nboxes; b0 += RP_PLAN_T) {
         const u64 b = b0 + threadIdx.x;
         u64 units = 0;
         if (b < bt.nboxes) {
@@ -110,9 +93,7 @@ __global__ __launch_bounds__(RV_PLAN_T) void regions_v_plan_kernel(RegionWalk w,
             BoxTerms t;
             const VBoxFate f = vbox_terms<false>(w, bt, table, boxes, b, wb, t);
             status[b] = f.ok ? ZCG_OK : ZCG_ERR_INVALID_INPUT;
-            if (f.ok && wb.total && (f.visits || w.fill))
-                units = vbox_rows(wb) ? (vbox_row_units(wb) + RV_WAVES - 1) / RV_WAVES
-                                      : (wb.total + (u64)RG_T * wb.V - 1) / ((u64)RG_T * wb.V);
+            if (f.ok && wb.total && (f.visits || w.fill)) units = box_units(wb);
         }
         u64 x = units;  // inclusive scan over the wave
 #pragma unroll
@@ -124,7 +105,7 @@ __global__ __launch_bounds__(RV_PLAN_T) void regions_v_plan_kernel(RegionWalk w,
         __syncthreads();
         u64 before = carry, all = 0;
 #pragma unroll
-        for (u32 i = 0; i < RV_PLAN_T / 64; i++) {
+        for (u32 i = 0; i < RP_PLAN_T / 64; i++) {
             if (i < wv) before += wsum[i];
             all += wsum[i];
         }
@@ -135,6 +116,10 @@ __global__ __launch_bounds__(RV_PLAN_T) void regions_v_plan_kernel(RegionWalk w,
     if (threadIdx.x == 0) prefix[bt.nboxes] = carry;
 }
 
+// The walk.  The unit loop is walk_units' (zcg_region_plan.h) in its own
+// lines: through the shared function this kernel's instructions change, and
+// the skew rows of tools/boxes_v_bench.py then miss the A/B rule (DESIGN.md
+// §6.7f).
 template <u32 DIR>
 __global__ __launch_bounds__(RG_T) void regions_v_kernel(RegionWalk w, BoxTable bt,
                                                          const u8* const* __restrict__ table,
@@ -162,17 +147,17 @@ __global__ __launch_bounds__(RG_T) void regions_v_kernel(RegionWalk w, BoxTable 
         BoxTerms t;
         vbox_terms<true>(w, bt, table, boxes, b, wb, t);
         const u64 end = pe < last ? pe : last;
-        if (vbox_rows(wb)) {
+        if (box_rows(wb)) {
             const u32 ppr = row_pieces(wb);
-            const u64 nwu = vbox_row_units(wb);
+            const u64 nwu = box_row_units(wb);
             for (; unit < end; unit++) {
-                const u64 wu = (unit - pb) * RV_WAVES + wv;
+                const u64 wu = (unit - pb) * RP_WAVES + wv;
                 if (wu >= nwu) continue;
                 const u64 row = wu / ppr;
-                walk_row_piece<ZCG_MAX_DIMS>(wb, t, row, (u32)(wu - row * ppr), DIR);
+                walk_row_piece<ZCG_MAX_DIMS>(wb, t, Dense{}, row, (u32)(wu - row * ppr), DIR);
             }
         } else {
-            for (; unit < end; unit++) walk_tile(wb, t, unit - pb, DIR);
+            for (; unit < end; unit++) walk_tile(wb, t, Dense{}, unit - pb, DIR);
         }
     }
 }
@@ -188,14 +173,12 @@ hipError_t launch_regions_v(const RegionWalk& w, const BoxTable& bt, const void*
                             const zcg_vbox* d_boxes, void* d_prefix, int32_t* d_status, uint32_t dir,
                             hipStream_t s) {
     if (bt.nboxes == 0) return hipSuccess;
-    hipLaunchKernelGGL(regions_v_plan_kernel, dim3(1), dim3(RV_PLAN_T), 0, s, w, bt, (const u8* const*)d_table,
+    hipLaunchKernelGGL(regions_v_plan_kernel, dim3(1), dim3(RP_PLAN_T), 0, s, w, bt, (const u8* const*)d_table,
                        d_boxes, (u64*)d_prefix, d_status);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || w.total == 0) return e;  // a zero extent in the bound: no box has work
-    const u64 per_box = (w.total + (u64)RG_T * w.V - 1) / ((u64)RG_T * w.V);
-    const u64 units = per_box * bt.nboxes;
-    hipLaunchKernelGGL(dir ? regions_v_kernel<1> : regions_v_kernel<0>, dim3((u32)(units < RV_GRID ? units : RV_GRID)),
-                       dim3(RG_T), 0, s, w, bt, (const u8* const*)d_table, d_boxes, (const u64*)d_prefix);
+    hipLaunchKernelGGL(dir ? regions_v_kernel<1> : regions_v_kernel<0>, dim3(walk_grid(w, bt.nboxes)), dim3(RG_T), 0,
+                       s, w, bt, (const u8* const*)d_table, d_boxes, (const u64*)d_prefix);
     return hipGetLastError();
 }
 

@@ -1,9 +1,17 @@
-// zcg_region_walk.h — the region assembly walk, written once for the four
-// kernels of zcg_region.hip (one box or many boxes per launch; a workgroup per
-// tile or a wave per row piece) and the kernel of zcg_region_v.hip (boxes of
-// differing shapes).  A kernel only decides where a box's terms (BoxTerms, and
-// for differing shapes the box's part of RegionWalk) come from; what is done
-// with them is here.
+// zcg_region_walk.h — the dense region walk, written once for every region
+// kernel: the four of zcg_region.hip (one box or many boxes per launch; a
+// workgroup per tile or a wave per row piece), zcg_region_v.hip's (boxes of
+// differing shapes) and, for boxes whose fast step is 1, the strided kernels
+// of zcg_region_s.hip and zcg_region_sw.hip.  A kernel only decides where a
+// box's terms (BoxTerms, for differing shapes the box's part of RegionWalk,
+// for strided boxes its Steps) come from; what is done with them is here.
+//
+// A step policy S says how far apart two samples of the box lie along
+// dimension k: Dense (the constant 1, an empty struct that leaves no trace in
+// the code) or Steps (a step per dimension).  Sample x of the box along k sits
+// at orr[k] + x * s(k) of the box's first chunk.  The walk itself needs the
+// fast dimension dense: a box with a fast step above 1 goes through
+// zcg_region_walk_s.h (gather) or zcg_region_walk_sw.h (scatter).
 //
 // The walk goes through a box in the chunks' memory order, 16 bytes per lane,
 // so reads from a chunk row and writes to an output row with unit stride are
@@ -26,6 +34,14 @@ constexpr u32 RG_T = 256;
 
 struct Pos {
     u32 x[ZCG_MAX_DIMS];
+};
+
+struct Dense {
+    __device__ __forceinline__ u32 operator()(u32) const { return 1; }
+};
+struct Steps {
+    u32 st[ZCG_MAX_DIMS];  // per dim, fast-first order; 1 where the box has fewer than two samples
+    __device__ __forceinline__ u32 operator()(u32 k) const { return st[k]; }
 };
 
 __device__ __forceinline__ void copy_elem(u8* dst, const u8* src, u32 es) {
@@ -55,15 +71,18 @@ __device__ __forceinline__ u32x4 fill_piece(u64 fv, u32 es) {
 __device__ __forceinline__ u32x4 fill_piece(const RegionWalk& w) { return fill_piece(w.fillv, w.es); }
 
 // where element p of the box is read from (nullptr: no visited chunk), and
-// how many elements from it stay in one chunk row and one box row
-__device__ __forceinline__ const u8* walk_src(const RegionWalk& w, const BoxTerms& t, const Pos& p, u32* run) {
+// how many elements from it stay in one chunk row and one box row (*run is
+// meaningful for a fast step of 1 only)
+template <class S>
+__device__ __forceinline__ const u8* walk_src(const RegionWalk& w, const BoxTerms& t, const S& s, const Pos& p,
+                                              u32* run) {
     u64 ti = 0, wi = 0;
     bool ok = true;
     u32 w0 = 0;
 #pragma unroll
     for (u32 k = 0; k < ZCG_MAX_DIMS; k++) {
         if (k >= w.nd) break;
-        const u32 r = t.orr[k] + p.x[k];
+        const u32 r = t.orr[k] + p.x[k] * s(k);
         const u32 q = r / w.cs[k];
         const u32 c = r - q * w.cs[k];
         if (k == 0) w0 = c;
@@ -102,11 +121,37 @@ __device__ __forceinline__ void walk_advance(const RegionWalk& w, Pos& p, u32 d)
     }
 }
 
+// The tile's first position (workgroup-uniform, scalar) plus this thread's
+// offset, added with carries; false: past the box.  For the tile functions of
+// zcg_region_walk_s.h and zcg_region_walk_sw.h.  walk_tile spells the same
+// lines out: calling this from it changes the register allocation of every
+// tile kernel of zcg_region.hip.
+__device__ __forceinline__ bool tile_start(const RegionWalk& w, u64 tile, Pos& p, u32* rem) {
+    const u64 tile_elems = (u64)RG_T * w.V;
+    u64 e = tile * tile_elems;
+#pragma unroll
+    for (u32 k = 0; k < ZCG_MAX_DIMS; k++) {
+        if (k < w.nd) {
+            const u64 q = e / w.bs[k];
+            p.x[k] = (u32)(e - q * w.bs[k]);
+            e = q;
+        } else {
+            p.x[k] = 0;
+        }
+    }
+    const u64 e0 = tile * tile_elems + (u64)threadIdx.x * w.V;
+    if (e0 >= w.total) return false;
+    walk_advance(w, p, threadIdx.x * w.V);
+    *rem = (u32)((w.total - e0) < w.V ? (w.total - e0) : w.V);
+    return true;
+}
+
 // Short box rows: one tile of RG_T 16-byte pieces of the box, by a workgroup.
 // The tile start is decomposed once (workgroup-uniform, scalar), threads add
-// their offset with carries.  dir 0: chunks -> box (read_ndarray), 1: box ->
-// chunks (write_ndarray).
-__device__ __forceinline__ void walk_tile(const RegionWalk& w, const BoxTerms& t, u64 tile, u32 dir) {
+// their offset with carries (tile_start's lines).  dir 0: chunks -> box
+// (read_ndarray), 1: box -> chunks (write_ndarray).
+template <class S>
+__device__ __forceinline__ void walk_tile(const RegionWalk& w, const BoxTerms& t, const S& s, u64 tile, u32 dir) {
     const u64 tile_elems = (u64)RG_T * w.V;
     Pos p;
     u64 e = tile * tile_elems;
@@ -125,7 +170,7 @@ __device__ __forceinline__ void walk_tile(const RegionWalk& w, const BoxTerms& t
     walk_advance(w, p, threadIdx.x * w.V);
     u32 rem = (u32)((w.total - e0) < w.V ? (w.total - e0) : w.V);
     u32 run;
-    const u8* src = walk_src(w, t, p, &run);
+    const u8* src = walk_src(w, t, s, p, &run);
     if (rem == w.V && run >= w.V && w.ostr[0] == 1) {  // one 16-byte piece, both sides contiguous
         u8* d = t.out + walk_dst(w, p) * (i64)w.es;
         if (dir) { if (src) st16((u8*)src, ld16(d)); }
@@ -145,7 +190,7 @@ __device__ __forceinline__ void walk_tile(const RegionWalk& w, const BoxTerms& t
         rem -= k;
         if (!rem) break;
         walk_advance(w, p, k);
-        src = walk_src(w, t, p, &run);
+        src = walk_src(w, t, s, p, &run);
     }
 }
 
@@ -153,6 +198,52 @@ __device__ __forceinline__ void walk_tile(const RegionWalk& w, const BoxTerms& t
 __host__ __device__ __forceinline__ u32 row_pieces(const RegionWalk& w) {
     const u64 span = (u64)ZCG_RG_U * 64 * w.V;
     return (u32)((w.bs[0] + span - 1) / span);
+}
+
+// the slow dimensions' part of a box row (scalar when the row is wave-uniform)
+struct RowTerms {
+    u64 ti;     // chunk-table index, slow dimensions
+    u64 wi;     // element index inside the chunk, slow dimensions
+    i64 drow;   // element offset of the row in the view
+    bool ok;    // every slow coordinate lies in a visited chunk
+
+    // sample x of slow dimension k
+    template <class S>
+    __device__ __forceinline__ void add(const RegionWalk& w, const BoxTerms& t, const S& s, u32 k, u32 x) {
+        const u32 r = t.orr[k] + x * s(k);
+        const u32 q = r / w.cs[k];
+        ok &= q < t.gn[k];
+        ti += (u64)q * w.tstr[k];
+        wi += (u64)(r - q * w.cs[k]) * w.cstr[k];
+        drow += (i64)x * w.ostr[k];
+    }
+};
+
+// from the row's index.  UNR: unroll count of the loop (walk_row_piece)
+template <u32 UNR, class S>
+__device__ __forceinline__ RowTerms row_terms(const RegionWalk& w, const BoxTerms& t, const S& s, u64 row) {
+    u64 e = row;
+    RowTerms R{0, 0, 0, true};
+#pragma unroll UNR
+    for (u32 k = 1; k < ZCG_MAX_DIMS; k++) {
+        if (k >= w.nd) break;
+        const u64 qd = e / w.bs[k];
+        R.add(w, t, s, k, (u32)(e - qd * w.bs[k]));
+        e = qd;
+    }
+    return R;
+}
+
+// from a position in the box
+template <class S>
+__device__ __forceinline__ RowTerms row_terms_at(const RegionWalk& w, const BoxTerms& t, const S& s, const Pos& p) {
+    RowTerms R{0, 0, 0, true};
+#pragma unroll
+    for (u32 k = 1; k < ZCG_MAX_DIMS; k++) {
+        if (k >= w.nd) break;
+        R.add(w, t, s, k, p.x[k]);
+    }
+    return R;
 }
 
 // Long box rows (the common case: the fast dimension spans many 16-byte
@@ -165,33 +256,19 @@ __host__ __device__ __forceinline__ u32 row_pieces(const RegionWalk& w) {
 // where the box terms are computed in registers (many boxes); 1 where they are
 // kernel arguments (one box): unrolled, that kernel keeps every argument in
 // SGPRs, spills them to VGPR lanes and runs 7 % slower on the bench leg.
-template <u32 UNR>
-__device__ __forceinline__ void walk_row_piece(const RegionWalk& w, const BoxTerms& t, u64 row, u32 piece,
-                                               u32 dir) {
+template <u32 UNR, class S>
+__device__ __forceinline__ void walk_row_piece(const RegionWalk& w, const BoxTerms& t, const S& s, u64 row,
+                                               u32 piece, u32 dir) {
     const u32 lane = threadIdx.x & 63;
     const u32x4 fill16 = fill_piece(w);
     const u32 V = w.V, bs0 = w.bs[0], cs0 = w.cs[0], orr0 = t.orr[0];
     const i64 es = w.es;
     constexpr u32 U = ZCG_RG_U;
     const u32 span = U * 64 * V;
-    // slow-dimension coordinates of this row (scalar)
-    u64 e = row, ti = 0, wi = 0;
-    i64 drow = 0;
-    bool ok = true;
-#pragma unroll UNR
-    for (u32 k = 1; k < ZCG_MAX_DIMS; k++) {
-        if (k >= w.nd) break;
-        const u64 qd = e / w.bs[k];
-        const u32 x = (u32)(e - qd * w.bs[k]);
-        e = qd;
-        const u32 r = t.orr[k] + x;
-        const u32 q = r / w.cs[k];
-        ok &= q < t.gn[k];
-        ti += (u64)q * w.tstr[k];
-        wi += (u64)(r - q * w.cs[k]) * w.cstr[k];
-        drow += (i64)x * w.ostr[k];
-    }
-    u8* drow_p = t.out + drow * es;
+    const RowTerms R = row_terms<UNR>(w, t, s, row);
+    const bool ok = R.ok;
+    const u64 ti = R.ti, wi = R.wi;
+    u8* drow_p = t.out + R.drow * es;
     // U pieces per lane in flight: loads first, then stores
     const u64 xb = (u64)piece * span + lane * V;
     u32x4 v[U];
