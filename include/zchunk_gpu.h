@@ -644,6 +644,84 @@ int zcg_write_regions_s(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table
 uint32_t zcg_regions_s_waves(const zcg_region* r, const uint64_t* offsets, const uint64_t* shapes,
                              const uint64_t* steps, uint32_t n_boxes, uint32_t* wave_of);
 
+/* ---- many single elements by coordinate in one call ------------------------
+ * numpy's a[i, j, k] with index arrays: sampled voxels, labelled points, sparse
+ * annotations.  The reference reads or writes each through a 1-element
+ * BoundingBox (read_ndarray, ndarray.rs:153-268; write_ndarray,
+ * ndarray.rs:276-385), and that pins the semantics: A POINT IS THE BOX OF SHAPE
+ * (1, ..., 1) AT ITS COORDINATE, for clipping, overhanging edge chunks, fill
+ * versus untouched and NULL table entries.  Nothing of a box is built, though:
+ * no record, no plan launch, no scratch; a lane of the kernel takes a point.
+ *
+ * `r` gives ndim, elem_size, chunk_order, fill_missing, fill_value,
+ * array_shape and chunk_shape; r->bbox_offset, r->bbox_shape and
+ * r->out_strides are ignored.  `coords` holds n_points*ndim coordinates,
+ * point-major, as `offsets` does everywhere above.
+ *
+ * The chunk of a point, along dimension d, is grid index coords[d] /
+ * chunk_shape[d], and the point VISITS it when the 1-element box does
+ * (bounded_coord_iter, ndarray.rs:410-432; get_chunk_bounds,
+ * ndarray.rs:434-446): along every dimension the coordinate is below
+ * array_shape[d], or it is beyond it and no multiple of chunk_shape[d].  The
+ * second case is the overhang of an edge chunk, which the box calls read and
+ * write over its nominal extent as well.  Any other point visits no chunk.
+ *
+ * Host code, no GPU and no context:
+ *  - zcg_points_grid: the smallest grid range lo[d] .. lo[d]+n[d] that holds
+ *    every chunk a point visits; the return value and lo / n follow
+ *    zcg_regions_grid's convention (0, with lo = n = 0, when no point visits a
+ *    chunk or n_points is 0).  It is zcg_regions_v_grid on the same coordinates
+ *    with every shape 1, by construction.
+ *  - zcg_points_last: keep[i] (n_points bytes) = 1 if and only if no later
+ *    point has the same coordinate, else 0; returns the number kept (0 for a
+ *    NULL argument or ndim outside 1..ZCG_MAX_DIMS).  A sort: n log n. */
+uint64_t zcg_points_grid(const zcg_region* r, const uint64_t* coords, uint64_t n_points, uint64_t* lo, uint64_t* n);
+uint64_t zcg_points_last(const uint64_t* coords, uint64_t n_points, uint32_t ndim, uint8_t* keep);
+
+/* d_coords is a DEVICE array of n_points*ndim coordinates; the values are a
+ * dense DEVICE array of n_points elements of elem_size bytes, point i being
+ * element i (d_out, written; d_in, only read).  The table arguments are
+ * zcg_read_regions'.  d_first_outside is one DEVICE word.
+ *  - zcg_read_points: point i receives the element of its chunk, at its
+ *    chunk-local position in the chunk memory order, if it visits a chunk that
+ *    is inside the table and not NULL; fill_value if fill_missing is set and
+ *    the chunk is NULL or the point visits no chunk; nothing (d_out[i] is
+ *    untouched) if fill_missing is clear.  No other byte of d_out is written.
+ *  - zcg_write_points: point i's value goes to that position if the point
+ *    visits a chunk that is inside the table and not NULL, the overhang of an
+ *    edge chunk included; else it is dropped.  fill_missing and fill_value are
+ *    ignored.  Two points of one call with the same coordinate leave the
+ *    element with one of their values, whole; which one wins is unspecified
+ *    (zcg_points_last tells a caller which points to drop so that the later
+ *    one wins).
+ *  - Points outside the table: a point that visits a chunk outside table_lo ..
+ *    table_lo + table_n is neither read nor written (the box calls give such a
+ *    box ZCG_ERR_INVALID_INPUT), and the other points are unaffected.  The
+ *    call sets *d_first_outside to UINT64_MAX on the stream (an 8-byte
+ *    device-to-device copy from a word the context owns: a captured memset
+ *    node did not keep its fill pattern from one replay to the next), and
+ *    the kernel lowers it to the lowest index of such a point (an atomic
+ *    minimum per wave that has one).  There is no status word per point: at 1
+ *    to 8 bytes of payload per point it would cost as much traffic as the
+ *    data.
+ *  - n_points == 0 returns ZCG_OK and launches nothing (d_first_outside is not
+ *    written).
+ *  - ndim outside 1..ZCG_MAX_DIMS, a bad elem_size, a chunk extent of 0 or of
+ *    2^32 and above return ZCG_ERR_INVALID_INPUT, as zcg_read_regions does;
+ *    so does a NULL d_coords, value array or d_first_outside.  n_points above
+ *    2^60 returns ZCG_ERR_UNSUPPORTED.  A coordinate may be any uint64_t, up
+ *    to 2^64-1.
+ *  - Asynchronous on `stream`: one kernel launch plus that reset, whatever
+ *    n_points is.  The call allocates nothing and does not synchronize with
+ *    the host.  d_coords is read when the kernel runs, so the call can be
+ *    captured in a graph and a replay sees new coordinates. */
+int zcg_read_points(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+                    const void* const* d_chunk_table, const uint64_t* d_coords, uint64_t n_points,
+                    void* d_out, uint64_t* d_first_outside, void* stream);
+int zcg_write_points(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+                     void* const* d_chunk_table, const uint64_t* d_coords, uint64_t n_points,
+                     const void* d_in, uint64_t* d_first_outside, void* stream);
+
 /* ---- FilesystemHierarchy chunk files ---------------
  * The e2e path's two ends: chunk files read into pinned staging by a pool of
  * `io_threads` host threads (open + shared flock + read, as ReadableStore::get,
@@ -953,6 +1031,48 @@ int zcg_store_write_boxes_s(zcg_ctx* ctx, const zcg_array_meta* meta, const char
                             const uint64_t* box_shapes, const uint64_t* box_steps, const uint64_t* offsets,
                             const void* const* ins, uint32_t n_boxes, uint64_t slot_budget_bytes,
                             uint32_t io_threads);
+
+/* ---- read_ndarray / write_ndarray for a list of coordinates -----------------
+ * The _v store calls for the 1-element boxes at `coords` (HOST, n_points*ndim,
+ * point-major), without the boxes: the values are one dense array of n_points
+ * elements, point i being element i.  Blocking, as the box calls are.
+ *  - The points are sorted on the host by chunk, then by their place in the
+ *    chunk.  The chunks opened and decoded are the unique chunks a point
+ *    visits (zcg_points_grid's rule), each once per group; no other file is
+ *    opened.  Groups are consecutive runs of the SORTED points whose chunks fit
+ *    slot_budget_bytes (0 = 4 GiB; at least one chunk); a group's table covers
+ *    the bounding grid range of its chunks, and more than 2^24 entries ->
+ *    ZCG_ERR_UNSUPPORTED.  One zcg_read_points / zcg_write_points launch per
+ *    group, on the sorted coordinates.
+ *  - Carried over from zcg_store_read_boxes_v word for word: the error
+ *    reporting (the first failing chunk is named by zcg_last_error), absent
+ *    files as NULL entries, the decode and verify flags of `meta`, the raw
+ *    dtype and ndim checks, and the in-grid check before any file is touched: a
+ *    point that visits a chunk outside the array's chunk grid ->
+ *    ZCG_ERR_INVALID_INPUT, zcg_last_error names the point.
+ *  - Read: the _device form writes d_out (DEVICE) in the caller's order, with
+ *    fill_missing as in zcg_region; the host form fills `out` (HOST) and sets
+ *    fill value where no chunk is.
+ *  - Write: the store ends up as if write_ndarray had run for the 1-element
+ *    boxes of point 0, 1, ... in order.  Of several points with one coordinate
+ *    only the last is scattered (zcg_points_last).  Every visited chunk is read
+ *    first (decoded; an absent one starts as fill value), except a chunk of one
+ *    element, which its point covers; then it is scattered into, encoded and
+ *    written once.  Reads precede writes inside a group.  No unvisited chunk is
+ *    opened, created or rewritten; a point that visits no chunk is dropped.
+ *  - n_points == 0 returns ZCG_OK; more than 2^32 points -> ZCG_ERR_UNSUPPORTED. */
+int zcg_store_read_points_device(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                                 const uint64_t* coords, uint64_t n_points, uint32_t fill_missing, void* d_out,
+                                 uint64_t slot_budget_bytes, uint32_t io_threads);
+int zcg_store_read_points(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                          const uint64_t* coords, uint64_t n_points, void* out, uint64_t slot_budget_bytes,
+                          uint32_t io_threads);
+int zcg_store_write_points_device(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                                  const uint64_t* coords, uint64_t n_points, const void* d_in,
+                                  uint64_t slot_budget_bytes, uint32_t io_threads);
+int zcg_store_write_points(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                           const uint64_t* coords, uint64_t n_points, const void* in, uint64_t slot_budget_bytes,
+                           uint32_t io_threads);
 
 #ifdef __cplusplus
 }

@@ -59,6 +59,9 @@ EXPORTED_SYMBOLS = (
     "zcg_region_s_chunks", "zcg_regions_s_grid", "zcg_regions_s_scratch_bytes", "zcg_read_regions_s",
     "zcg_store_read_boxes_s_device", "zcg_store_read_boxes_s",
     "zcg_write_regions_s", "zcg_regions_s_waves", "zcg_store_write_boxes_s_device", "zcg_store_write_boxes_s",
+    "zcg_points_grid", "zcg_points_last", "zcg_read_points", "zcg_write_points",
+    "zcg_store_read_points_device", "zcg_store_read_points",
+    "zcg_store_write_points_device", "zcg_store_write_points",
 )
 
 
@@ -282,6 +285,26 @@ def load_library(path: str = LIB_PATH):
         L.zcg_store_write_boxes_s.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
                                               vp, vp, vp, vp, u32, u64, u32]
         L.zcg_store_write_boxes_s.restype = ctypes.c_int
+        L.zcg_points_grid.argtypes = [ctypes.POINTER(Region), vp, u64, vp, vp]
+        L.zcg_points_grid.restype = u64
+        L.zcg_points_last.argtypes = [vp, u64, u32, vp]
+        L.zcg_points_last.restype = u64
+        L.zcg_read_points.argtypes = [vp, ctypes.POINTER(Region), vp, vp, vp, vp, u64, vp, vp, vp]
+        L.zcg_read_points.restype = ctypes.c_int
+        L.zcg_write_points.argtypes = [vp, ctypes.POINTER(Region), vp, vp, vp, vp, u64, vp, vp, vp]
+        L.zcg_write_points.restype = ctypes.c_int
+        L.zcg_store_read_points_device.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
+                                                   vp, u64, u32, vp, u64, u32]
+        L.zcg_store_read_points_device.restype = ctypes.c_int
+        L.zcg_store_read_points.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
+                                            vp, u64, vp, u64, u32]
+        L.zcg_store_read_points.restype = ctypes.c_int
+        L.zcg_store_write_points_device.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
+                                                    vp, u64, vp, u64, u32]
+        L.zcg_store_write_points_device.restype = ctypes.c_int
+        L.zcg_store_write_points.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
+                                             vp, u64, vp, u64, u32]
+        L.zcg_store_write_points.restype = ctypes.c_int
         _lib = L
         return L
 

@@ -47,6 +47,9 @@ struct zcg_ctx {
     size_t h_pin_bytes = 0;
     // store pipeline slots (zcg_store.cpp), created on first use
     zcg_store_slots* store = nullptr;
+    // one device word holding UINT64_MAX: the source of the point calls' reset of
+    // *d_first_outside (a copy, not a memset: see launch_points)
+    uint64_t* d_all_ones = nullptr;
 };
 
 namespace zcg {
@@ -216,6 +219,11 @@ zcg_ctx* zcg_create(int device) {
         delete ctx;
         return nullptr;
     }
+    if (hipMalloc((void**)&ctx->d_all_ones, sizeof(uint64_t)) != hipSuccess ||
+        hipMemset(ctx->d_all_ones, 0xFF, sizeof(uint64_t)) != hipSuccess) {
+        zcg_destroy(ctx);
+        return nullptr;
+    }
     return ctx;
 }
 
@@ -227,6 +235,7 @@ void zcg_destroy(zcg_ctx* ctx) {
     for (auto& w : ctx->ws) ws_release(w);
     if (ctx->d_buf) (void)hipFree(ctx->d_buf);
     if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
+    if (ctx->d_all_ones) (void)hipFree(ctx->d_all_ones);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -608,13 +617,13 @@ static uint64_t hull_extent(uint64_t cnt, uint64_t step) {
 // r->bbox_shape.  `steps` not NULL: shapes are sample counts, a box's range is
 // its hull's, and a box with a zero step adds nothing.
 static uint64_t regions_grid(const zcg_region* r, const uint64_t* offsets, const uint64_t* shapes,
-                             const uint64_t* steps, uint32_t n_boxes, uint64_t* lo, uint64_t* n) {
+                             const uint64_t* steps, uint64_t n_boxes, uint64_t* lo, uint64_t* n) {
     if (!r || r->ndim < 1 || r->ndim > ZCG_MAX_DIMS) return 0;
     const uint32_t nd = r->ndim;
     uint64_t ulo[ZCG_MAX_DIMS] = {0}, uhi[ZCG_MAX_DIMS] = {0};
     bool any = false;
     zcg_region one = *r;
-    for (uint32_t b = 0; b < n_boxes && offsets; b++) {
+    for (uint64_t b = 0; b < n_boxes && offsets; b++) {
         uint64_t blo[ZCG_MAX_DIMS], bn[ZCG_MAX_DIMS];
         bool stepped = true;
         for (uint32_t d = 0; d < nd; d++) {
@@ -833,3 +842,70 @@ int zcg_write_regions_s(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table
 }
 
 }  // extern "C"
+
+// ---- a list of coordinates (zcg_region_p.hip) -------------------------------
+// A point is the box of shape (1, ..., 1) at its coordinate: its grid range is
+// zcg_region_grid's for that box, so zcg_points_grid is zcg_regions_v_grid with
+// every shape 1 by construction.
+extern "C" uint64_t zcg_points_grid(const zcg_region* r, const uint64_t* coords, uint64_t n_points, uint64_t* lo,
+                                    uint64_t* n) {
+    if (!r || r->ndim < 1 || r->ndim > ZCG_MAX_DIMS) return 0;
+    zcg_region one = *r;
+    for (uint32_t d = 0; d < r->ndim; d++) one.bbox_shape[d] = 1;
+    return regions_grid(&one, coords, nullptr, nullptr, n_points, lo, n);
+}
+
+namespace zcg {
+// zcg_read_points (dir 0) and zcg_write_points (dir 1); d_order (DEVICE,
+// n_points entries, or NULL) places point p's value at element d_order[p] of
+// d_vals: the store calls hand the kernel points sorted by chunk
+// (zcg_points.cpp).
+int points_call(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+                const void* const* d_chunk_table, const uint64_t* d_coords, const uint64_t* d_order,
+                uint64_t n_points, void* d_vals, uint64_t* d_first_outside, void* stream, uint32_t dir) {
+    const int head = region_head(ctx, r);
+    if (head != ZCG_OK || n_points == 0) return head;
+    zcg_region one = *r;  // bbox_* are ignored
+    for (uint32_t d = 0; d < r->ndim; d++) one.bbox_shape[d] = 1;
+    RegionWalk w;
+    uint64_t entries;
+    const int rc = region_walk(ctx, &one, nullptr, table_n, "points: chunk extent must stay below 2^32 elements", &w,
+                               &entries);
+    if (rc != ZCG_OK) return rc;
+    if (dir) w.fill = 0;
+    BoxTable bt{};
+    PointRecip pr{};
+    for (uint32_t k = 0; k < w.nd; k++) {
+        const uint32_t d = region_dim(r, k);
+        bt.dim[k] = d;
+        bt.as[k] = r->array_shape[d];
+        bt.tlo[k] = table_lo ? table_lo[d] : 0;
+        bt.tn[k] = table_n ? table_n[d] : 0;
+        pr.m[k] = w.cs[k] > 1 ? ~0ull / w.cs[k] + 1 : 0;  // ceil(2^64 / chunk extent)
+    }
+    if (!d_coords || !d_vals || !d_first_outside || (entries && !d_chunk_table)) return ZCG_ERR_INVALID_INPUT;
+    if (n_points > (1ull << 60)) {
+        ctx->err = "points: n_points must stay at or below 2^60";
+        return ZCG_ERR_UNSUPPORTED;
+    }
+    (void)hipSetDevice(ctx->device);
+    const hipError_t e = launch_points(w, bt, pr, n_points, d_chunk_table, d_coords, d_order, d_vals, d_first_outside,
+                                       ctx->d_all_ones, dir, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, e, "points launch");
+    return ZCG_OK;
+}
+}  // namespace zcg
+
+extern "C" int zcg_read_points(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+                               const void* const* d_chunk_table, const uint64_t* d_coords, uint64_t n_points,
+                               void* d_out, uint64_t* d_first_outside, void* stream) {
+    return zcg::points_call(ctx, r, table_lo, table_n, d_chunk_table, d_coords, nullptr, n_points, d_out,
+                            d_first_outside, stream, 0);
+}
+
+extern "C" int zcg_write_points(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+                                void* const* d_chunk_table, const uint64_t* d_coords, uint64_t n_points,
+                                const void* d_in, uint64_t* d_first_outside, void* stream) {
+    return zcg::points_call(ctx, r, table_lo, table_n, (const void* const*)d_chunk_table, d_coords, nullptr, n_points,
+                            (void*)d_in, d_first_outside, stream, 1);
+}

@@ -1027,3 +1027,431 @@ extern "C" int zcg_store_write_boxes_s(zcg_ctx* ctx, const zcg_array_meta* meta,
     return write_boxes(ctx, meta, root, path, box_shapes, box_steps, nullptr, true, offsets, ins, n_boxes,
                        slot_budget_bytes, io_threads, true);
 }
+
+// ---- a list of coordinates --------------------------------------------------
+// zcg_store_read_points / zcg_store_write_points: read_ndarray / write_ndarray
+// (ndarray.rs:153-385) for the 1-element boxes at the coordinates, without the
+// boxes.  The points are sorted by chunk, then by their place in the chunk:
+// the sort yields the unique chunks and the groups (consecutive runs of sorted
+// points whose chunks fit the slot budget), and a wave's lanes fall into one
+// chunk and neighbouring lines.  The kernel (zcg_region_p.hip) gets the sorted
+// coordinates with each point's original index, so a device caller's values
+// stay in the caller's order; host values are permuted on the host.
+extern "C" uint64_t zcg_points_last(const uint64_t* coords, uint64_t n_points, uint32_t ndim, uint8_t* keep) {
+    if (!coords || !keep || ndim < 1 || ndim > ZCG_MAX_DIMS) return 0;
+    std::vector<uint64_t> idx(n_points);
+    for (uint64_t i = 0; i < n_points; i++) idx[i] = i;
+    // equal coordinates next to each other, the latest point last
+    std::sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) {
+        const uint64_t *ca = coords + a * ndim, *cb = coords + b * ndim;
+        for (uint32_t d = 0; d < ndim; d++)
+            if (ca[d] != cb[d]) return ca[d] < cb[d];
+        return a < b;
+    });
+    uint64_t kept = 0;
+    for (uint64_t i = 0; i < n_points; i++) {
+        const bool last = i + 1 == n_points ||
+                          memcmp(coords + idx[i] * ndim, coords + idx[i + 1] * ndim, ndim * sizeof(uint64_t)) != 0;
+        keep[idx[i]] = last ? 1 : 0;
+        kept += last;
+    }
+    return kept;
+}
+
+namespace zcg {
+int points_call(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+                const void* const* d_chunk_table, const uint64_t* d_coords, const uint64_t* d_order,
+                uint64_t n_points, void* d_vals, uint64_t* d_first_outside, void* stream, uint32_t dir);
+}
+
+namespace {
+
+struct SortedPoint {
+    uint64_t key;  // linear chunk index over the array's grid; ~0: the point visits no chunk
+    uint64_t at;   // element index inside the chunk, in the chunk memory order
+    uint64_t i;    // index in the caller's list
+};
+
+// plan_boxes for points: the same argument checks and in-grid rule (a point is
+// its 1-element box), then the sort and the groups.  Group::b0 .. b1 index
+// `pts`.  keep (write): only points with keep[i] != 0 take part, and points
+// that visit no chunk are dropped.
+int plan_points(zcg_ctx* ctx, const std::string& what, const zcg_array_meta* meta, const char* root, const char* path,
+                uint32_t fill_missing, const uint64_t* coords, const void* buf, uint64_t n_points,
+                const uint8_t* keep, uint64_t slot_budget_bytes, Plan& P, std::vector<SortedPoint>& pts) {
+    if (!ctx || !meta || !root || !path) return ZCG_ERR_INVALID_INPUT;
+    if (n_points && (!coords || !buf)) return ZCG_ERR_INVALID_INPUT;
+    auto say = [&](const std::string& e) { ctx_set_error(ctx, e); };
+    const int mrc = meta_args_status(what, meta, say);
+    if (mrc != ZCG_OK) return mrc;
+    const uint32_t nd = meta->ndim;
+    const uint32_t es = meta->array.dtype.elem_size;
+    if (es != 1 && es != 2 && es != 4 && es != 8) return ZCG_ERR_INVALID_INPUT;
+    P.nd = nd;
+    P.es = es;
+    if (n_points == 0) {
+        P.nothing = true;
+        return ZCG_OK;
+    }
+    if (n_points >= (1ull << 32)) {  // Group::b0 / b1
+        ctx_set_error(ctx, what + ": more than 2^32 points in one call");
+        return ZCG_ERR_UNSUPPORTED;
+    }
+    zcg_region& r = P.r;
+    memset(&r, 0, sizeof r);
+    r.ndim = nd;
+    r.elem_size = es;
+    r.chunk_order = meta->chunk_order;
+    r.fill_missing = fill_missing ? 1u : 0u;
+    r.fill_value = meta->has_fill_value ? meta->fill_value : 0;
+    uint64_t extent[ZCG_MAX_DIMS], cstr[ZCG_MAX_DIMS];
+    for (uint32_t d = 0; d < nd; d++) {
+        if (meta->chunk_shape[d] == 0) return ZCG_ERR_INVALID_INPUT;
+        r.array_shape[d] = meta->shape[d];
+        r.chunk_shape[d] = meta->chunk_shape[d];
+        r.bbox_shape[d] = 1;
+        extent[d] = u64_ceil_div(meta->shape[d], meta->chunk_shape[d]);
+    }
+    {
+        uint64_t g = 1, c = 1;
+        for (int d = (int)nd - 1; d >= 0; d--) {
+            P.gstr[d] = g;
+            if (extent[d] && g > (~0ull) / extent[d]) {
+                ctx_set_error(ctx, what + ": the array's chunk grid exceeds 2^64 chunks");
+                return ZCG_ERR_UNSUPPORTED;
+            }
+            g *= extent[d];
+        }
+        for (uint32_t k = 0; k < nd; k++) {
+            const uint32_t d = meta->chunk_order == 1 ? k : nd - 1 - k;
+            cstr[d] = c;
+            c *= meta->chunk_shape[d];
+        }
+    }
+    const uint64_t D = P.D = meta->array.chunk_num_elements * (uint64_t)es;
+    const uint64_t budget = slot_budget_bytes ? slot_budget_bytes : BOXES_DEFAULT_BUDGET;
+    const uint64_t max_chunks = std::max<uint64_t>(budget / std::max<uint64_t>(D, 1), 1);
+
+    // every point's chunk: in bounds (the reference panics at storage.rs:217)
+    pts.clear();
+    pts.reserve(n_points);
+    zcg_region rb = r;
+    for (uint64_t i = 0; i < n_points; i++) {
+        if (keep && !keep[i]) continue;
+        uint64_t lo[ZCG_MAX_DIMS], n[ZCG_MAX_DIMS];
+        for (uint32_t d = 0; d < nd; d++) rb.bbox_offset[d] = coords[i * nd + d];
+        SortedPoint sp{~0ull, 0, i};
+        if (zcg_region_grid(&rb, lo, n)) {
+            sp.key = 0;
+            for (uint32_t d = 0; d < nd; d++) {
+                if (lo[d] + n[d] - 1 >= extent[d]) {
+                    for (uint32_t k = 0; k < nd; k++) lo[k] += n[k] - 1;
+                    ctx_set_error(ctx, what + ": point " + std::to_string(i) + " visits chunk " + pos_text(lo, nd) +
+                                           " outside the array's chunk grid");
+                    return ZCG_ERR_INVALID_INPUT;
+                }
+                sp.key += lo[d] * P.gstr[d];
+                sp.at += (rb.bbox_offset[d] - lo[d] * r.chunk_shape[d]) * cstr[d];
+            }
+        } else if (keep) {
+            continue;  // write: no chunk, no element
+        }
+        pts.push_back(sp);
+    }
+    std::sort(pts.begin(), pts.end(), [](const SortedPoint& a, const SortedPoint& b) {
+        return a.key != b.key ? a.key < b.key : a.at != b.at ? a.at < b.at : a.i < b.i;
+    });
+
+    // groups: runs of sorted points whose unique chunks fit the budget; the points without a chunk end the last
+    Group cur{0, 0, {}, {}};
+    for (size_t s = 0; s < pts.size(); s++) {
+        const uint64_t key = pts[s].key;
+        if (key != ~0ull && (cur.keys.empty() || cur.keys.back() != key)) {
+            if (cur.keys.size() >= max_chunks) {
+                cur.b1 = (uint32_t)s;
+                P.groups.push_back(std::move(cur));
+                cur = Group{(uint32_t)s, (uint32_t)s, {}, {}};
+            }
+            cur.keys.push_back(key);
+        }
+    }
+    cur.b1 = (uint32_t)pts.size();
+    if (cur.b1 > cur.b0) P.groups.push_back(std::move(cur));
+    // a group's table: the bounding grid range of its chunks
+    const size_t ng = P.groups.size();
+    P.glo.assign(ng * ZCG_MAX_DIMS, 0);
+    P.gn.assign(ng * ZCG_MAX_DIMS, 0);
+    P.gentries.assign(ng, 0);
+    for (size_t g = 0; g < ng; g++) {
+        Group& G = P.groups[g];
+        // a one-element chunk is covered by its point; any other is read before the scatter
+        G.read_first.assign(G.keys.size(), meta->array.chunk_num_elements != 1 ? 1 : 0);
+        uint64_t hi[ZCG_MAX_DIMS] = {0}, pos[ZCG_MAX_DIMS];
+        uint64_t* lo = &P.glo[g * ZCG_MAX_DIMS];
+        for (size_t i = 0; i < G.keys.size(); i++) {
+            P.key_pos(G.keys[i], pos);
+            for (uint32_t d = 0; d < nd; d++) {
+                lo[d] = i ? std::min(lo[d], pos[d]) : pos[d];
+                hi[d] = i ? std::max(hi[d], pos[d] + 1) : pos[d] + 1;
+            }
+        }
+        uint64_t entries = G.keys.empty() ? 0 : 1;
+        for (uint32_t d = 0; d < nd; d++) {
+            P.gn[g * ZCG_MAX_DIMS + d] = hi[d] - lo[d];
+            entries = entries > BOXES_MAX_TABLE ? entries : entries * (hi[d] - lo[d]);
+        }
+        P.gentries[g] = entries;
+        if (entries > BOXES_MAX_TABLE) {
+            ctx_set_error(ctx, what + ": the points' chunk table (" + std::to_string(entries) +
+                                   " entries) exceeds 2^24; split the points over several calls");
+            return ZCG_ERR_UNSUPPORTED;
+        }
+    }
+    return ZCG_OK;
+}
+
+// The device side of one group of sorted points: [table entries][coordinates
+// np * nd][original indices np][the word for points outside the table].
+struct PointsDev {
+    DevMem mem;
+    size_t o_co = 0, o_ord = 0, o_fo = 0;
+    std::vector<uint64_t> host;  // coordinates, then indices
+};
+
+hipError_t points_upload(const Plan& P, const Group& G, const std::vector<SortedPoint>& pts, const uint64_t* coords,
+                         const void* const* table, uint64_t entries, PointsDev& X, hipStream_t s) {
+    const uint32_t nd = P.nd;
+    const size_t np = G.b1 - G.b0;
+    X.o_co = (entries * sizeof(void*) + 255) & ~(size_t)255;
+    X.o_ord = X.o_co + np * nd * sizeof(uint64_t);
+    X.o_fo = X.o_ord + np * sizeof(uint64_t);
+    hipError_t e = X.mem.alloc(X.o_fo + sizeof(uint64_t));
+    if (e != hipSuccess) return e;
+    X.host.resize(np * nd + np);
+    for (size_t i = 0; i < np; i++) {
+        const SortedPoint& sp = pts[G.b0 + i];
+        memcpy(&X.host[i * nd], coords + sp.i * nd, nd * sizeof(uint64_t));
+        X.host[np * nd + i] = sp.i;
+    }
+    uint8_t* db = (uint8_t*)X.mem.p;
+    if (entries) e = hipMemcpyAsync(db, table, entries * sizeof(void*), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(db + X.o_co, X.host.data(), X.host.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s);
+    return e;
+}
+
+int points_outside(zcg_ctx* ctx, const std::string& what, uint64_t first_outside) {
+    if (first_outside == ~0ull) return ZCG_OK;
+    ctx_set_error(ctx, what + ": sorted point " + std::to_string(first_outside) + " fell outside its group's table");
+    return ZCG_ERR_RUNTIME;
+}
+
+int read_points(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path, const uint64_t* coords,
+                uint64_t n_points, uint32_t fill_missing, void* out, uint64_t slot_budget_bytes, uint32_t io_threads,
+                bool host) {
+    const std::string what = "read_points";
+    Plan P;
+    std::vector<SortedPoint> pts;
+    // 1. before any file is read
+    const int prc = plan_points(ctx, what, meta, root, path, host ? 1 : fill_missing, coords, out, n_points, nullptr,
+                                slot_budget_bytes, P, pts);
+    if (prc != ZCG_OK) return prc;
+    if (P.nothing) return ZCG_OK;
+    const uint32_t es = P.es;
+
+    (void)hipSetDevice(ctx_device(ctx));
+    Stream st;
+    hipError_t e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
+    if (e != hipSuccess) return fail_hip(ctx, e, "read_points stream");
+
+    // 2. per group: read + decode its chunks once, build the table, one launch
+    std::vector<uint8_t> bounce;
+    for (size_t g = 0; g < P.groups.size(); g++) {
+        const Group& G = P.groups[g];
+        const uint32_t m = (uint32_t)G.keys.size();
+        const size_t np = G.b1 - G.b0;
+        const uint64_t* lo = &P.glo[g * ZCG_MAX_DIMS];
+        const uint64_t* n = &P.gn[g * ZCG_MAX_DIMS];
+        const uint64_t entries = P.gentries[g];
+        GroupSlots S;
+        DevMem staging;
+        std::vector<const void*> table(std::max<uint64_t>(entries, 1), nullptr);
+        if (m) {
+            int rc = group_slots(ctx, what, meta, root, path, P, g, S);
+            if (rc != ZCG_OK) return rc;
+            std::vector<int32_t> status(m, ZCG_OK);
+            rc = zcg_store_read_chunks_device(ctx, &meta->array, m, S.cpaths.data(), S.ptrs.data(), status.data(),
+                                              io_threads ? io_threads : 1);
+            if (rc != ZCG_OK) return rc;
+            for (uint32_t i = 0; i < m; i++) {
+                if (status[i] == ZCG_ABSENT) continue;  // read_chunk -> Ok(None): a NULL entry
+                if (status[i] != ZCG_OK) return chunk_failed(ctx, what, P, G.keys[i], status[i]);
+                table[S.tidx[i]] = S.ptrs[i];
+            }
+        }
+        PointsDev X;
+        if (host && (e = staging.alloc(np * es)) != hipSuccess) return fail_hip(ctx, e, "read_points staging");
+        e = points_upload(P, G, pts, coords, table.data(), entries, X, st.s);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(st.s);  // the host vectors of an enqueued copy end with this scope
+            return fail_hip(ctx, e, "read_points H2D");
+        }
+        uint8_t* db = (uint8_t*)X.mem.p;
+        // host: the group's values in sorted order, permuted below; device: straight to the caller's order
+        const int rc = points_call(ctx, &P.r, lo, n, (const void* const*)db, (const uint64_t*)(db + X.o_co),
+                                   host ? nullptr : (const uint64_t*)(db + X.o_ord), np, host ? staging.p : out,
+                                   (uint64_t*)(db + X.o_fo), (void*)st.s, 0);
+        if (rc != ZCG_OK) {
+            (void)hipStreamSynchronize(st.s);
+            return rc;
+        }
+        uint64_t first_outside = ~0ull;
+        e = hipMemcpyAsync(&first_outside, db + X.o_fo, sizeof first_outside, hipMemcpyDeviceToHost, st.s);
+        if (e == hipSuccess && host) {
+            bounce.resize(np * es);
+            e = hipMemcpyAsync(bounce.data(), staging.p, np * es, hipMemcpyDeviceToHost, st.s);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(st.s);
+        else (void)hipStreamSynchronize(st.s);
+        if (e != hipSuccess) return fail_hip(ctx, e, "read_points assembly");
+        const int orc = points_outside(ctx, what, first_outside);
+        if (orc != ZCG_OK) return orc;
+        if (host)
+            for (size_t i = 0; i < np; i++)
+                memcpy((uint8_t*)out + pts[G.b0 + i].i * es, bounce.data() + i * es, es);
+    }
+    return ZCG_OK;
+}
+
+// write_ndarray for the 1-element boxes of point 0, 1, ... in order: of two
+// points with one coordinate the later one counts (zcg_points_last), so the
+// kernel never sees two values for one element.  Per group: every chunk is
+// read (or, absent, prefilled) unless it has one element, the points are
+// scattered, and every chunk of the group is encoded and written once.
+int write_points(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path, const uint64_t* coords,
+                 uint64_t n_points, const void* in, uint64_t slot_budget_bytes, uint32_t io_threads, bool host) {
+    const std::string what = "write_points";
+    Plan P;
+    std::vector<SortedPoint> pts;
+    std::vector<uint8_t> keep(n_points, 1);
+    if (coords && meta && meta->ndim >= 1 && meta->ndim <= ZCG_MAX_DIMS)
+        zcg_points_last(coords, n_points, meta->ndim, keep.data());
+    // 1. before any file is read or written
+    const int prc = plan_points(ctx, what, meta, root, path, 0, coords, in, n_points, keep.data(), slot_budget_bytes,
+                                P, pts);
+    if (prc != ZCG_OK) return prc;
+    if (P.nothing) return ZCG_OK;
+    const uint32_t es = P.es;
+    const uint64_t fillv = meta->has_fill_value ? meta->fill_value : 0;
+    const uint32_t threads = io_threads ? io_threads : 1;
+
+    (void)hipSetDevice(ctx_device(ctx));
+    Stream st;
+    hipError_t e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
+    if (e != hipSuccess) return fail_hip(ctx, e, "write_points stream");
+
+    std::vector<uint8_t> bounce;
+    for (size_t g = 0; g < P.groups.size(); g++) {
+        const Group& G = P.groups[g];
+        const uint32_t m = (uint32_t)G.keys.size();
+        const size_t np = G.b1 - G.b0;
+        if (m == 0) continue;
+        const uint64_t* lo = &P.glo[g * ZCG_MAX_DIMS];
+        const uint64_t* n = &P.gn[g * ZCG_MAX_DIMS];
+        const uint64_t entries = P.gentries[g];
+        GroupSlots S;
+        DevMem staging, absent_dev;
+        int rc = group_slots(ctx, what, meta, root, path, P, g, S);
+        if (rc != ZCG_OK) return rc;
+
+        // 2. the existing chunks; absent ones start as fill value
+        std::vector<void*> absent;
+        if (G.read_first[0]) {
+            std::vector<int32_t> status(m, ZCG_OK);
+            rc = zcg_store_read_chunks_device(ctx, &meta->array, m, S.cpaths.data(), S.ptrs.data(), status.data(),
+                                              threads);
+            if (rc != ZCG_OK) return rc;
+            for (uint32_t i = 0; i < m; i++) {
+                if (status[i] == ZCG_ABSENT) absent.push_back(S.ptrs[i]);  // ndarray.rs:351-364
+                else if (status[i] != ZCG_OK) return chunk_failed(ctx, what, P, G.keys[i], status[i]);
+            }
+        }
+
+        // 3. the table (every chunk of the group has a slot), the points, the values
+        std::vector<void*> table(entries, nullptr);
+        for (uint32_t i = 0; i < m; i++) table[S.tidx[i]] = S.ptrs[i];
+        PointsDev X;
+        if (host && (e = staging.alloc(np * es)) != hipSuccess) return fail_hip(ctx, e, "write_points staging");
+        if (!absent.empty() && (e = absent_dev.alloc(absent.size() * sizeof(void*))) != hipSuccess)
+            return fail_hip(ctx, e, "write_points table");
+        e = points_upload(P, G, pts, coords, (const void* const*)table.data(), entries, X, st.s);
+        if (e == hipSuccess && !absent.empty())
+            e = hipMemcpyAsync(absent_dev.p, absent.data(), absent.size() * sizeof(void*), hipMemcpyHostToDevice, st.s);
+        if (e == hipSuccess && host) {
+            bounce.resize(np * es);
+            for (size_t i = 0; i < np; i++)
+                memcpy(bounce.data() + i * es, (const uint8_t*)in + pts[G.b0 + i].i * es, es);
+            e = hipMemcpyAsync(staging.p, bounce.data(), np * es, hipMemcpyHostToDevice, st.s);
+        }
+        if (e == hipSuccess)
+            e = launch_slot_fill((void* const*)absent_dev.p, (uint32_t)absent.size(), P.D, es, fillv, st.s);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(st.s);  // the host vectors of an enqueued copy end with this scope
+            return fail_hip(ctx, e, "write_points H2D");
+        }
+
+        // 4. the scatter: no two points of the call share an element
+        uint8_t* db = (uint8_t*)X.mem.p;
+        rc = points_call(ctx, &P.r, lo, n, (const void* const*)db, (const uint64_t*)(db + X.o_co),
+                         host ? nullptr : (const uint64_t*)(db + X.o_ord), np, host ? staging.p : (void*)in,
+                         (uint64_t*)(db + X.o_fo), (void*)st.s, 1);
+        if (rc != ZCG_OK) {
+            (void)hipStreamSynchronize(st.s);
+            return rc;
+        }
+        uint64_t first_outside = ~0ull;
+        e = hipMemcpyAsync(&first_outside, db + X.o_fo, sizeof first_outside, hipMemcpyDeviceToHost, st.s);
+        if (e == hipSuccess) e = hipStreamSynchronize(st.s);
+        else (void)hipStreamSynchronize(st.s);
+        if (e != hipSuccess) return fail_hip(ctx, e, "write_points scatter");
+        rc = points_outside(ctx, what, first_outside);
+        if (rc != ZCG_OK) return rc;
+
+        // 5. encode and write every chunk of the group, once
+        std::vector<int32_t> wst(m, ZCG_OK);
+        rc = zcg_store_write_chunks_device(ctx, &meta->array, m, S.cpaths.data(), (const void* const*)S.ptrs.data(),
+                                           wst.data(), threads);
+        if (rc != ZCG_OK) return rc;
+        for (uint32_t i = 0; i < m; i++)
+            if (wst[i] != ZCG_OK) return chunk_failed(ctx, what, P, G.keys[i], wst[i]);
+    }
+    return ZCG_OK;
+}
+
+}  // namespace
+
+extern "C" int zcg_store_read_points_device(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root,
+                                            const char* path, const uint64_t* coords, uint64_t n_points,
+                                            uint32_t fill_missing, void* d_out, uint64_t slot_budget_bytes,
+                                            uint32_t io_threads) {
+    return read_points(ctx, meta, root, path, coords, n_points, fill_missing, d_out, slot_budget_bytes, io_threads,
+                       false);
+}
+
+extern "C" int zcg_store_read_points(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                                     const uint64_t* coords, uint64_t n_points, void* out,
+                                     uint64_t slot_budget_bytes, uint32_t io_threads) {
+    return read_points(ctx, meta, root, path, coords, n_points, 1, out, slot_budget_bytes, io_threads, true);
+}
+
+extern "C" int zcg_store_write_points_device(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root,
+                                             const char* path, const uint64_t* coords, uint64_t n_points,
+                                             const void* d_in, uint64_t slot_budget_bytes, uint32_t io_threads) {
+    return write_points(ctx, meta, root, path, coords, n_points, d_in, slot_budget_bytes, io_threads, false);
+}
+
+extern "C" int zcg_store_write_points(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                                      const uint64_t* coords, uint64_t n_points, const void* in,
+                                      uint64_t slot_budget_bytes, uint32_t io_threads) {
+    return write_points(ctx, meta, root, path, coords, n_points, in, slot_budget_bytes, io_threads, true);
+}

@@ -287,6 +287,11 @@ struct BoxTable {
     u64 tn[ZCG_MAX_DIMS];      // table extent
 };
 
+// Division of a point's coordinate by the chunk extent (zcg_region_p.hip).
+struct PointRecip {
+    u64 m[ZCG_MAX_DIMS];       // per dim, fast-first order: ceil(2^64 / chunk extent); unused for an extent of 1
+};
+
 }  // namespace zcg
 
 // Internal launchers (zcg_*.hip) used by zcg_api.cpp.
@@ -417,6 +422,14 @@ hipError_t launch_regions_s_plan(const RegionWalk& w, const BoxTable& bt, const 
                                  const zcg_sbox* d_boxes, void* d_prefix, int32_t* d_status, hipStream_t s);
 hipError_t launch_regions_sw(const RegionWalk& w, const BoxTable& bt, void* const* d_table, const zcg_sbox* d_boxes,
                              void* d_prefix, int32_t* d_status, hipStream_t s);
+// A list of coordinates (zcg_region_p.hip): w.bs, w.total, w.ostr, bt.nboxes
+// and bt.upb are unused.  Point p's value is element d_order[p] of d_vals, or
+// element p when d_order is NULL; *d_first_outside is reset on the stream by a
+// copy of *d_all_ones (a device word holding UINT64_MAX) and lowered to the
+// lowest p whose chunk is outside the table.
+hipError_t launch_points(const RegionWalk& w, const BoxTable& bt, const PointRecip& rc, uint64_t n,
+                         const void* const* d_table, const uint64_t* d_coords, const uint64_t* d_order, void* d_vals,
+                         uint64_t* d_first_outside, const uint64_t* d_all_ones, uint32_t dir, hipStream_t s);
 // m device slots of D bytes (d_slots: DEVICE array of their bases, each a
 // multiple of `es`), filled with the element `fillv`
 hipError_t launch_slot_fill(void* const* d_slots, uint32_t m, uint64_t D, uint32_t es, uint64_t fillv,

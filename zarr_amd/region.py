@@ -924,3 +924,157 @@ def _write_sub_batch(hier, path_name, meta, bbox, coords, b0, b1, dt, D, N, cap,
     if len(bad):
         i = int(bad[0])
         raise ZarrIOError(_native.STATUS_NAMES.get(int(st[i]), str(st[i])), f"chunk {list(coords[b0 + i])}")
+
+
+# ---- a list of coordinates (numpy's a[i, j, k] with index arrays) -------------
+
+def _coords_arg(coords, nd: int) -> np.ndarray:
+    """`coords` as a contiguous (P, ndim) uint64 array: a (P, ndim) integer
+    array, or a tuple of ndim index arrays as numpy's a[i, j, k] takes."""
+    if isinstance(coords, tuple):
+        if len(coords) != nd:
+            raise ZarrIOError("InvalidData", "Wrong number of dimensions")
+        cols = [np.asarray(c).reshape(-1) for c in coords]
+        if len({c.shape[0] for c in cols}) > 1:
+            raise ValueError("index arrays differ in length")
+        a = np.stack(cols, axis=1) if cols[0].shape[0] else np.zeros((0, nd), np.uint64)
+    else:
+        a = np.asarray(coords)
+        if a.size == 0:
+            a = np.zeros((0, nd), np.uint64)
+        if a.ndim != 2 or a.shape[1] != nd:
+            raise ZarrIOError("InvalidData", "Wrong number of dimensions")
+    if a.dtype.kind not in "iu" and a.dtype != object:
+        raise TypeError("coordinates must be integers")
+    if a.size and (a.dtype.kind == "i" or a.dtype == object) and min(int(x) for x in a.reshape(-1)) < 0:
+        raise ValueError("negative coordinate")
+    return np.ascontiguousarray(a.astype(np.uint64))
+
+
+def points_grid(meta: ArrayMetadata, coords):
+    """zcg_points_grid (host code, no GPU): the smallest grid range that holds
+    every chunk a point visits -> (lo, n); regions_v_grid with shapes all 1."""
+    L = _native.load_library()
+    nd = meta.get_ndim()
+    r = _region(meta, BoundingBox([0] * nd, [1] * nd), 1, False, 0, [0] * nd)
+    c = _coords_arg(coords, nd)
+    lo = (ctypes.c_uint64 * _native.MAX_DIMS)()
+    n = (ctypes.c_uint64 * _native.MAX_DIMS)()
+    L.zcg_points_grid(ctypes.byref(r), c.ctypes.data, c.shape[0], ctypes.addressof(lo), ctypes.addressof(n))
+    return [int(lo[d]) for d in range(nd)], [int(n[d]) for d in range(nd)]
+
+
+def points_last(coords) -> np.ndarray:
+    """zcg_points_last (host code, no GPU): a bool array, True where no later
+    point has the same coordinate.  `coords` is (P, ndim)."""
+    L = _native.load_library()
+    a = np.asarray(coords)
+    c = _coords_arg(coords, len(coords) if isinstance(coords, tuple) else (a.shape[1] if a.ndim == 2 else 1))
+    keep = np.zeros(max(c.shape[0], 1), np.uint8)
+    L.zcg_points_last(c.ctypes.data, c.shape[0], c.shape[1], keep.ctypes.data)
+    return keep[: c.shape[0]].astype(bool)
+
+
+def _points(name: str, meta: ArrayMetadata, es, table, table_lo, table_n, coords, vals, first_outside, fill,
+            fill_value, device, stream) -> None:
+    ctx = _native.context(device)
+    nd = meta.get_ndim()
+    r = _region(meta, BoundingBox([0] * nd, [1] * nd), es, fill, fill_value, [0] * nd)
+    lo = (ctypes.c_uint64 * _native.MAX_DIMS)(*[int(x) for x in table_lo])
+    n = (ctypes.c_uint64 * _native.MAX_DIMS)(*[int(x) for x in table_n])
+    P = coords.numel() * coords.element_size() // (8 * nd) if coords is not None else 0
+    st = getattr(ctx.lib, name)(ctx.handle, ctypes.byref(r), ctypes.addressof(lo), ctypes.addressof(n),
+                                table.data_ptr() if table is not None else None,
+                                coords.data_ptr() if P else None, P,
+                                vals.data_ptr() if vals is not None else None,
+                                first_outside.data_ptr() if first_outside is not None else None,
+                                _stream_handle(stream, device))
+    _raise_status(st, ctx, name[4:])
+
+
+def assemble_points(meta: ArrayMetadata, es: int, table, table_lo, table_n, coords, out, first_outside,
+                    fill: bool = False, fill_value: int = 0, device: int = 0, stream=None) -> None:
+    """Device-level gather (zcg_read_points): `coords` = device int64/uint64
+    tensor of P x ndim coordinates, `out` = dense device tensor of P elements,
+    `first_outside` = device tensor of one 64-bit word (UINT64_MAX, or the
+    lowest index of a point whose chunk lies outside the table).  The table
+    arguments are assemble_regions'.  Asynchronous."""
+    _points("zcg_read_points", meta, es, table, table_lo, table_n, coords, out, first_outside, fill, fill_value,
+            device, stream)
+
+
+def scatter_points(meta: ArrayMetadata, es: int, table, table_lo, table_n, coords, values, first_outside,
+                   device: int = 0, stream=None) -> None:
+    """Device-level inverse of assemble_points (zcg_write_points): value i goes
+    to the chunk slot element of point i.  Points of one call that share a
+    coordinate leave either value; drop the earlier ones with points_last where
+    the later one must win.  Asynchronous."""
+    _points("zcg_write_points", meta, es, table, table_lo, table_n, coords, values, first_outside, False, 0,
+            device, stream)
+
+
+def read_points(hier, path_name: str, meta: ArrayMetadata, coords, t, device: int = 0, as_tensor: bool = False,
+                slot_budget_bytes: int = 0, io_threads: int = 0, flags: int = 0):
+    """a[coords] in one native call (zcg_store_read_points[_device]): a 1-D
+    array (with as_tensor a device tensor) of len(coords) elements, element i
+    being read_ndarray of the 1-element box at coords[i].  Only the chunks that
+    hold a point are opened, each decoded once."""
+    import torch
+    check_array_type(t, meta)
+    nd = meta.get_ndim()
+    c = _coords_arg(coords, nd)
+    P = c.shape[0]
+    dt = np.dtype(t).newbyteorder("=")
+    am = _native_meta(meta, flags)
+    ctx = _native.context(device)
+    root, path = os.fsencode(hier.base_path), path_name.encode()
+    threads = io_threads or 16
+    if as_tensor:
+        out = torch.empty(max(P, 1) * dt.itemsize, dtype=torch.uint8, device=torch.device("cuda", device))
+        r = ctx.lib.zcg_store_read_points_device(ctx.handle, ctypes.byref(am), root, path, c.ctypes.data, P, 1,
+                                                 out.data_ptr(), slot_budget_bytes, threads)
+    else:
+        host = np.empty(max(P, 1), dt)
+        r = ctx.lib.zcg_store_read_points(ctx.handle, ctypes.byref(am), root, path, c.ctypes.data, P,
+                                          host.ctypes.data, slot_budget_bytes, threads)
+    if r != _native.OK:
+        raise ZarrIOError(_native.STATUS_NAMES.get(r, str(r)), f"read_points: {ctx.last_error()}")
+    if as_tensor:
+        return out[: P * dt.itemsize].view(getattr(torch, dt.name)) if hasattr(torch, dt.name) else out[: P * dt.itemsize]
+    return host[:P]
+
+
+def write_points(hier, path_name: str, meta: ArrayMetadata, coords, values, device: int = 0,
+                 slot_budget_bytes: int = 0, io_threads: int = 0, flags: int = 0) -> None:
+    """a[coords] = values in one native call (zcg_store_write_points[_device]):
+    the store ends up as if write_ndarray had run for the 1-element boxes in
+    order, so of two points with one coordinate the later one wins.  `values`
+    is a numpy array, or a device tensor, of len(coords) elements.  Every chunk
+    that holds a point is read at most once, and encoded and written once.
+    `flags`: decode flags for the chunks that are read first."""
+    nd = meta.get_ndim()
+    c = _coords_arg(coords, nd)
+    P = c.shape[0]
+    am = _native_meta(meta, flags)
+    ctx = _native.context(device)
+    root, path = os.fsencode(hier.base_path), path_name.encode()
+    threads = io_threads or 16
+    if hasattr(values, "data_ptr"):
+        if values.numel() != P:
+            raise ZarrIOError("InvalidData", "Coordinates and values differ in number")
+        v = values.contiguous()
+        if v.element_size() != am.array.dtype.elem_size:
+            raise ZarrIOError("InvalidData", "Element size differs from the array's")
+        r = ctx.lib.zcg_store_write_points_device(ctx.handle, ctypes.byref(am), root, path, c.ctypes.data, P,
+                                                  v.data_ptr(), slot_budget_bytes, threads)
+    else:
+        a = np.asarray(values).reshape(-1)
+        if a.shape[0] != P:
+            raise ZarrIOError("InvalidData", "Coordinates and values differ in number")
+        dt = a.dtype.newbyteorder("=")
+        check_array_type(dt, meta)
+        a = np.ascontiguousarray(a.astype(dt, copy=False))
+        r = ctx.lib.zcg_store_write_points(ctx.handle, ctypes.byref(am), root, path, c.ctypes.data, P,
+                                           a.ctypes.data if P else None, slot_budget_bytes, threads)
+    if r != _native.OK:
+        raise ZarrIOError(_native.STATUS_NAMES.get(r, str(r)), f"write_points: {ctx.last_error()}")
