@@ -24,7 +24,10 @@ The device legs time with HIP events on the launch stream after a warm-up,
 `--repeats` times alternating the sides in one process, and report the median
 and the min..max spread of each.  Writes profiles/boxes_v_bench.json.
 
-usage: tools/boxes_v_bench.py [--repeats R] [--out FILE] [--legs mixed,skew,uniform,store]
+The store leg runs 3 repeats at the most (its loop sides take 5 s per repeat)
+unless --uncapped is given.
+
+usage: tools/boxes_v_bench.py [--repeats R] [--out FILE] [--legs mixed,skew,uniform,store] [--uncapped]
 """
 import argparse
 import ctypes
@@ -248,7 +251,7 @@ def leg_store(repeats):
     import torch
     from zarr_amd import ArrayMetadata, FilesystemHierarchy, Gzip, SliceDataChunk
     from zarr_amd.region import BoundingBox, read_ndarray, read_ndarrays_v, region_grid, write_ndarray, write_ndarrays_v
-    repeats = min(repeats, 3)
+    repeats = repeats if UNCAPPED else min(repeats, 3)  # the loop sides take 5 s per repeat
     meta = ArrayMetadata.new([256] * 3, [64] * 3, "<u2", Gzip(6))
     meta.chunk_memory_layout = "C"
     rng = np.random.default_rng(3)
@@ -300,6 +303,8 @@ def leg_store(repeats):
             "write_speedup_of_medians": round(s["write_loop"]["median_ms"] / s["write_one"]["median_ms"], 2)}
 
 
+UNCAPPED = False  # --uncapped: the store leg runs --repeats repeats, not 3 at the most
+
 LEGS = {"mixed": leg_mixed, "skew": leg_skew, "uniform": leg_uniform, "store": leg_store}
 
 
@@ -308,8 +313,11 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "boxes_v_bench.json"))
     ap.add_argument("--legs", default="mixed,skew,uniform,store")
+    ap.add_argument("--uncapped", action="store_true", help="store leg: do not cap the repeats at 3")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    global UNCAPPED
+    UNCAPPED = args.uncapped
     if args.child:
         print("RESULT " + json.dumps(LEGS[args.child](args.repeats)))
         return 0
@@ -317,7 +325,8 @@ def main():
     for name in args.legs.split(","):
         try:
             p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name, "--repeats",
-                                str(args.repeats)], capture_output=True, text=True, timeout=LIMITS[name])
+                                str(args.repeats)] + (["--uncapped"] if args.uncapped else []),
+                               capture_output=True, text=True, timeout=LIMITS[name])
         except subprocess.TimeoutExpired:
             print(f"{name}: no result inside {LIMITS[name]} s; stopping", file=sys.stderr)
             return 1

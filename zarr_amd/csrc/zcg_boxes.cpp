@@ -1,30 +1,47 @@
-// zcg_boxes.cpp — read_ndarray for many bounding boxes in one native call
-// (ZarrNdarrayReader::read_ndarray, src/ndarray.rs:153-268, once per box in the
-// reference): the chunks all boxes visit are read and decoded once
-// (zcg_store_read_chunks_device), and every box is assembled from the shared
-// chunk table by one zcg_read_regions launch.
+// zcg_boxes.cpp — the store-level calls for many boxes and for a list of
+// coordinates (ZarrNdarrayReader::read_ndarray, src/ndarray.rs:153-268, and
+// write_ndarray, ndarray.rs:276-385, once per box in the reference): plan, then
+// one driver.
 //
-// Boxes are taken in consecutive groups whose unique chunks fit a budget of
-// decoded device slots; a chunk two groups share is decoded in each.
+// Plan (before any file is opened).  plan_head checks what `meta` alone decides
+// and fills the region descriptor all items share; plan_boxes and plan_points
+// add the in-grid check of every visited chunk and take the items in
+// consecutive groups whose unique chunks fit a budget of decoded device slots
+// (a chunk two groups share is decoded in each), each group with its union
+// table range.  A strided box's chunks (the _s calls) are the touched ones
+// (zcg_region_s_chunks), not the hull's whole grid range; points are sorted by
+// chunk first, so a group is a run of sorted points.
 //
-// write_ndarray for many boxes (ndarray.rs:276-385) is the same plan the other
-// way round: per group the chunks under a partial first box are read (absent
-// ones prefilled), the boxes are scattered in the waves of zcg_regions_waves
-// (zcg_write_regions per wave, so a later box wins), and every chunk of the
-// group is encoded and written once (zcg_store_write_chunks_device).
+// Driver.  run_groups is the per-group loop, once for both directions and both
+// kinds of item.  It owns the stream, the group's slots and chunk files, which
+// chunks are read first, the chunk table, the absent list and its fill, the one
+// synchronisation per group (also the one place where an error after an
+// enqueued copy waits before the host vectors go out of scope), the per-chunk
+// failure report and, on the write side, the one encode-and-write of every
+// chunk of the group.
+//   read:  every chunk of the group is read and decoded once; an absent one is
+//          a NULL table entry.  A group without chunks still launches: items
+//          outside every chunk get fill.
+//   write: a group without chunks is skipped; only chunks with read_first set
+//          are read (boxes: those whose first visiting box leaves part of them
+//          uncovered; points: all, unless a chunk is one element), absent ones
+//          start as fill value; nothing is written if a step before failed.
 //
-// The _v calls take a shape per box; they share the planner and the two
-// drivers with the one-shape calls, which pass one shape for all boxes and
-// keep the one-shape kernels (zcg_read_regions / zcg_write_regions); boxes of
-// differing shapes go through zcg_read_regions_v / zcg_write_regions_v.
-//
-// The _s calls add a step per box and dimension: the planner then takes a
-// box's chunks from zcg_region_s_chunks (the touched chunks, a product of
-// per-dimension index sets) instead of the hull's whole grid range, and the
-// boxes are assembled by zcg_read_regions_s or scattered by
-// zcg_write_regions_s in the waves of zcg_regions_s_waves.  On the write side
-// a touched chunk is read first unless its first box covers it sample by
-// sample (step 1, or a chunk extent of 1, along every dimension).
+// Payloads.  What is scattered or assembled is the payload's business: its part
+// of the group's device block, its staging and bounce copies, its launches, its
+// status check and its host copy-back.
+//   BoxPayload:    [records nb][status nb][scratch of the _v kernels].  One
+//                  shape for all boxes keeps the one-shape kernels
+//                  (zcg_read_regions / zcg_write_regions), a shape per box the
+//                  _v kernels, a step per box and dimension the _s kernels.  A
+//                  read is one launch; a write is one launch per wave of
+//                  zcg_regions[_v|_s]_waves, so a later box wins.  Host callers
+//                  get one copy per group, straight to or from their memory
+//                  when the boxes are consecutive, else through a bounce buffer.
+//   PointsPayload: [coordinates np * nd][original indices np][first-outside
+//                  word].  One launch (zcg_region_p.hip); a device caller's
+//                  values stay in the caller's order through the index array,
+//                  host values are permuted on the host.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -52,9 +69,11 @@ uint64_t u64_ceil_div(uint64_t a, uint64_t b) { return (a + 1) / b + (a % b != 0
 
 struct DevMem {
     void* p = nullptr;
-    ~DevMem() { if (p) (void)hipFree(p); }
+    ~DevMem() { release(); }
+    void release() { if (p) (void)hipFree(p); p = nullptr; }
     hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 256)); }
 };
+size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 struct Stream {
     hipStream_t s = nullptr;
     ~Stream() { if (s) (void)hipStreamDestroy(s); }
@@ -72,8 +91,8 @@ std::string pos_text(const uint64_t* pos, uint32_t nd) {
     return s + "]";
 }
 
-int fail_hip(zcg_ctx* ctx, hipError_t e, const char* what) {
-    ctx_set_error(ctx, std::string(what) + ": " + hipGetErrorString(e));
+int fail_hip(zcg_ctx* ctx, hipError_t e, const std::string& what) {
+    ctx_set_error(ctx, what + ": " + hipGetErrorString(e));
     return ZCG_ERR_RUNTIME;
 }
 
@@ -90,8 +109,10 @@ struct Plan {
     const uint64_t* steps = nullptr;    // the _s calls (varied): box b's steps, steps + b * nd; shapes are sample counts
     size_t sstep = 0;
     std::vector<uint64_t> at;           // byte offset of box b among the boxes back to back, dense (n_boxes + 1)
+    uint64_t extent[ZCG_MAX_DIMS];      // the array's chunk grid
     uint64_t gstr[ZCG_MAX_DIMS];        // linear chunk keys over the array's grid
-    bool nothing = false;               // n_boxes == 0: the call is done
+    uint64_t budget = 0;                // bytes of decoded slots a group may hold
+    bool nothing = false;               // no box, no point: the call is done
     std::vector<Group> groups;
     std::vector<uint64_t> glo, gn, gentries;  // per group: table range (ZCG_MAX_DIMS each), entries
 
@@ -151,6 +172,63 @@ int sbox_args_status(const std::string& what, uint32_t b, uint32_t nd, const uin
     return ZCG_OK;
 }
 
+// What plan_boxes and plan_points share, up to "nothing to do" (P.nothing) and
+// on to the region descriptor and the array's chunk grid.  It comes in two
+// parts, because plan_boxes refuses boxes above 2^62 bytes between them and a
+// call that is wrong in two ways keeps its status.  `where` and `bufs`: the
+// items' positions and memory, NULL only without items; `items` names them in
+// the refusal of 2^32 and more (Group::b0 / b1 are 32-bit).
+int plan_head(zcg_ctx* ctx, const std::string& what, const zcg_array_meta* meta, const char* root, const char* path,
+              const void* where, const void* bufs, uint64_t n, const char* items, bool fill_missing, Plan& P) {
+    if (!ctx || !meta || !root || !path) return ZCG_ERR_INVALID_INPUT;
+    if (n && (!where || !bufs)) return ZCG_ERR_INVALID_INPUT;
+    const int mrc = meta_args_status(what, meta, [&](const std::string& e) { ctx_set_error(ctx, e); });
+    if (mrc != ZCG_OK) return mrc;
+    const uint32_t nd = meta->ndim;
+    const uint32_t es = meta->array.dtype.elem_size;
+    if (es != 1 && es != 2 && es != 4 && es != 8) return ZCG_ERR_INVALID_INPUT;
+    P.nd = nd;
+    P.es = es;
+    P.D = meta->array.chunk_num_elements * (uint64_t)es;
+    if (n == 0) {
+        P.nothing = true;
+        return ZCG_OK;
+    }
+    if (n >= (1ull << 32)) {
+        ctx_set_error(ctx, what + ": more than 2^32 " + items + " in one call");
+        return ZCG_ERR_UNSUPPORTED;
+    }
+    zcg_region& r = P.r;
+    memset(&r, 0, sizeof r);
+    r.ndim = nd;
+    r.elem_size = es;
+    r.chunk_order = meta->chunk_order;
+    r.fill_missing = fill_missing ? 1u : 0u;
+    r.fill_value = meta->has_fill_value ? meta->fill_value : 0;
+    for (uint32_t d = 0; d < nd; d++) {
+        if (meta->chunk_shape[d] == 0) return ZCG_ERR_INVALID_INPUT;
+        r.array_shape[d] = meta->shape[d];
+        r.chunk_shape[d] = meta->chunk_shape[d];
+        P.extent[d] = u64_ceil_div(meta->shape[d], meta->chunk_shape[d]);
+    }
+    return ZCG_OK;
+}
+
+// plan_head's second part: linear chunk keys over the grid, and the budget
+int plan_head_grid(zcg_ctx* ctx, const std::string& what, uint64_t slot_budget_bytes, Plan& P) {
+    uint64_t g = 1;
+    for (int d = (int)P.nd - 1; d >= 0; d--) {
+        P.gstr[d] = g;
+        if (P.extent[d] && g > (~0ull) / P.extent[d]) {
+            ctx_set_error(ctx, what + ": the array's chunk grid exceeds 2^64 chunks");
+            return ZCG_ERR_UNSUPPORTED;
+        }
+        g *= P.extent[d];
+    }
+    P.budget = slot_budget_bytes ? slot_budget_bytes : BOXES_DEFAULT_BUDGET;
+    return ZCG_OK;
+}
+
 // Argument checks, the in-bounds check of every visited chunk (the reference
 // panics at storage.rs:217) and the grouping under the slot budget.  `what`
 // prefixes the messages.  host == true: boxes are host buffers, each dense in
@@ -166,43 +244,18 @@ int plan_boxes(zcg_ctx* ctx, const std::string& what, const zcg_array_meta* meta
                uint32_t fill_missing,
                const uint64_t* offsets, const void* const* bufs, uint32_t n_boxes, uint64_t slot_budget_bytes,
                bool host, bool cover, Plan& P) {
-    if (!ctx || !meta || !root || !path || (!box_shape && !(varied && n_boxes == 0)) ||
-        (!host && !strides && !varied))
-        return ZCG_ERR_INVALID_INPUT;
-    if (n_boxes && (!offsets || !bufs)) return ZCG_ERR_INVALID_INPUT;
+    if ((!box_shape && !(varied && n_boxes == 0)) || (!host && !strides && !varied)) return ZCG_ERR_INVALID_INPUT;
     auto say = [&](const std::string& e) { ctx_set_error(ctx, e); };
-    const int mrc = meta_args_status(what, meta, say);
-    if (mrc != ZCG_OK) return mrc;
-    const uint32_t nd = meta->ndim;
-    const uint32_t es = meta->array.dtype.elem_size;
-    if (es != 1 && es != 2 && es != 4 && es != 8) return ZCG_ERR_INVALID_INPUT;
-    P.nd = nd;
-    P.es = es;
-    if (n_boxes == 0) {
-        P.nothing = true;
-        return ZCG_OK;
-    }
-
+    const int hrc = plan_head(ctx, what, meta, root, path, offsets, bufs, n_boxes, "boxes", host || fill_missing, P);
+    if (hrc != ZCG_OK || P.nothing) return hrc;
+    const uint32_t nd = P.nd, es = P.es;
     zcg_region& r = P.r;
-    uint64_t* gstr = P.gstr;
+    const uint64_t *gstr = P.gstr, *extent = P.extent;
     P.varied = varied;
     P.shapes = box_shape;
     P.sstep = varied ? nd : 0;
     P.strides = varied && !host ? strides : nullptr;
     P.steps = box_steps;
-    memset(&r, 0, sizeof r);
-    r.ndim = nd;
-    r.elem_size = es;
-    r.chunk_order = meta->chunk_order;
-    r.fill_missing = host ? 1u : (fill_missing ? 1u : 0u);
-    r.fill_value = meta->has_fill_value ? meta->fill_value : 0;
-    uint64_t extent[ZCG_MAX_DIMS];
-    for (uint32_t d = 0; d < nd; d++) {
-        if (meta->chunk_shape[d] == 0) return ZCG_ERR_INVALID_INPUT;
-        r.array_shape[d] = meta->shape[d];
-        r.chunk_shape[d] = meta->chunk_shape[d];
-        extent[d] = u64_ceil_div(meta->shape[d], meta->chunk_shape[d]);
-    }
     // the boxes back to back, and the bound of their extents
     P.at.assign((size_t)n_boxes + 1, 0);
     for (uint32_t b = 0; b < n_boxes; b++) {
@@ -218,25 +271,17 @@ int plan_boxes(zcg_ctx* ctx, const std::string& what, const zcg_array_meta* meta
         }
         P.at[b + 1] = P.at[b] + elems * es;
     }
-    {   // dense host layout in the chunk memory order; linear chunk keys over the grid
+    {   // dense host layout in the chunk memory order
         int64_t acc = 1;
-        uint64_t g = 1;
         for (uint32_t k = 0; k < nd; k++) {
             const uint32_t d = meta->chunk_order == 1 ? k : nd - 1 - k;
             r.out_strides[d] = varied ? 0 : host ? acc : strides[d];
             acc *= (int64_t)std::max<uint64_t>(r.bbox_shape[d], 1);
         }
-        for (int d = (int)nd - 1; d >= 0; d--) {
-            gstr[d] = g;
-            if (extent[d] && g > (~0ull) / extent[d]) {
-                ctx_set_error(ctx, what + ": the array's chunk grid exceeds 2^64 chunks");
-                return ZCG_ERR_UNSUPPORTED;
-            }
-            g *= extent[d];
-        }
     }
-    const uint64_t D = P.D = meta->array.chunk_num_elements * (uint64_t)es;
-    const uint64_t budget = slot_budget_bytes ? slot_budget_bytes : BOXES_DEFAULT_BUDGET;
+    const int grc = plan_head_grid(ctx, what, slot_budget_bytes, P);
+    if (grc != ZCG_OK) return grc;
+    const uint64_t D = P.D, budget = P.budget;
 
     // every box's visited chunks: in bounds, grouped under the slot budget.
     // seen: chunk key -> does the group's first box to visit it leave part of
@@ -480,244 +525,91 @@ int regions_launch(zcg_ctx* ctx, const Plan& P, const uint64_t* lo, const uint64
                                   (void*)s);
 }
 
-// host == true: outs are host buffers, each box dense in the chunk memory
-// order with fill (read_ndarray); else device views with the caller's strides.
-// varied: plan_boxes' (a shape, and as a device view strides, per box).
-int read_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
-               const uint64_t* box_shape, const uint64_t* box_steps, const int64_t* out_strides, bool varied,
-               uint32_t fill_missing,
-               const uint64_t* offsets, void* const* outs, uint32_t n_boxes, uint64_t slot_budget_bytes,
-               uint32_t io_threads, bool host) {
-    const std::string what = "read_boxes";
-    Plan P;
-    // 1. before any file is read
-    const int prc = plan_boxes(ctx, what, meta, root, path, box_shape, box_steps, out_strides, varied, fill_missing,
-                               offsets, outs, n_boxes, slot_budget_bytes, host, false, P);
-    if (prc != ZCG_OK) return prc;
-    if (P.nothing || P.at[n_boxes] == 0) return ZCG_OK;
-
+// The per-group loop of every store-level call (the header comment has the
+// contract).  Payload X, per group G and in this order:
+//   X.device_bytes(G)                 bytes of its part of the group's device block
+//   X.upload(G, d_part, stream)       its records and a host caller's values, enqueued
+//   X.launch(ctx, G, lo, n, d_table, stream)
+//                                     its kernels, then its status and a host caller's
+//                                     results on their way back, enqueued
+//   X.finish(ctx, G)                  after the synchronisation: its status check and
+//                                     host copy-back
+// Host memory that X hands to an enqueued copy must live as long as X does.
+template <class Payload>
+int run_groups(zcg_ctx* ctx, const std::string& what, const zcg_array_meta* meta, const char* root, const char* path,
+               const Plan& P, bool write, uint32_t io_threads, Payload& X) {
+    const uint32_t threads = io_threads ? io_threads : 1;
+    const uint64_t fillv = meta->has_fill_value ? meta->fill_value : 0;
     (void)hipSetDevice(ctx_device(ctx));
     Stream st;
     hipError_t e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
-    if (e != hipSuccess) return fail_hip(ctx, e, "read_boxes stream");
+    if (e != hipSuccess) return fail_hip(ctx, e, what + " stream");
 
-    // 2. per group: read + decode its chunks once, build the table, one launch
     for (size_t g = 0; g < P.groups.size(); g++) {
         const Group& G = P.groups[g];
-        const uint32_t nb = G.b1 - G.b0, m = (uint32_t)G.keys.size();
+        const uint32_t m = (uint32_t)G.keys.size();
+        if (write && m == 0) continue;  // no item of the group visits a chunk: nothing to write
         const uint64_t* lo = &P.glo[g * ZCG_MAX_DIMS];
         const uint64_t* n = &P.gn[g * ZCG_MAX_DIMS];
         const uint64_t entries = P.gentries[g];
         GroupSlots S;
-        DevMem meta_dev, staging;
-        std::vector<const void*> table(std::max<uint64_t>(entries, 1), nullptr);
+        DevMem block;
+
+        // 1. the chunks that are read first: all of them (read), or those a write leaves partly as
+        // they were.  Read: an absent chunk is a NULL entry (read_chunk -> Ok(None)); write: every
+        // chunk has a slot, and an absent one starts as fill value (ndarray.rs:351-364)
+        std::vector<void*> table(std::max<uint64_t>(entries, 1), nullptr), absent;
         if (m) {
             int rc = group_slots(ctx, what, meta, root, path, P, g, S);
             if (rc != ZCG_OK) return rc;
-            std::vector<int32_t> status(m, ZCG_OK);
-            rc = zcg_store_read_chunks_device(ctx, &meta->array, m, S.cpaths.data(), S.ptrs.data(), status.data(),
-                                              io_threads ? io_threads : 1);
-            if (rc != ZCG_OK) return rc;
-            for (uint32_t i = 0; i < m; i++) {
-                if (status[i] == ZCG_ABSENT) continue;  // read_chunk -> Ok(None): a NULL entry
-                if (status[i] != ZCG_OK) return chunk_failed(ctx, what, P, G.keys[i], status[i]);
-                table[S.tidx[i]] = S.ptrs[i];
-            }
-        }
-        // device: [table entries][boxes nb][status nb][scratch of the _v kernels]
-        const uint64_t group_bytes = P.at[G.b1] - P.at[G.b0];
-        const size_t o_box = (entries * sizeof(void*) + 255) & ~(size_t)255;
-        const size_t o_st = (o_box + (size_t)nb * record_bytes(P) + 255) & ~(size_t)255;
-        const size_t o_scr = (o_st + (size_t)nb * sizeof(int32_t) + 255) & ~(size_t)255;
-        if ((e = meta_dev.alloc(o_scr + (P.varied ? zcg_regions_v_scratch_bytes(nb) : 0))) != hipSuccess)
-            return fail_hip(ctx, e, "read_boxes table");
-        if (host && (e = staging.alloc(group_bytes)) != hipSuccess)
-            return fail_hip(ctx, e, "read_boxes staging");
-        const std::vector<uint8_t> boxes = box_records(P, offsets, outs, staging.p, G.b0, nb, host);
-        uint8_t* db = (uint8_t*)meta_dev.p;
-        if (entries) e = hipMemcpyAsync(db, table.data(), entries * sizeof(void*), hipMemcpyHostToDevice, st.s);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(db + o_box, boxes.data(), boxes.size(), hipMemcpyHostToDevice, st.s);
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(st.s);  // the host vectors of an enqueued copy end with this scope
-            return fail_hip(ctx, e, "read_boxes H2D");
-        }
-        const int rc = regions_launch(ctx, P, lo, n, db, db + o_box, 0, nb, db + o_scr, (int32_t*)(db + o_st), st.s, 0);
-        if (rc != ZCG_OK) {
-            (void)hipStreamSynchronize(st.s);
-            return rc;
-        }
-        std::vector<int32_t> bst(nb, ZCG_OK);
-        e = hipMemcpyAsync(bst.data(), db + o_st, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, st.s);
-        std::vector<uint8_t> bounce;
-        if (e == hipSuccess && host) {
-            // one D2H per group: straight into the caller's boxes when they are
-            // consecutive in memory, else through a bounce buffer
-            bool dense = true;
-            for (uint32_t i = 1; i < nb && dense; i++)
-                dense = (uint8_t*)outs[G.b0 + i] == (uint8_t*)outs[G.b0] + (P.at[G.b0 + i] - P.at[G.b0]);
-            uint8_t* dst = (uint8_t*)outs[G.b0];
-            if (!dense) {
-                bounce.resize(group_bytes);
-                dst = bounce.data();
-            }
-            if (group_bytes) e = hipMemcpyAsync(dst, staging.p, group_bytes, hipMemcpyDeviceToHost, st.s);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(st.s);
-        else (void)hipStreamSynchronize(st.s);
-        if (e != hipSuccess) return fail_hip(ctx, e, "read_boxes assembly");
-        for (uint32_t i = 0; i < nb; i++)
-            if (bst[i] != ZCG_OK) {
-                ctx_set_error(ctx, "read_boxes: box " + std::to_string(G.b0 + i) + ": status " + std::to_string(bst[i]));
-                return bst[i];
-            }
-        if (!bounce.empty())
-            for (uint32_t i = 0; i < nb; i++)
-                if (P.box_bytes(G.b0 + i))
-                    memcpy(outs[G.b0 + i], bounce.data() + (P.at[G.b0 + i] - P.at[G.b0]), P.box_bytes(G.b0 + i));
-    }
-    return ZCG_OK;
-}
-
-// write_ndarray for the boxes in order (ndarray.rs:276-385).  Per group: the
-// slots of chunks whose first visiting box is partial are read (or, absent,
-// prefilled); the boxes are scattered wave by wave; every slot is encoded and
-// written.  host == true: ins are host buffers, dense in the chunk memory
-// order.  varied, box_steps: plan_boxes'.
-int write_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
-                const uint64_t* box_shape, const uint64_t* box_steps, const int64_t* in_strides, bool varied,
-                const uint64_t* offsets,
-                const void* const* ins, uint32_t n_boxes, uint64_t slot_budget_bytes, uint32_t io_threads,
-                bool host) {
-    const std::string what = "write_boxes";
-    Plan P;
-    // 1. before any file is read or written
-    const int prc = plan_boxes(ctx, what, meta, root, path, box_shape, box_steps, in_strides, varied, 0, offsets, ins,
-                               n_boxes, slot_budget_bytes, host, true, P);
-    if (prc != ZCG_OK) return prc;
-    if (P.nothing || P.at[n_boxes] == 0) return ZCG_OK;
-    const zcg_region& r = P.r;
-    const uint32_t nd = P.nd, es = P.es;
-    const uint64_t fillv = meta->has_fill_value ? meta->fill_value : 0;
-    const uint32_t threads = io_threads ? io_threads : 1;
-
-    (void)hipSetDevice(ctx_device(ctx));
-    Stream st;
-    hipError_t e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
-    if (e != hipSuccess) return fail_hip(ctx, e, "write_boxes stream");
-    std::vector<uint32_t> wave_of;
-
-    for (size_t g = 0; g < P.groups.size(); g++) {
-        const Group& G = P.groups[g];
-        const uint32_t nb = G.b1 - G.b0, m = (uint32_t)G.keys.size();
-        if (m == 0) continue;  // no box of the group visits a chunk: nothing to write
-        const uint64_t* lo = &P.glo[g * ZCG_MAX_DIMS];
-        const uint64_t* n = &P.gn[g * ZCG_MAX_DIMS];
-        const uint64_t entries = P.gentries[g];
-        GroupSlots S;
-        DevMem meta_dev, staging;
-        int rc = group_slots(ctx, what, meta, root, path, P, g, S);
-        if (rc != ZCG_OK) return rc;
-
-        // 2. the existing chunks under a partial first box; absent ones start as fill value
-        std::vector<void*> absent;
-        {
             std::vector<uint32_t> idx;
             std::vector<const char*> rpaths;
             std::vector<void*> rptrs;
-            for (uint32_t i = 0; i < m; i++)
-                if (G.read_first[i]) {
-                    idx.push_back(i);
-                    rpaths.push_back(S.cpaths[i]);
-                    rptrs.push_back(S.ptrs[i]);
-                }
+            for (uint32_t i = 0; i < m; i++) {
+                table[S.tidx[i]] = S.ptrs[i];
+                if (write && !G.read_first[i]) continue;
+                idx.push_back(i);
+                rpaths.push_back(S.cpaths[i]);
+                rptrs.push_back(S.ptrs[i]);
+            }
+            std::vector<int32_t> status(idx.size(), ZCG_OK);
             if (!idx.empty()) {
-                std::vector<int32_t> status(idx.size(), ZCG_OK);
                 rc = zcg_store_read_chunks_device(ctx, &meta->array, (uint32_t)idx.size(), rpaths.data(), rptrs.data(),
                                                   status.data(), threads);
                 if (rc != ZCG_OK) return rc;
-                for (size_t k = 0; k < idx.size(); k++) {
-                    if (status[k] == ZCG_ABSENT) absent.push_back(rptrs[k]);  // ndarray.rs:351-364
-                    else if (status[k] != ZCG_OK) return chunk_failed(ctx, what, P, G.keys[idx[k]], status[k]);
+            }
+            for (size_t k = 0; k < idx.size(); k++) {
+                if (status[k] == ZCG_ABSENT) {
+                    if (write) absent.push_back(rptrs[k]);
+                    else table[S.tidx[idx[k]]] = nullptr;
+                } else if (status[k] != ZCG_OK) {
+                    return chunk_failed(ctx, what, P, G.keys[idx[k]], status[k]);
                 }
             }
         }
 
-        // 3. device: [table entries][boxes nb][status nb][absent slots][scratch of the _v kernels]; every
-        // visited chunk has a slot
-        std::vector<void*> table(entries, nullptr);
-        for (uint32_t i = 0; i < m; i++) table[S.tidx[i]] = S.ptrs[i];
-        const uint64_t group_bytes = P.at[G.b1] - P.at[G.b0];
-        const size_t o_box = (entries * sizeof(void*) + 255) & ~(size_t)255;
-        const size_t o_st = (o_box + (size_t)nb * record_bytes(P) + 255) & ~(size_t)255;
-        const size_t o_abs = (o_st + (size_t)nb * sizeof(int32_t) + 255) & ~(size_t)255;
-        const size_t o_scr = (o_abs + absent.size() * sizeof(void*) + 255) & ~(size_t)255;
-        if ((e = meta_dev.alloc(o_scr + (P.varied ? zcg_regions_v_scratch_bytes(nb) : 0))) != hipSuccess)
-            return fail_hip(ctx, e, "write_boxes table");
-        if (host && (e = staging.alloc(group_bytes)) != hipSuccess)
-            return fail_hip(ctx, e, "write_boxes staging");
-        const std::vector<uint8_t> boxes = box_records(P, offsets, ins, staging.p, G.b0, nb, host);
-        uint8_t* db = (uint8_t*)meta_dev.p;
-        std::vector<uint8_t> bounce;
-        e = hipMemcpyAsync(db, table.data(), entries * sizeof(void*), hipMemcpyHostToDevice, st.s);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(db + o_box, boxes.data(), boxes.size(), hipMemcpyHostToDevice, st.s);
+        // 2. device: [table entries][absent slots][the payload's part]
+        const size_t o_abs = up256(entries * sizeof(void*));
+        const size_t o_pay = up256(o_abs + absent.size() * sizeof(void*));
+        if ((e = block.alloc(o_pay + X.device_bytes(G))) != hipSuccess) return fail_hip(ctx, e, what + " table");
+        uint8_t* db = (uint8_t*)block.p;
+        if (entries) e = hipMemcpyAsync(db, table.data(), entries * sizeof(void*), hipMemcpyHostToDevice, st.s);
         if (e == hipSuccess && !absent.empty())
             e = hipMemcpyAsync(db + o_abs, absent.data(), absent.size() * sizeof(void*), hipMemcpyHostToDevice, st.s);
-        if (e == hipSuccess && host) {
-            // one H2D per group: straight from the caller's boxes when they are
-            // consecutive in memory, else through a bounce buffer
-            bool dense = true;
-            for (uint32_t i = 1; i < nb && dense; i++)
-                dense = (const uint8_t*)ins[G.b0 + i] == (const uint8_t*)ins[G.b0] + (P.at[G.b0 + i] - P.at[G.b0]);
-            const uint8_t* src = (const uint8_t*)ins[G.b0];
-            if (!dense) {
-                bounce.resize(group_bytes);
-                for (uint32_t i = 0; i < nb; i++)
-                    if (P.box_bytes(G.b0 + i))
-                        memcpy(bounce.data() + (P.at[G.b0 + i] - P.at[G.b0]), ins[G.b0 + i], P.box_bytes(G.b0 + i));
-                src = bounce.data();
-            }
-            if (group_bytes) e = hipMemcpyAsync(staging.p, src, group_bytes, hipMemcpyHostToDevice, st.s);
-        }
-        if (e == hipSuccess)
-            e = launch_slot_fill((void* const*)(db + o_abs), (uint32_t)absent.size(), P.D, es, fillv, st.s);
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(st.s);  // the host vectors of an enqueued copy end with this scope
-            return fail_hip(ctx, e, "write_boxes H2D");
-        }
+        if (e == hipSuccess) e = X.upload(G, db + o_pay, st.s);
+        if (e == hipSuccess && write)
+            e = launch_slot_fill((void* const*)(db + o_abs), (uint32_t)absent.size(), P.D, P.es, fillv, st.s);
 
-        // 4. the scatter, wave by wave: a later box wins what it shares with an earlier one
-        wave_of.resize(nb);
-        if (P.steps)
-            zcg_regions_s_waves(&r, offsets + (size_t)G.b0 * nd, box_shape + (size_t)G.b0 * nd,
-                                box_steps + (size_t)G.b0 * nd, nb, wave_of.data());
-        else if (P.varied)
-            zcg_regions_v_waves(&r, offsets + (size_t)G.b0 * nd, box_shape + (size_t)G.b0 * nd, nb, wave_of.data());
-        else
-            zcg_regions_waves(&r, offsets + (size_t)G.b0 * nd, nb, wave_of.data());
-        for (uint32_t b0 = 0; b0 < nb;) {
-            uint32_t b1 = b0 + 1;
-            while (b1 < nb && wave_of[b1] == wave_of[b0]) b1++;
-            rc = regions_launch(ctx, P, lo, n, db, db + o_box, b0, b1 - b0, db + o_scr, (int32_t*)(db + o_st), st.s, 1);
-            if (rc != ZCG_OK) {
-                (void)hipStreamSynchronize(st.s);
-                return rc;
-            }
-            b0 = b1;
-        }
-        std::vector<int32_t> bst(nb, ZCG_OK);
-        e = hipMemcpyAsync(bst.data(), db + o_st, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, st.s);
-        if (e == hipSuccess) e = hipStreamSynchronize(st.s);
-        else (void)hipStreamSynchronize(st.s);
-        if (e != hipSuccess) return fail_hip(ctx, e, "write_boxes scatter");
-        for (uint32_t i = 0; i < nb; i++)
-            if (bst[i] != ZCG_OK) {
-                ctx_set_error(ctx, "write_boxes: box " + std::to_string(G.b0 + i) + ": status " + std::to_string(bst[i]));
-                return bst[i];
-            }
+        // 3. the payload's launches, and the group's one synchronisation: whatever went wrong after
+        // a copy was enqueued, the host vectors of this scope and of X outlive the copy
+        int rc = e != hipSuccess ? fail_hip(ctx, e, what + " H2D") : X.launch(ctx, G, lo, n, db, st.s);
+        e = hipStreamSynchronize(st.s);
+        if (rc == ZCG_OK && e != hipSuccess) rc = fail_hip(ctx, e, what + (write ? " scatter" : " assembly"));
+        if (rc == ZCG_OK) rc = X.finish(ctx, G);
+        if (rc != ZCG_OK) return rc;
+        if (!write) continue;
 
-        // 5. encode and write every chunk of the group, once
+        // 4. write: encode and write every chunk of the group, once
         std::vector<int32_t> wst(m, ZCG_OK);
         rc = zcg_store_write_chunks_device(ctx, &meta->array, m, S.cpaths.data(), (const void* const*)S.ptrs.data(),
                                            wst.data(), threads);
@@ -728,171 +620,146 @@ int write_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, cons
     return ZCG_OK;
 }
 
-// a box's cells along one dimension: first and last cell index
-struct CellRange {
-    uint64_t lo, hi;
+// The boxes of a group (the header comment has the device layout).  bufs[b]:
+// box b's host buffer, dense in the chunk memory order (host), or the base of
+// its device view; a read writes through it.
+struct BoxPayload {
+    const Plan& P;
+    const std::string& what;
+    const uint64_t* offsets;
+    void* const* bufs;
+    bool host, write;
+    DevMem staging;  // host: the group's boxes back to back
+    std::vector<uint8_t> recs, bounce;
+    bool copy_back = false;  // a read went through `bounce`: finish() hands the boxes out
+    std::vector<int32_t> bst;
+    std::vector<uint32_t> wave_of;
+    uint8_t* d = nullptr;  // the group's records; status and scratch follow
+    size_t o_st = 0, o_scr = 0;
+
+    uint64_t group_bytes(const Group& G) const { return P.at[G.b1] - P.at[G.b0]; }
+    uint8_t* bounce_at(const Group& G, uint32_t b) { return bounce.data() + (P.at[b] - P.at[G.b0]); }
+    // are the group's host buffers consecutive in memory?  Then one copy serves them as they are
+    bool consecutive(const Group& G) const {
+        for (uint32_t b = G.b0 + 1; b < G.b1; b++)
+            if ((uint8_t*)bufs[b] != (uint8_t*)bufs[G.b0] + (P.at[b] - P.at[G.b0])) return false;
+        return true;
+    }
+
+    size_t device_bytes(const Group& G) {
+        const uint32_t nb = G.b1 - G.b0;
+        o_st = up256((size_t)nb * record_bytes(P));
+        o_scr = up256(o_st + (size_t)nb * sizeof(int32_t));
+        return o_scr + (P.varied ? zcg_regions_v_scratch_bytes(nb) : 0);
+    }
+
+    hipError_t upload(const Group& G, uint8_t* d_part, hipStream_t s) {
+        d = d_part;
+        hipError_t e = host ? staging.alloc(group_bytes(G)) : hipSuccess;
+        if (e != hipSuccess) return e;
+        recs = box_records(P, offsets, bufs, staging.p, G.b0, G.b1 - G.b0, host);
+        e = hipMemcpyAsync(d, recs.data(), recs.size(), hipMemcpyHostToDevice, s);
+        if (e != hipSuccess || !host || !write || !group_bytes(G)) return e;
+        const uint8_t* src = (const uint8_t*)bufs[G.b0];
+        if (!consecutive(G)) {
+            bounce.resize(group_bytes(G));
+            for (uint32_t b = G.b0; b < G.b1; b++)
+                if (P.box_bytes(b)) memcpy(bounce_at(G, b), bufs[b], P.box_bytes(b));
+            src = bounce.data();
+        }
+        return hipMemcpyAsync(staging.p, src, group_bytes(G), hipMemcpyHostToDevice, s);
+    }
+
+    int launch(zcg_ctx* ctx, const Group& G, const uint64_t* lo, const uint64_t* n, void* d_table, hipStream_t s) {
+        const uint32_t nb = G.b1 - G.b0, nd = P.nd;
+        int32_t* d_st = (int32_t*)(d + o_st);
+        if (!write) {
+            const int rc = regions_launch(ctx, P, lo, n, d_table, d, 0, nb, d + o_scr, d_st, s, 0);
+            if (rc != ZCG_OK) return rc;
+        } else {
+            // wave by wave: a later box wins what it shares with an earlier one
+            const uint64_t* off = offsets + (size_t)G.b0 * nd;
+            wave_of.resize(nb);
+            if (P.steps)
+                zcg_regions_s_waves(&P.r, off, P.shapes + (size_t)G.b0 * nd, P.steps + (size_t)G.b0 * nd, nb,
+                                    wave_of.data());
+            else if (P.varied)
+                zcg_regions_v_waves(&P.r, off, P.shapes + (size_t)G.b0 * nd, nb, wave_of.data());
+            else
+                zcg_regions_waves(&P.r, off, nb, wave_of.data());
+            for (uint32_t b0 = 0; b0 < nb;) {
+                uint32_t b1 = b0 + 1;
+                while (b1 < nb && wave_of[b1] == wave_of[b0]) b1++;
+                const int rc = regions_launch(ctx, P, lo, n, d_table, d, b0, b1 - b0, d + o_scr, d_st, s, 1);
+                if (rc != ZCG_OK) return rc;
+                b0 = b1;
+            }
+        }
+        bst.assign(nb, ZCG_OK);
+        hipError_t e = hipMemcpyAsync(bst.data(), d_st, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+        copy_back = false;
+        if (e == hipSuccess && host && !write && group_bytes(G)) {
+            uint8_t* dst = (uint8_t*)bufs[G.b0];
+            if (!consecutive(G)) {
+                bounce.resize(group_bytes(G));
+                dst = bounce.data();
+                copy_back = true;
+            }
+            e = hipMemcpyAsync(dst, staging.p, group_bytes(G), hipMemcpyDeviceToHost, s);
+        }
+        return e == hipSuccess ? ZCG_OK : fail_hip(ctx, e, what + (write ? " scatter" : " assembly"));
+    }
+
+    int finish(zcg_ctx* ctx, const Group& G) {
+        staging.release();
+        for (uint32_t b = G.b0; b < G.b1; b++)
+            if (bst[b - G.b0] != ZCG_OK) {
+                ctx_set_error(ctx, what + ": box " + std::to_string(b) + ": status " + std::to_string(bst[b - G.b0]));
+                return bst[b - G.b0];
+            }
+        if (copy_back)  // a read whose buffers are not consecutive
+            for (uint32_t b = G.b0; b < G.b1; b++)
+                if (P.box_bytes(b)) memcpy(bufs[b], bounce_at(G, b), P.box_bytes(b));
+        return ZCG_OK;
+    }
 };
 
-typedef unsigned __int128 u128;
-
-// Do the progressions {o1 + i*s1, i < c1} and {o2 + j*s2, j < c2} share an
-// index?  c1, c2 >= 1, s1, s2 >= 1, and both last samples are below 2^64.
-// Exact, by the congruence x = o1 (mod s1), x = o2 (mod s2): solvable iff
-// gcd(s1, s2) divides o2 - o1; the least solution at or above max(o1, o2) must
-// not pass either last sample.  No loop over samples.
-bool progressions_meet(uint64_t o1, uint64_t c1, uint64_t s1, uint64_t o2, uint64_t c2, uint64_t s2) {
-    if (c1 < 2) s1 = 1;  // the step of a lone sample is irrelevant
-    if (c2 < 2) s2 = 1;
-    if (o1 > o2) { std::swap(o1, o2); std::swap(c1, c2); std::swap(s1, s2); }
-    const u128 last1 = (u128)o1 + (u128)(c1 - 1) * s1, last2 = (u128)o2 + (u128)(c2 - 1) * s2;
-    const u128 last = std::min(last1, last2);
-    if (o2 > last) return false;
-    uint64_t g = s1, h = s2;
-    while (h) { const uint64_t t = g % h; g = h; h = t; }
-    const uint64_t diff = o2 - o1;
-    if (diff % g) return false;
-    // x = o1 + s1*k with (s1/g)*k = diff/g (mod m), m = s2/g: k = (diff/g) * inverse of s1/g mod m
-    const uint64_t m = s2 / g, a = (s1 / g) % m;
-    uint64_t k = 0;
-    if (m > 1) {
-        __int128 t0 = 0, t1 = 1;  // extended Euclid: t1 * a = r1 (mod m)
-        uint64_t r0 = m, r1 = a;
-        while (r1 > 1) {
-            const uint64_t q = r0 / r1, r2 = r0 - q * r1;
-            const __int128 t2 = t0 - (__int128)q * t1;
-            r0 = r1; r1 = r2; t0 = t1; t1 = t2;
-        }
-        const uint64_t inv = (uint64_t)(((t1 % (__int128)m) + m) % m);  // gcd(a, m) = 1, so r1 ends at 1
-        k = (uint64_t)((u128)((diff / g) % m) * inv % m);
-    }
-    u128 x = (u128)o1 + (u128)s1 * k;  // the least solution at or above o1; the next ones are lcm apart
-    if (x < o2) {
-        const u128 lcm = (u128)(s1 / g) * s2, need = (u128)o2 - x;
-        if (lcm > last) return false;  // the next solution is past every sample
-        x += (need + lcm - 1) / lcm * lcm;
-    }
-    return x <= last;
+// write == false: read_ndarray for every box; host == true: bufs are host
+// buffers, each box dense in the chunk memory order with fill, else device
+// views with the caller's strides.  write == true: write_ndarray for the boxes
+// in order (ndarray.rs:276-385).  varied, box_steps: plan_boxes'.
+int run_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+              const uint64_t* box_shape, const uint64_t* box_steps, const int64_t* strides, bool varied,
+              uint32_t fill_missing, const uint64_t* offsets, void* const* bufs, uint32_t n_boxes,
+              uint64_t slot_budget_bytes, uint32_t io_threads, bool host, bool write) {
+    const std::string what = write ? "write_boxes" : "read_boxes";
+    Plan P;
+    // before any file is read or written
+    const int prc = plan_boxes(ctx, what, meta, root, path, box_shape, box_steps, strides, varied, fill_missing,
+                               offsets, bufs, n_boxes, slot_budget_bytes, host, write, P);
+    if (prc != ZCG_OK) return prc;
+    if (P.nothing || P.at[n_boxes] == 0) return ZCG_OK;
+    BoxPayload X{P, what, offsets, bufs, host, write};
+    return run_groups(ctx, what, meta, root, path, P, write, io_threads, X);
 }
 
-// zcg_regions_waves, zcg_regions_v_waves and zcg_regions_s_waves: box b's
-// shape is shapes + b * sstep (sstep 0: one shape for all); steps (n_boxes *
-// ndim, or NULL): shapes are sample counts and two boxes intersect when their
-// progressions do.  Cells and hashing go by the hulls.
-uint32_t regions_waves(const zcg_region* r, const uint64_t* offsets, const uint64_t* shapes, size_t sstep,
-                       const uint64_t* steps, uint32_t n_boxes, uint32_t* wave_of) {
-    if (!r || !offsets || !shapes || !wave_of || n_boxes == 0) return 0;
-    const uint32_t nd = r->ndim;
-    if (nd < 1 || nd > ZCG_MAX_DIMS) return 0;
-    // strided: the hulls' extents (saturating) stand in for the shapes below;
-    // a box with a step of 0 gets a zero extent and intersects nothing
-    const uint64_t* counts = shapes;
-    std::vector<uint64_t> hulls;
-    std::vector<uint8_t> over;  // per box: a hull end passes 2^64
-    if (steps) {
-        hulls.assign((size_t)n_boxes * nd, 0);
-        over.assign(n_boxes, 0);
-        for (uint32_t b = 0; b < n_boxes; b++) {
-            bool stepped = true;
-            for (uint32_t d = 0; d < nd; d++) stepped &= steps[(size_t)b * nd + d] != 0;
-            for (uint32_t d = 0; stepped && d < nd; d++) {
-                const size_t i = (size_t)b * nd + d;
-                const uint64_t c = counts[i];
-                const u128 e = c ? (u128)(c - 1) * (c > 1 ? steps[i] : 1) + 1 : 0;
-                hulls[i] = e > ~0ull ? ~0ull : (uint64_t)e;
-                if (e + offsets[i] > ~0ull) over[b] = 1;
-            }
-        }
-        shapes = hulls.data();
-        sstep = nd;
-    }
-    // Cells: per dimension the smallest multiple of the chunk extent that holds
-    // the largest box extent (r->bbox_shape, unless a box exceeds it), so a box
-    // lies in at most two cells per dimension and two boxes that intersect
-    // share a cell.  A box is compared with the boxes of the current wave that
-    // are registered in one of its cells.
-    uint64_t cell[ZCG_MAX_DIMS];
-    for (uint32_t d = 0; d < nd; d++) {
-        uint64_t bs = steps ? 0 : sstep ? r->bbox_shape[d] : shapes[d];
-        for (uint32_t b = 0; sstep && b < n_boxes; b++) bs = std::max(bs, shapes[(size_t)b * sstep + d]);
-        const uint64_t cs = r->chunk_shape[d] ? r->chunk_shape[d] : 1;
-        const uint64_t k = std::max<uint64_t>(bs / cs + (bs % cs ? 1 : 0), 1);
-        cell[d] = k > (~0ull) / cs ? ~0ull : k * cs;
-    }
-    auto end_of = [&](uint32_t b, uint32_t d) {
-        const uint64_t o = offsets[(size_t)b * nd + d], e = o + shapes[(size_t)b * sstep + d];
-        return e < o ? ~0ull : e;  // saturating
-    };
-    std::unordered_map<uint64_t, std::vector<uint32_t>> cells;  // hash of the cell position -> boxes
-    uint32_t wave = 0;
-    for (uint32_t b = 0; b < n_boxes; b++) {
-        const uint64_t* ob = offsets + (size_t)b * nd;
-        CellRange cr[ZCG_MAX_DIMS];
-        bool has = true;  // false: the saturated extent is empty, the box intersects nothing
-        uint32_t ncell = 1;
-        for (uint32_t d = 0; d < nd; d++) {
-            const uint64_t e = end_of(b, d);
-            if (e <= ob[d]) { has = false; break; }
-            cr[d] = CellRange{ob[d] / cell[d], (e - 1) / cell[d]};
-            ncell *= (uint32_t)(cr[d].hi - cr[d].lo + 1);
-        }
-        if (!has) {
-            wave_of[b] = wave;
-            continue;
-        }
-        uint64_t keys[1u << ZCG_MAX_DIMS];
-        for (uint32_t c = 0; c < ncell; c++) {
-            uint64_t h = 0x9E3779B97F4A7C15ull;
-            uint32_t rem = c;
-            for (uint32_t d = 0; d < nd; d++) {
-                const uint32_t w = (uint32_t)(cr[d].hi - cr[d].lo + 1);
-                h = (h ^ (cr[d].lo + rem % w)) * 0xFF51AFD7ED558CCDull;
-                h ^= h >> 32;
-                rem /= w;
-            }
-            keys[c] = h;
-        }
-        bool hit = false;
-        for (uint32_t c = 0; c < ncell && !hit; c++) {
-            auto it = cells.find(keys[c]);
-            if (it == cells.end()) continue;
-            for (uint32_t a : it->second) {
-                const uint64_t* oa = offsets + (size_t)a * nd;
-                bool meet = true;
-                const bool exact = steps && !over[a] && !over[b];  // else the (saturated) hulls' intervals
-                for (uint32_t d = 0; d < nd && meet; d++)
-                    meet = exact ? progressions_meet(oa[d], counts[(size_t)a * nd + d], steps[(size_t)a * nd + d],
-                                                     ob[d], counts[(size_t)b * nd + d], steps[(size_t)b * nd + d])
-                                 : std::max(oa[d], ob[d]) < std::min(end_of(a, d), end_of(b, d));
-                if (meet) { hit = true; break; }
-            }
-        }
-        if (hit) {
-            wave++;
-            cells.clear();
-        }
-        wave_of[b] = wave;
-        for (uint32_t c = 0; c < ncell; c++) cells[keys[c]].push_back(b);
-    }
-    return wave + 1;
+int read_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+               const uint64_t* box_shape, const uint64_t* box_steps, const int64_t* out_strides, bool varied,
+               uint32_t fill_missing, const uint64_t* offsets, void* const* outs, uint32_t n_boxes,
+               uint64_t slot_budget_bytes, uint32_t io_threads, bool host) {
+    return run_boxes(ctx, meta, root, path, box_shape, box_steps, out_strides, varied, fill_missing, offsets, outs,
+                     n_boxes, slot_budget_bytes, io_threads, host, false);
+}
+
+int write_boxes(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                const uint64_t* box_shape, const uint64_t* box_steps, const int64_t* in_strides, bool varied,
+                const uint64_t* offsets, const void* const* ins, uint32_t n_boxes, uint64_t slot_budget_bytes,
+                uint32_t io_threads, bool host) {
+    return run_boxes(ctx, meta, root, path, box_shape, box_steps, in_strides, varied, 0, offsets, (void* const*)ins,
+                     n_boxes, slot_budget_bytes, io_threads, host, true);
 }
 
 }  // namespace
-
-extern "C" uint32_t zcg_regions_waves(const zcg_region* r, const uint64_t* offsets, uint32_t n_boxes,
-                                      uint32_t* wave_of) {
-    return regions_waves(r, offsets, r ? r->bbox_shape : nullptr, 0, nullptr, n_boxes, wave_of);
-}
-
-extern "C" uint32_t zcg_regions_v_waves(const zcg_region* r, const uint64_t* offsets, const uint64_t* shapes,
-                                        uint32_t n_boxes, uint32_t* wave_of) {
-    return regions_waves(r, offsets, shapes, r ? r->ndim : 0, nullptr, n_boxes, wave_of);
-}
-
-extern "C" uint32_t zcg_regions_s_waves(const zcg_region* r, const uint64_t* offsets, const uint64_t* shapes,
-                                        const uint64_t* steps, uint32_t n_boxes, uint32_t* wave_of) {
-    if (!steps) return 0;
-    return regions_waves(r, offsets, shapes, r ? r->ndim : 0, steps, n_boxes, wave_of);
-}
 
 extern "C" int zcg_store_write_boxes_device(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root,
                                             const char* path, const uint64_t* box_shape, const int64_t* in_strides,
@@ -1037,27 +904,6 @@ extern "C" int zcg_store_write_boxes_s(zcg_ctx* ctx, const zcg_array_meta* meta,
 // chunk and neighbouring lines.  The kernel (zcg_region_p.hip) gets the sorted
 // coordinates with each point's original index, so a device caller's values
 // stay in the caller's order; host values are permuted on the host.
-extern "C" uint64_t zcg_points_last(const uint64_t* coords, uint64_t n_points, uint32_t ndim, uint8_t* keep) {
-    if (!coords || !keep || ndim < 1 || ndim > ZCG_MAX_DIMS) return 0;
-    std::vector<uint64_t> idx(n_points);
-    for (uint64_t i = 0; i < n_points; i++) idx[i] = i;
-    // equal coordinates next to each other, the latest point last
-    std::sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) {
-        const uint64_t *ca = coords + a * ndim, *cb = coords + b * ndim;
-        for (uint32_t d = 0; d < ndim; d++)
-            if (ca[d] != cb[d]) return ca[d] < cb[d];
-        return a < b;
-    });
-    uint64_t kept = 0;
-    for (uint64_t i = 0; i < n_points; i++) {
-        const bool last = i + 1 == n_points ||
-                          memcmp(coords + idx[i] * ndim, coords + idx[i + 1] * ndim, ndim * sizeof(uint64_t)) != 0;
-        keep[idx[i]] = last ? 1 : 0;
-        kept += last;
-    }
-    return kept;
-}
-
 namespace zcg {
 int points_call(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
                 const void* const* d_chunk_table, const uint64_t* d_coords, const uint64_t* d_order,
@@ -1079,58 +925,21 @@ struct SortedPoint {
 int plan_points(zcg_ctx* ctx, const std::string& what, const zcg_array_meta* meta, const char* root, const char* path,
                 uint32_t fill_missing, const uint64_t* coords, const void* buf, uint64_t n_points,
                 const uint8_t* keep, uint64_t slot_budget_bytes, Plan& P, std::vector<SortedPoint>& pts) {
-    if (!ctx || !meta || !root || !path) return ZCG_ERR_INVALID_INPUT;
-    if (n_points && (!coords || !buf)) return ZCG_ERR_INVALID_INPUT;
-    auto say = [&](const std::string& e) { ctx_set_error(ctx, e); };
-    const int mrc = meta_args_status(what, meta, say);
-    if (mrc != ZCG_OK) return mrc;
-    const uint32_t nd = meta->ndim;
-    const uint32_t es = meta->array.dtype.elem_size;
-    if (es != 1 && es != 2 && es != 4 && es != 8) return ZCG_ERR_INVALID_INPUT;
-    P.nd = nd;
-    P.es = es;
-    if (n_points == 0) {
-        P.nothing = true;
-        return ZCG_OK;
-    }
-    if (n_points >= (1ull << 32)) {  // Group::b0 / b1
-        ctx_set_error(ctx, what + ": more than 2^32 points in one call");
-        return ZCG_ERR_UNSUPPORTED;
-    }
+    const int hrc = plan_head(ctx, what, meta, root, path, coords, buf, n_points, "points", fill_missing, P);
+    if (hrc != ZCG_OK || P.nothing) return hrc;
+    const uint32_t nd = P.nd;
     zcg_region& r = P.r;
-    memset(&r, 0, sizeof r);
-    r.ndim = nd;
-    r.elem_size = es;
-    r.chunk_order = meta->chunk_order;
-    r.fill_missing = fill_missing ? 1u : 0u;
-    r.fill_value = meta->has_fill_value ? meta->fill_value : 0;
-    uint64_t extent[ZCG_MAX_DIMS], cstr[ZCG_MAX_DIMS];
-    for (uint32_t d = 0; d < nd; d++) {
-        if (meta->chunk_shape[d] == 0) return ZCG_ERR_INVALID_INPUT;
-        r.array_shape[d] = meta->shape[d];
-        r.chunk_shape[d] = meta->chunk_shape[d];
+    const int grc = plan_head_grid(ctx, what, slot_budget_bytes, P);
+    if (grc != ZCG_OK) return grc;
+    const uint64_t* extent = P.extent;
+    uint64_t cstr[ZCG_MAX_DIMS], c = 1;  // element strides inside a chunk, in the chunk memory order
+    for (uint32_t k = 0; k < nd; k++) {
+        const uint32_t d = meta->chunk_order == 1 ? k : nd - 1 - k;
         r.bbox_shape[d] = 1;
-        extent[d] = u64_ceil_div(meta->shape[d], meta->chunk_shape[d]);
+        cstr[d] = c;
+        c *= meta->chunk_shape[d];
     }
-    {
-        uint64_t g = 1, c = 1;
-        for (int d = (int)nd - 1; d >= 0; d--) {
-            P.gstr[d] = g;
-            if (extent[d] && g > (~0ull) / extent[d]) {
-                ctx_set_error(ctx, what + ": the array's chunk grid exceeds 2^64 chunks");
-                return ZCG_ERR_UNSUPPORTED;
-            }
-            g *= extent[d];
-        }
-        for (uint32_t k = 0; k < nd; k++) {
-            const uint32_t d = meta->chunk_order == 1 ? k : nd - 1 - k;
-            cstr[d] = c;
-            c *= meta->chunk_shape[d];
-        }
-    }
-    const uint64_t D = P.D = meta->array.chunk_num_elements * (uint64_t)es;
-    const uint64_t budget = slot_budget_bytes ? slot_budget_bytes : BOXES_DEFAULT_BUDGET;
-    const uint64_t max_chunks = std::max<uint64_t>(budget / std::max<uint64_t>(D, 1), 1);
+    const uint64_t max_chunks = std::max<uint64_t>(P.budget / std::max<uint64_t>(P.D, 1), 1);
 
     // every point's chunk: in bounds (the reference panics at storage.rs:217)
     pts.clear();
@@ -1210,222 +1019,104 @@ int plan_points(zcg_ctx* ctx, const std::string& what, const zcg_array_meta* met
     return ZCG_OK;
 }
 
-// The device side of one group of sorted points: [table entries][coordinates
-// np * nd][original indices np][the word for points outside the table].
-struct PointsDev {
-    DevMem mem;
-    size_t o_co = 0, o_ord = 0, o_fo = 0;
-    std::vector<uint64_t> host;  // coordinates, then indices
+// The sorted points of a group (the header comment has the device layout).
+// vals: the caller's values in the caller's order, host or device; a read
+// writes them.
+struct PointsPayload {
+    const Plan& P;
+    const std::string& what;
+    const std::vector<SortedPoint>& pts;
+    const uint64_t* coords;
+    void* vals;
+    bool host, write;
+    DevMem staging;  // host: the group's values in sorted order
+    std::vector<uint64_t> recs;  // coordinates, then indices
+    std::vector<uint8_t> bounce;
+    uint64_t first_outside = ~0ull;
+    uint8_t* d = nullptr;  // the group's coordinates; indices and the first-outside word follow
+    size_t o_ord = 0, o_fo = 0;
+
+    size_t device_bytes(const Group& G) {
+        const size_t np = G.b1 - G.b0;
+        o_ord = np * P.nd * sizeof(uint64_t);
+        o_fo = o_ord + np * sizeof(uint64_t);
+        return o_fo + sizeof(uint64_t);
+    }
+
+    hipError_t upload(const Group& G, uint8_t* d_part, hipStream_t s) {
+        const uint32_t nd = P.nd, es = P.es;
+        const size_t np = G.b1 - G.b0;
+        d = d_part;
+        hipError_t e = host ? staging.alloc(np * es) : hipSuccess;
+        if (e != hipSuccess) return e;
+        recs.resize(np * nd + np);
+        for (size_t i = 0; i < np; i++) {
+            const SortedPoint& sp = pts[G.b0 + i];
+            memcpy(&recs[i * nd], coords + sp.i * nd, nd * sizeof(uint64_t));
+            recs[np * nd + i] = sp.i;
+        }
+        e = hipMemcpyAsync(d, recs.data(), recs.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s);
+        if (e != hipSuccess || !host || !write) return e;
+        bounce.resize(np * es);
+        for (size_t i = 0; i < np; i++)
+            memcpy(bounce.data() + i * es, (const uint8_t*)vals + pts[G.b0 + i].i * es, es);
+        return hipMemcpyAsync(staging.p, bounce.data(), np * es, hipMemcpyHostToDevice, s);
+    }
+
+    // one launch: no two points of a write share an element (zcg_points_last).  host: the group's
+    // values in sorted order, permuted on the host; device: straight from or to the caller's order
+    int launch(zcg_ctx* ctx, const Group& G, const uint64_t* lo, const uint64_t* n, void* d_table, hipStream_t s) {
+        const size_t np = G.b1 - G.b0;
+        const int rc = points_call(ctx, &P.r, lo, n, (const void* const*)d_table, (const uint64_t*)d,
+                                   host ? nullptr : (const uint64_t*)(d + o_ord), np, host ? staging.p : vals,
+                                   (uint64_t*)(d + o_fo), (void*)s, write ? 1 : 0);
+        if (rc != ZCG_OK) return rc;
+        first_outside = ~0ull;
+        hipError_t e = hipMemcpyAsync(&first_outside, d + o_fo, sizeof first_outside, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && host && !write) {
+            bounce.resize(np * P.es);
+            e = hipMemcpyAsync(bounce.data(), staging.p, np * P.es, hipMemcpyDeviceToHost, s);
+        }
+        return e == hipSuccess ? ZCG_OK : fail_hip(ctx, e, what + (write ? " scatter" : " assembly"));
+    }
+
+    int finish(zcg_ctx* ctx, const Group& G) {
+        staging.release();
+        if (first_outside != ~0ull) {
+            ctx_set_error(ctx, what + ": sorted point " + std::to_string(first_outside) +
+                                   " fell outside its group's table");
+            return ZCG_ERR_RUNTIME;
+        }
+        if (host && !write)
+            for (size_t i = 0; i < (size_t)(G.b1 - G.b0); i++)
+                memcpy((uint8_t*)vals + pts[G.b0 + i].i * P.es, bounce.data() + i * P.es, P.es);
+        return ZCG_OK;
+    }
 };
 
-hipError_t points_upload(const Plan& P, const Group& G, const std::vector<SortedPoint>& pts, const uint64_t* coords,
-                         const void* const* table, uint64_t entries, PointsDev& X, hipStream_t s) {
-    const uint32_t nd = P.nd;
-    const size_t np = G.b1 - G.b0;
-    X.o_co = (entries * sizeof(void*) + 255) & ~(size_t)255;
-    X.o_ord = X.o_co + np * nd * sizeof(uint64_t);
-    X.o_fo = X.o_ord + np * sizeof(uint64_t);
-    hipError_t e = X.mem.alloc(X.o_fo + sizeof(uint64_t));
-    if (e != hipSuccess) return e;
-    X.host.resize(np * nd + np);
-    for (size_t i = 0; i < np; i++) {
-        const SortedPoint& sp = pts[G.b0 + i];
-        memcpy(&X.host[i * nd], coords + sp.i * nd, nd * sizeof(uint64_t));
-        X.host[np * nd + i] = sp.i;
-    }
-    uint8_t* db = (uint8_t*)X.mem.p;
-    if (entries) e = hipMemcpyAsync(db, table, entries * sizeof(void*), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(db + X.o_co, X.host.data(), X.host.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s);
-    return e;
-}
-
-int points_outside(zcg_ctx* ctx, const std::string& what, uint64_t first_outside) {
-    if (first_outside == ~0ull) return ZCG_OK;
-    ctx_set_error(ctx, what + ": sorted point " + std::to_string(first_outside) + " fell outside its group's table");
-    return ZCG_ERR_RUNTIME;
-}
-
-int read_points(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path, const uint64_t* coords,
-                uint64_t n_points, uint32_t fill_missing, void* out, uint64_t slot_budget_bytes, uint32_t io_threads,
-                bool host) {
-    const std::string what = "read_points";
+// read_ndarray (write == false) or write_ndarray (true) for the 1-element boxes
+// of point 0, 1, ... in order.  Of two points of a write with one coordinate
+// the later one counts (zcg_points_last), so the kernel never sees two values
+// for one element.
+int run_points(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path, const uint64_t* coords,
+               uint64_t n_points, uint32_t fill_missing, void* vals, uint64_t slot_budget_bytes, uint32_t io_threads,
+               bool host, bool write) {
+    const std::string what = write ? "write_points" : "read_points";
     Plan P;
     std::vector<SortedPoint> pts;
-    // 1. before any file is read
-    const int prc = plan_points(ctx, what, meta, root, path, host ? 1 : fill_missing, coords, out, n_points, nullptr,
-                                slot_budget_bytes, P, pts);
+    std::vector<uint8_t> keep;
+    if (write) {
+        keep.assign(n_points, 1);
+        if (coords && meta && meta->ndim >= 1 && meta->ndim <= ZCG_MAX_DIMS)
+            zcg_points_last(coords, n_points, meta->ndim, keep.data());
+    }
+    // before any file is read or written
+    const int prc = plan_points(ctx, what, meta, root, path, !write && (host || fill_missing), coords, vals, n_points,
+                                write ? keep.data() : nullptr, slot_budget_bytes, P, pts);
     if (prc != ZCG_OK) return prc;
     if (P.nothing) return ZCG_OK;
-    const uint32_t es = P.es;
-
-    (void)hipSetDevice(ctx_device(ctx));
-    Stream st;
-    hipError_t e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
-    if (e != hipSuccess) return fail_hip(ctx, e, "read_points stream");
-
-    // 2. per group: read + decode its chunks once, build the table, one launch
-    std::vector<uint8_t> bounce;
-    for (size_t g = 0; g < P.groups.size(); g++) {
-        const Group& G = P.groups[g];
-        const uint32_t m = (uint32_t)G.keys.size();
-        const size_t np = G.b1 - G.b0;
-        const uint64_t* lo = &P.glo[g * ZCG_MAX_DIMS];
-        const uint64_t* n = &P.gn[g * ZCG_MAX_DIMS];
-        const uint64_t entries = P.gentries[g];
-        GroupSlots S;
-        DevMem staging;
-        std::vector<const void*> table(std::max<uint64_t>(entries, 1), nullptr);
-        if (m) {
-            int rc = group_slots(ctx, what, meta, root, path, P, g, S);
-            if (rc != ZCG_OK) return rc;
-            std::vector<int32_t> status(m, ZCG_OK);
-            rc = zcg_store_read_chunks_device(ctx, &meta->array, m, S.cpaths.data(), S.ptrs.data(), status.data(),
-                                              io_threads ? io_threads : 1);
-            if (rc != ZCG_OK) return rc;
-            for (uint32_t i = 0; i < m; i++) {
-                if (status[i] == ZCG_ABSENT) continue;  // read_chunk -> Ok(None): a NULL entry
-                if (status[i] != ZCG_OK) return chunk_failed(ctx, what, P, G.keys[i], status[i]);
-                table[S.tidx[i]] = S.ptrs[i];
-            }
-        }
-        PointsDev X;
-        if (host && (e = staging.alloc(np * es)) != hipSuccess) return fail_hip(ctx, e, "read_points staging");
-        e = points_upload(P, G, pts, coords, table.data(), entries, X, st.s);
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(st.s);  // the host vectors of an enqueued copy end with this scope
-            return fail_hip(ctx, e, "read_points H2D");
-        }
-        uint8_t* db = (uint8_t*)X.mem.p;
-        // host: the group's values in sorted order, permuted below; device: straight to the caller's order
-        const int rc = points_call(ctx, &P.r, lo, n, (const void* const*)db, (const uint64_t*)(db + X.o_co),
-                                   host ? nullptr : (const uint64_t*)(db + X.o_ord), np, host ? staging.p : out,
-                                   (uint64_t*)(db + X.o_fo), (void*)st.s, 0);
-        if (rc != ZCG_OK) {
-            (void)hipStreamSynchronize(st.s);
-            return rc;
-        }
-        uint64_t first_outside = ~0ull;
-        e = hipMemcpyAsync(&first_outside, db + X.o_fo, sizeof first_outside, hipMemcpyDeviceToHost, st.s);
-        if (e == hipSuccess && host) {
-            bounce.resize(np * es);
-            e = hipMemcpyAsync(bounce.data(), staging.p, np * es, hipMemcpyDeviceToHost, st.s);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(st.s);
-        else (void)hipStreamSynchronize(st.s);
-        if (e != hipSuccess) return fail_hip(ctx, e, "read_points assembly");
-        const int orc = points_outside(ctx, what, first_outside);
-        if (orc != ZCG_OK) return orc;
-        if (host)
-            for (size_t i = 0; i < np; i++)
-                memcpy((uint8_t*)out + pts[G.b0 + i].i * es, bounce.data() + i * es, es);
-    }
-    return ZCG_OK;
-}
-
-// write_ndarray for the 1-element boxes of point 0, 1, ... in order: of two
-// points with one coordinate the later one counts (zcg_points_last), so the
-// kernel never sees two values for one element.  Per group: every chunk is
-// read (or, absent, prefilled) unless it has one element, the points are
-// scattered, and every chunk of the group is encoded and written once.
-int write_points(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path, const uint64_t* coords,
-                 uint64_t n_points, const void* in, uint64_t slot_budget_bytes, uint32_t io_threads, bool host) {
-    const std::string what = "write_points";
-    Plan P;
-    std::vector<SortedPoint> pts;
-    std::vector<uint8_t> keep(n_points, 1);
-    if (coords && meta && meta->ndim >= 1 && meta->ndim <= ZCG_MAX_DIMS)
-        zcg_points_last(coords, n_points, meta->ndim, keep.data());
-    // 1. before any file is read or written
-    const int prc = plan_points(ctx, what, meta, root, path, 0, coords, in, n_points, keep.data(), slot_budget_bytes,
-                                P, pts);
-    if (prc != ZCG_OK) return prc;
-    if (P.nothing) return ZCG_OK;
-    const uint32_t es = P.es;
-    const uint64_t fillv = meta->has_fill_value ? meta->fill_value : 0;
-    const uint32_t threads = io_threads ? io_threads : 1;
-
-    (void)hipSetDevice(ctx_device(ctx));
-    Stream st;
-    hipError_t e = hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking);
-    if (e != hipSuccess) return fail_hip(ctx, e, "write_points stream");
-
-    std::vector<uint8_t> bounce;
-    for (size_t g = 0; g < P.groups.size(); g++) {
-        const Group& G = P.groups[g];
-        const uint32_t m = (uint32_t)G.keys.size();
-        const size_t np = G.b1 - G.b0;
-        if (m == 0) continue;
-        const uint64_t* lo = &P.glo[g * ZCG_MAX_DIMS];
-        const uint64_t* n = &P.gn[g * ZCG_MAX_DIMS];
-        const uint64_t entries = P.gentries[g];
-        GroupSlots S;
-        DevMem staging, absent_dev;
-        int rc = group_slots(ctx, what, meta, root, path, P, g, S);
-        if (rc != ZCG_OK) return rc;
-
-        // 2. the existing chunks; absent ones start as fill value
-        std::vector<void*> absent;
-        if (G.read_first[0]) {
-            std::vector<int32_t> status(m, ZCG_OK);
-            rc = zcg_store_read_chunks_device(ctx, &meta->array, m, S.cpaths.data(), S.ptrs.data(), status.data(),
-                                              threads);
-            if (rc != ZCG_OK) return rc;
-            for (uint32_t i = 0; i < m; i++) {
-                if (status[i] == ZCG_ABSENT) absent.push_back(S.ptrs[i]);  // ndarray.rs:351-364
-                else if (status[i] != ZCG_OK) return chunk_failed(ctx, what, P, G.keys[i], status[i]);
-            }
-        }
-
-        // 3. the table (every chunk of the group has a slot), the points, the values
-        std::vector<void*> table(entries, nullptr);
-        for (uint32_t i = 0; i < m; i++) table[S.tidx[i]] = S.ptrs[i];
-        PointsDev X;
-        if (host && (e = staging.alloc(np * es)) != hipSuccess) return fail_hip(ctx, e, "write_points staging");
-        if (!absent.empty() && (e = absent_dev.alloc(absent.size() * sizeof(void*))) != hipSuccess)
-            return fail_hip(ctx, e, "write_points table");
-        e = points_upload(P, G, pts, coords, (const void* const*)table.data(), entries, X, st.s);
-        if (e == hipSuccess && !absent.empty())
-            e = hipMemcpyAsync(absent_dev.p, absent.data(), absent.size() * sizeof(void*), hipMemcpyHostToDevice, st.s);
-        if (e == hipSuccess && host) {
-            bounce.resize(np * es);
-            for (size_t i = 0; i < np; i++)
-                memcpy(bounce.data() + i * es, (const uint8_t*)in + pts[G.b0 + i].i * es, es);
-            e = hipMemcpyAsync(staging.p, bounce.data(), np * es, hipMemcpyHostToDevice, st.s);
-        }
-        if (e == hipSuccess)
-            e = launch_slot_fill((void* const*)absent_dev.p, (uint32_t)absent.size(), P.D, es, fillv, st.s);
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(st.s);  // the host vectors of an enqueued copy end with this scope
-            return fail_hip(ctx, e, "write_points H2D");
-        }
-
-        // 4. the scatter: no two points of the call share an element
-        uint8_t* db = (uint8_t*)X.mem.p;
-        rc = points_call(ctx, &P.r, lo, n, (const void* const*)db, (const uint64_t*)(db + X.o_co),
-                         host ? nullptr : (const uint64_t*)(db + X.o_ord), np, host ? staging.p : (void*)in,
-                         (uint64_t*)(db + X.o_fo), (void*)st.s, 1);
-        if (rc != ZCG_OK) {
-            (void)hipStreamSynchronize(st.s);
-            return rc;
-        }
-        uint64_t first_outside = ~0ull;
-        e = hipMemcpyAsync(&first_outside, db + X.o_fo, sizeof first_outside, hipMemcpyDeviceToHost, st.s);
-        if (e == hipSuccess) e = hipStreamSynchronize(st.s);
-        else (void)hipStreamSynchronize(st.s);
-        if (e != hipSuccess) return fail_hip(ctx, e, "write_points scatter");
-        rc = points_outside(ctx, what, first_outside);
-        if (rc != ZCG_OK) return rc;
-
-        // 5. encode and write every chunk of the group, once
-        std::vector<int32_t> wst(m, ZCG_OK);
-        rc = zcg_store_write_chunks_device(ctx, &meta->array, m, S.cpaths.data(), (const void* const*)S.ptrs.data(),
-                                           wst.data(), threads);
-        if (rc != ZCG_OK) return rc;
-        for (uint32_t i = 0; i < m; i++)
-            if (wst[i] != ZCG_OK) return chunk_failed(ctx, what, P, G.keys[i], wst[i]);
-    }
-    return ZCG_OK;
+    PointsPayload X{P, what, pts, coords, vals, host, write};
+    return run_groups(ctx, what, meta, root, path, P, write, io_threads, X);
 }
 
 }  // namespace
@@ -1434,24 +1125,25 @@ extern "C" int zcg_store_read_points_device(zcg_ctx* ctx, const zcg_array_meta* 
                                             const char* path, const uint64_t* coords, uint64_t n_points,
                                             uint32_t fill_missing, void* d_out, uint64_t slot_budget_bytes,
                                             uint32_t io_threads) {
-    return read_points(ctx, meta, root, path, coords, n_points, fill_missing, d_out, slot_budget_bytes, io_threads,
-                       false);
+    return run_points(ctx, meta, root, path, coords, n_points, fill_missing, d_out, slot_budget_bytes, io_threads,
+                      false, false);
 }
 
 extern "C" int zcg_store_read_points(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
                                      const uint64_t* coords, uint64_t n_points, void* out,
                                      uint64_t slot_budget_bytes, uint32_t io_threads) {
-    return read_points(ctx, meta, root, path, coords, n_points, 1, out, slot_budget_bytes, io_threads, true);
+    return run_points(ctx, meta, root, path, coords, n_points, 1, out, slot_budget_bytes, io_threads, true, false);
 }
 
 extern "C" int zcg_store_write_points_device(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root,
                                              const char* path, const uint64_t* coords, uint64_t n_points,
                                              const void* d_in, uint64_t slot_budget_bytes, uint32_t io_threads) {
-    return write_points(ctx, meta, root, path, coords, n_points, d_in, slot_budget_bytes, io_threads, false);
+    return run_points(ctx, meta, root, path, coords, n_points, 0, (void*)d_in, slot_budget_bytes, io_threads, false,
+                      true);
 }
 
 extern "C" int zcg_store_write_points(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
                                       const uint64_t* coords, uint64_t n_points, const void* in,
                                       uint64_t slot_budget_bytes, uint32_t io_threads) {
-    return write_points(ctx, meta, root, path, coords, n_points, in, slot_budget_bytes, io_threads, true);
+    return run_points(ctx, meta, root, path, coords, n_points, 0, (void*)in, slot_budget_bytes, io_threads, true, true);
 }

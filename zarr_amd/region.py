@@ -217,6 +217,92 @@ def assemble_regions(meta: ArrayMetadata, shape: Sequence[int], es: int, table, 
     _raise_status(st, ctx, "read_regions")
 
 
+def _native_meta(meta: ArrayMetadata, flags: int):
+    st, am, msg = _native.array_meta_from_json(meta.to_json())
+    if st != _native.OK:
+        raise ZarrIOError(_native.STATUS_NAMES.get(st, str(st)), f"array metadata: {msg}")
+    am.array.compression.flags = flags
+    return am
+
+
+class _StoreCall:
+    """One store-level native call, prepared: the native metadata (`am`), the
+    context, and the encoded root and path.  call(what, name, *args) runs
+    lib.<name>(ctx, am, root, path, *args) and raises what a status other than
+    OK stands for, with `what` before the context's message."""
+
+    def __init__(self, hier, path_name: str, meta: ArrayMetadata, flags: int, device: int):
+        self.am = _native_meta(meta, flags)
+        self.ctx = _native.context(device)
+        self.head = (self.ctx.handle, ctypes.byref(self.am), os.fsencode(hier.base_path), path_name.encode())
+
+    def __call__(self, what: str, name: str, *args) -> None:
+        r = getattr(self.ctx.lib, name)(*self.head, *args)
+        if r != _native.OK:
+            raise ZarrIOError(_native.STATUS_NAMES.get(r, str(r)), f"{what}: {self.ctx.last_error()}")
+
+
+def _u64(rows, nd: int) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(rows, dtype=np.uint64).reshape(-1, nd))
+
+
+class _Boxes:
+    """A list of B boxes as the store-level calls take them: offsets, shapes
+    and optional steps as contiguous B x ndim uint64 arrays (offs, shp, stp),
+    every box's dense element strides in the chunk memory order, and the byte
+    offsets `at` (B + 1) of the boxes back to back."""
+
+    def __init__(self, meta: ArrayMetadata, offsets, shapes, es: int, steps=None):
+        nd = meta.get_ndim()
+        self.order = "F" if meta.chunk_memory_layout == "F" else "C"
+        self.es = es
+        self.shapes = [tuple(s) for s in shapes]
+        self.B = len(self.shapes)
+        self.offs, self.shp, self.stp = _u64(offsets, nd), _u64(self.shapes, nd), steps
+        known, self.strides, self.at = {}, [], [0]
+        for s in self.shapes:
+            if s not in known:
+                known[s] = _strides(s, self.order), int(np.prod(s, dtype=object)) * es
+            self.strides.append(list(known[s][0]))  # a list of its own per box, as a caller may change it
+            self.at.append(self.at[-1] + known[s][1])
+
+    def pointers(self, base: int):
+        """Box b's address when the boxes lie back to back from `base`."""
+        return (ctypes.c_void_p * max(self.B, 1))(*[base + a for a in self.at[:-1]])
+
+    def out(self, device=None):
+        """Memory for the boxes back to back: host bytes, or with `device` a
+        uint8 tensor -> (buffer, pointers)."""
+        if device is None:
+            buf = np.empty(max(self.at[-1], 1), np.uint8)
+            return buf, self.pointers(buf.ctypes.data)
+        import torch
+        buf = torch.empty(max(self.at[-1], 1), dtype=torch.uint8, device=torch.device("cuda", device))
+        return buf, self.pointers(buf.data_ptr())
+
+    def views(self, host: np.ndarray, dt) -> list:
+        """The boxes in `host` (out()'s bytes) as arrays, not copied."""
+        return [np.ndarray(s, dtype=dt, buffer=host, offset=self.at[b],
+                           strides=tuple(k * self.es for k in self.strides[b])) for b, s in enumerate(self.shapes)]
+
+
+def _dense_inputs(meta: ArrayMetadata, arrays):
+    """Host input boxes, each dense in the chunk memory order -> (the dense
+    arrays, which own the memory; their shapes B x ndim; the pointer array)."""
+    nd = meta.get_ndim()
+    arrays = [np.asarray(a) for a in arrays]
+    dense = []
+    for a in arrays:
+        if a.ndim != nd:
+            raise ZarrIOError("InvalidData", "Wrong number of dimensions")
+        dt = a.dtype.newbyteorder("=")
+        check_array_type(dt, meta)
+        dense.append(np.ascontiguousarray(a.astype(dt, copy=False).T if meta.chunk_memory_layout == "F"
+                                          else a.astype(dt, copy=False)))
+    ins = (ctypes.c_void_p * max(len(dense), 1))(*[a.ctypes.data if a.size else 0 for a in dense])
+    return dense, _u64([a.shape for a in arrays], nd), ins
+
+
 def read_ndarrays(hier, path_name: str, meta: ArrayMetadata, offsets, shape: Sequence[int], t, device: int = 0,
                   as_tensor: bool = False, flags: int = 0, slot_budget_bytes: int = 0):
     """read_ndarray for many boxes of one `shape` in one native call
@@ -226,45 +312,25 @@ def read_ndarrays(hier, path_name: str, meta: ArrayMetadata, offsets, shape: Seq
     decoded chunks held on the device at a time (0: 4 GiB).  With as_tensor the
     result is (uint8 device tensor of B boxes back to back, element strides of
     one box), as read_ndarray gives for one."""
-    import torch
     check_array_type(t, meta)
     shape = [int(x) for x in shape]
-    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64).reshape(-1, len(shape)))
+    offs = _u64(offsets, len(shape))
     if len(shape) != meta.get_ndim():
         raise ZarrIOError("InvalidData", "Wrong number of dimensions")
-    B = offs.shape[0]
     dt = np.dtype(t).newbyteorder("=")
-    es = dt.itemsize
-    order = "F" if meta.chunk_memory_layout == "F" else "C"
-    strides = _strides(shape, order)
-    total = int(np.prod(shape)) if shape else 1
-    st, am, msg = _native.array_meta_from_json(meta.to_json())
-    if st != _native.OK:
-        raise ZarrIOError(_native.STATUS_NAMES.get(st, str(st)), f"array metadata: {msg}")
-    am.array.compression.flags = flags
-    ctx = _native.context(device)
+    bx = _Boxes(meta, offs, [shape] * offs.shape[0], dt.itemsize)
+    strides = _strides(shape, bx.order)
+    call = _StoreCall(hier, path_name, meta, flags, device)
     bshape = (ctypes.c_uint64 * _native.MAX_DIMS)(*shape)
-    root, path = os.fsencode(hier.base_path), path_name.encode()
+    buf, outs = bx.out(device if as_tensor else None)
+    tail = (bx.offs.ctypes.data, ctypes.addressof(outs), bx.B, slot_budget_bytes, 16)
     if as_tensor:
-        out = torch.empty(max(B * total * es, 1), dtype=torch.uint8, device=torch.device("cuda", device))
-        outs = (ctypes.c_void_p * max(B, 1))(*[out.data_ptr() + b * total * es for b in range(B)])
         ostr = (ctypes.c_int64 * _native.MAX_DIMS)(*strides)
-        r = ctx.lib.zcg_store_read_boxes_device(ctx.handle, ctypes.byref(am), root, path, ctypes.addressof(bshape),
-                                                ctypes.addressof(ostr), 1, offs.ctypes.data, ctypes.addressof(outs),
-                                                B, slot_budget_bytes, 16)
-    else:
-        host = np.empty(max(B * total * es, 1), np.uint8)
-        outs = (ctypes.c_void_p * max(B, 1))(*[host.ctypes.data + b * total * es for b in range(B)])
-        r = ctx.lib.zcg_store_read_boxes(ctx.handle, ctypes.byref(am), root, path, ctypes.addressof(bshape),
-                                         offs.ctypes.data, ctypes.addressof(outs), B, slot_budget_bytes, 16)
-    if r != _native.OK:
-        raise ZarrIOError(_native.STATUS_NAMES.get(r, str(r)), f"read_boxes: {ctx.last_error()}")
-    if as_tensor:
-        return out[: B * total * es], strides
-    res = np.empty((B, *shape), dtype=dt, order="C")
-    for b in range(B):
-        box = np.ndarray(tuple(shape), dtype=dt, buffer=host, offset=b * total * es,
-                         strides=tuple(s * es for s in strides))
+        call("read_boxes", "zcg_store_read_boxes_device", ctypes.addressof(bshape), ctypes.addressof(ostr), 1, *tail)
+        return buf[: bx.at[-1]], strides
+    call("read_boxes", "zcg_store_read_boxes", ctypes.addressof(bshape), *tail)
+    res = np.empty((bx.B, *shape), dtype=dt, order="C")
+    for b, box in enumerate(bx.views(buf, dt)):
         res[b] = box
     return res
 
@@ -291,19 +357,39 @@ def scatter_regions(meta: ArrayMetadata, shape: Sequence[int], es: int, table, t
     _raise_status(st, ctx, "write_regions")
 
 
+def _grid(name: str, meta: ArrayMetadata, bound, *rows):
+    """A zcg_*_grid call (host code, no GPU) over `rows` (each B x ndim: the
+    offsets, then what else the call takes per box) -> (lo, n)."""
+    L = _native.load_library()
+    nd = meta.get_ndim()
+    r = _region(meta, BoundingBox([0] * nd, bound), 1, False, 0, [0] * nd)
+    rows = [_u64(x, nd) for x in rows]
+    lo = (ctypes.c_uint64 * _native.MAX_DIMS)()
+    n = (ctypes.c_uint64 * _native.MAX_DIMS)()
+    getattr(L, name)(ctypes.byref(r), *[x.ctypes.data for x in rows], rows[0].shape[0], ctypes.addressof(lo),
+                     ctypes.addressof(n))
+    return [int(lo[d]) for d in range(nd)], [int(n[d]) for d in range(nd)]
+
+
+def _waves(name: str, meta: ArrayMetadata, bound, *rows):
+    """A zcg_*_waves call (host code, no GPU) over `rows` as for _grid ->
+    (number of waves, wave index per box)."""
+    L = _native.load_library()
+    nd = meta.get_ndim()
+    r = _region(meta, BoundingBox([0] * nd, bound), 1, False, 0, [0] * nd)
+    rows = [_u64(x, nd) for x in rows]
+    B = rows[0].shape[0]
+    wave_of = np.zeros(max(B, 1), np.uint32)
+    n = getattr(L, name)(ctypes.byref(r), *[x.ctypes.data for x in rows], B, wave_of.ctypes.data)
+    return int(n), [int(w) for w in wave_of[:B]]
+
+
 def regions_waves(meta: ArrayMetadata, offsets, shape: Sequence[int]):
     """zcg_regions_waves (host code, no GPU): the greedy split of the boxes
     `offsets` (B x ndim) of one `shape` into consecutive runs of pairwise
     disjoint boxes -> (number of waves, wave index per box).  scatter_regions
     calls for the waves, in order on one stream, let the later box win."""
-    L = _native.load_library()
-    nd = meta.get_ndim()
-    r = _region(meta, BoundingBox([0] * nd, shape), 1, False, 0, [0] * nd)
-    offs = np.ascontiguousarray(np.array(offsets, dtype=np.uint64).reshape(-1, nd))
-    B = offs.shape[0]
-    wave_of = np.zeros(max(B, 1), np.uint32)
-    n = L.zcg_regions_waves(ctypes.byref(r), offs.ctypes.data, B, wave_of.ctypes.data)
-    return int(n), [int(w) for w in wave_of[:B]]
+    return _waves("zcg_regions_waves", meta, shape, offsets)
 
 
 def write_ndarrays(hier, path_name: str, meta: ArrayMetadata, offsets, arrays, device: int = 0,
@@ -336,38 +422,26 @@ def write_ndarrays(hier, path_name: str, meta: ArrayMetadata, offsets, arrays, d
         shape = [int(x) for x in arrays.shape[1:]]
         dt = arrays.dtype.newbyteorder("=")
     check_array_type(dt, meta)
-    es = dt.itemsize
-    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64).reshape(-1, nd))
-    B = offs.shape[0]
-    order = "F" if meta.chunk_memory_layout == "F" else "C"
-    total = int(np.prod(shape)) if shape else 1
-    if not tensor_in and arrays.shape[0] != B:
+    offs = _u64(offsets, nd)
+    if not tensor_in and arrays.shape[0] != offs.shape[0]:
         raise ZarrIOError("InvalidData", "Bounding boxes and arrays differ in number")
-    st, am, msg = _native.array_meta_from_json(meta.to_json())
-    if st != _native.OK:
-        raise ZarrIOError(_native.STATUS_NAMES.get(st, str(st)), f"array metadata: {msg}")
-    am.array.compression.flags = flags
-    ctx = _native.context(device)
+    bx = _Boxes(meta, offs, [shape] * offs.shape[0], dt.itemsize)
+    call = _StoreCall(hier, path_name, meta, flags, device)
     bshape = (ctypes.c_uint64 * _native.MAX_DIMS)(*shape)
-    root, path = os.fsencode(hier.base_path), path_name.encode()
     if tensor_in:
-        if tensor.numel() * tensor.element_size() < B * total * es:
+        if tensor.numel() * tensor.element_size() < bx.at[-1]:
             raise ZarrIOError("InvalidData", "Bounding boxes and array have different shape")
-        ins = (ctypes.c_void_p * max(B, 1))(*[tensor.data_ptr() + b * total * es for b in range(B)])
-        istr = (ctypes.c_int64 * _native.MAX_DIMS)(*_strides(shape, order))
-        r = ctx.lib.zcg_store_write_boxes_device(ctx.handle, ctypes.byref(am), root, path, ctypes.addressof(bshape),
-                                                 ctypes.addressof(istr), offs.ctypes.data, ctypes.addressof(ins), B,
-                                                 slot_budget_bytes, 16)
+        ins = bx.pointers(tensor.data_ptr())
+        istr = (ctypes.c_int64 * _native.MAX_DIMS)(*_strides(shape, bx.order))
+        call("write_boxes", "zcg_store_write_boxes_device", ctypes.addressof(bshape), ctypes.addressof(istr),
+             bx.offs.ctypes.data, ctypes.addressof(ins), bx.B, slot_budget_bytes, 16)
     else:
         # box b dense in the chunk memory order, the boxes back to back
         host = np.ascontiguousarray(arrays.astype(dt, copy=False).transpose([0] + list(range(nd, 0, -1)))
-                                    if order == "F" else arrays.astype(dt, copy=False))
-        base = host.ctypes.data if host.size else 0
-        ins = (ctypes.c_void_p * max(B, 1))(*[base + b * total * es for b in range(B)])
-        r = ctx.lib.zcg_store_write_boxes(ctx.handle, ctypes.byref(am), root, path, ctypes.addressof(bshape),
-                                          offs.ctypes.data, ctypes.addressof(ins), B, slot_budget_bytes, 16)
-    if r != _native.OK:
-        raise ZarrIOError(_native.STATUS_NAMES.get(r, str(r)), f"write_boxes: {ctx.last_error()}")
+                                    if bx.order == "F" else arrays.astype(dt, copy=False))
+        ins = bx.pointers(host.ctypes.data if host.size else 0)
+        call("write_boxes", "zcg_store_write_boxes", ctypes.addressof(bshape), bx.offs.ctypes.data,
+             ctypes.addressof(ins), bx.B, slot_budget_bytes, 16)
 
 
 def vboxes_tensor(offsets, shapes, strides, bases, device: int = 0):
@@ -392,17 +466,19 @@ def regions_v_scratch_bytes(n_boxes: int) -> int:
     return int(_native.load_library().zcg_regions_v_scratch_bytes(int(n_boxes)))
 
 
-def _regions_v(name: str, meta: ArrayMetadata, bound, es, table, table_lo, table_n, boxes, status, scratch, fill,
-               fill_value, device, stream) -> None:
+def _regions_vs(record, scratch_bytes, name: str, meta: ArrayMetadata, bound, es, table, table_lo, table_n, boxes,
+                status, scratch, fill, fill_value, device, stream) -> None:
+    """The _v and _s device-level calls: `record` is the box record type
+    (_native.VBox or SBox), `scratch_bytes` its call's scratch size function."""
     ctx = _native.context(device)
     nd = meta.get_ndim()
     r = _region(meta, BoundingBox([0] * nd, bound), es, fill, fill_value, [0] * nd)
     lo = (ctypes.c_uint64 * _native.MAX_DIMS)(*[int(x) for x in table_lo])
     n = (ctypes.c_uint64 * _native.MAX_DIMS)(*[int(x) for x in table_n])
-    n_boxes = boxes.numel() * boxes.element_size() // ctypes.sizeof(_native.VBox) if boxes is not None else 0
+    n_boxes = boxes.numel() * boxes.element_size() // ctypes.sizeof(record) if boxes is not None else 0
     if n_boxes and scratch is None:
         import torch
-        scratch = torch.empty(regions_v_scratch_bytes(n_boxes), dtype=torch.uint8, device=boxes.device)
+        scratch = torch.empty(scratch_bytes(n_boxes), dtype=torch.uint8, device=boxes.device)
     st = getattr(ctx.lib, name)(ctx.handle, ctypes.byref(r), ctypes.addressof(lo), ctypes.addressof(n),
                                 table.data_ptr() if table is not None else None,
                                 boxes.data_ptr() if n_boxes else None, n_boxes,
@@ -419,8 +495,8 @@ def assemble_regions_v(meta: ArrayMetadata, bound: Sequence[int], es: int, table
     `bound` = the largest extent per dimension any box may have.  `scratch` =
     device tensor of regions_v_scratch_bytes(B) bytes (None: allocated here,
     which a captured call must not do).  Asynchronous."""
-    _regions_v("zcg_read_regions_v", meta, bound, es, table, table_lo, table_n, boxes, status, scratch, fill,
-               fill_value, device, stream)
+    _regions_vs(_native.VBox, regions_v_scratch_bytes, "zcg_read_regions_v", meta, bound, es, table, table_lo,
+                table_n, boxes, status, scratch, fill, fill_value, device, stream)
 
 
 def scatter_regions_v(meta: ArrayMetadata, bound: Sequence[int], es: int, table, table_lo, table_n, boxes, status,
@@ -429,8 +505,8 @@ def scatter_regions_v(meta: ArrayMetadata, bound: Sequence[int], es: int, table,
     box's view is written into the chunk slots of `table`.  Boxes of one call
     that overlap leave either value; split the call with regions_v_waves where
     the later box must win.  Asynchronous."""
-    _regions_v("zcg_write_regions_v", meta, bound, es, table, table_lo, table_n, boxes, status, scratch, False, 0,
-               device, stream)
+    _regions_vs(_native.VBox, regions_v_scratch_bytes, "zcg_write_regions_v", meta, bound, es, table, table_lo,
+                table_n, boxes, status, scratch, False, 0, device, stream)
 
 
 def _bound(shapes, nd: int) -> List[int]:
@@ -440,39 +516,34 @@ def _bound(shapes, nd: int) -> List[int]:
 def regions_v_grid(meta: ArrayMetadata, offsets, shapes):
     """zcg_regions_v_grid (host code, no GPU): the union of the boxes' grid
     ranges -> (lo, n)."""
-    L = _native.load_library()
-    nd = meta.get_ndim()
-    r = _region(meta, BoundingBox([0] * nd, _bound(shapes, nd)), 1, False, 0, [0] * nd)
-    offs = np.ascontiguousarray(np.array(offsets, dtype=np.uint64).reshape(-1, nd))
-    shp = np.ascontiguousarray(np.array(shapes, dtype=np.uint64).reshape(-1, nd))
-    lo = (ctypes.c_uint64 * _native.MAX_DIMS)()
-    n = (ctypes.c_uint64 * _native.MAX_DIMS)()
-    L.zcg_regions_v_grid(ctypes.byref(r), offs.ctypes.data, shp.ctypes.data, offs.shape[0], ctypes.addressof(lo),
-                         ctypes.addressof(n))
-    return [int(lo[d]) for d in range(nd)], [int(n[d]) for d in range(nd)]
+    return _grid("zcg_regions_v_grid", meta, _bound(shapes, meta.get_ndim()), offsets, shapes)
 
 
 def regions_v_waves(meta: ArrayMetadata, offsets, shapes):
     """zcg_regions_v_waves (host code, no GPU): regions_waves for boxes
     `offsets` (B x ndim) with `shapes` (B x ndim) -> (number of waves, wave
     index per box)."""
-    L = _native.load_library()
+    return _waves("zcg_regions_v_waves", meta, _bound(shapes, meta.get_ndim()), offsets, shapes)
+
+
+def _read_boxes(hier, path_name, meta, boxes, steps, t, device, as_tensor, flags, slot_budget_bytes):
+    """read_ndarrays_v (steps None) and read_ndarrays_s."""
+    check_array_type(t, meta)
     nd = meta.get_ndim()
-    r = _region(meta, BoundingBox([0] * nd, _bound(shapes, nd)), 1, False, 0, [0] * nd)
-    offs = np.ascontiguousarray(np.array(offsets, dtype=np.uint64).reshape(-1, nd))
-    shp = np.ascontiguousarray(np.array(shapes, dtype=np.uint64).reshape(-1, nd))
-    B = offs.shape[0]
-    wave_of = np.zeros(max(B, 1), np.uint32)
-    n = L.zcg_regions_v_waves(ctypes.byref(r), offs.ctypes.data, shp.ctypes.data, B, wave_of.ctypes.data)
-    return int(n), [int(w) for w in wave_of[:B]]
-
-
-def _native_meta(meta: ArrayMetadata, flags: int):
-    st, am, msg = _native.array_meta_from_json(meta.to_json())
-    if st != _native.OK:
-        raise ZarrIOError(_native.STATUS_NAMES.get(st, str(st)), f"array metadata: {msg}")
-    am.array.compression.flags = flags
-    return am
+    for bb in boxes:
+        if len(bb.offset) != nd:
+            raise ZarrIOError("InvalidData", "Wrong number of dimensions")
+    stp = None if steps is None else _steps_arg(steps, len(boxes), nd)
+    dt = np.dtype(t).newbyteorder("=")
+    bx = _Boxes(meta, [bb.offset for bb in boxes], [bb.shape for bb in boxes], dt.itemsize, stp)
+    call = _StoreCall(hier, path_name, meta, flags, device)
+    buf, outs = bx.out(device if as_tensor else None)
+    name = "zcg_store_read_boxes_" + ("v" if stp is None else "s") + ("_device" if as_tensor else "")
+    args = [bx.shp.ctypes.data] + ([] if stp is None else [stp.ctypes.data]) + ([None, 1] if as_tensor else [])
+    call("read_boxes", name, *args, bx.offs.ctypes.data, ctypes.addressof(outs), bx.B, slot_budget_bytes, 16)
+    if as_tensor:
+        return buf[: bx.at[-1]], bx.at[:-1], bx.strides
+    return [v.copy(order=bx.order) for v in bx.views(buf, dt)]
 
 
 def read_ndarrays_v(hier, path_name: str, meta: ArrayMetadata, boxes: Sequence[BoundingBox], t, device: int = 0,
@@ -483,42 +554,7 @@ def read_ndarrays_v(hier, path_name: str, meta: ArrayMetadata, boxes: Sequence[B
     decoded once.  With as_tensor the result is (uint8 device tensor of the
     boxes back to back, byte offset per box, element strides per box), each box
     dense in the chunk memory order."""
-    import torch
-    check_array_type(t, meta)
-    nd = meta.get_ndim()
-    for bb in boxes:
-        if len(bb.offset) != nd:
-            raise ZarrIOError("InvalidData", "Wrong number of dimensions")
-    B = len(boxes)
-    dt = np.dtype(t).newbyteorder("=")
-    es = dt.itemsize
-    order = "F" if meta.chunk_memory_layout == "F" else "C"
-    offs = np.ascontiguousarray(np.array([bb.offset for bb in boxes], dtype=np.uint64).reshape(-1, nd))
-    shp = np.ascontiguousarray(np.array([bb.shape for bb in boxes], dtype=np.uint64).reshape(-1, nd))
-    strides = [_strides(bb.shape, order) for bb in boxes]
-    at = [0]
-    for bb in boxes:
-        at.append(at[-1] + int(np.prod(bb.shape, dtype=object)) * es)
-    am = _native_meta(meta, flags)
-    ctx = _native.context(device)
-    root, path = os.fsencode(hier.base_path), path_name.encode()
-    if as_tensor:
-        out = torch.empty(max(at[-1], 1), dtype=torch.uint8, device=torch.device("cuda", device))
-        outs = (ctypes.c_void_p * max(B, 1))(*[out.data_ptr() + at[b] for b in range(B)])
-        r = ctx.lib.zcg_store_read_boxes_v_device(ctx.handle, ctypes.byref(am), root, path, shp.ctypes.data, None, 1,
-                                                  offs.ctypes.data, ctypes.addressof(outs), B, slot_budget_bytes, 16)
-    else:
-        host = np.empty(max(at[-1], 1), np.uint8)
-        outs = (ctypes.c_void_p * max(B, 1))(*[host.ctypes.data + at[b] for b in range(B)])
-        r = ctx.lib.zcg_store_read_boxes_v(ctx.handle, ctypes.byref(am), root, path, shp.ctypes.data,
-                                           offs.ctypes.data, ctypes.addressof(outs), B, slot_budget_bytes, 16)
-    if r != _native.OK:
-        raise ZarrIOError(_native.STATUS_NAMES.get(r, str(r)), f"read_boxes: {ctx.last_error()}")
-    if as_tensor:
-        return out[: at[-1]], at[:-1], strides
-    return [np.ndarray(tuple(bb.shape), dtype=dt, buffer=host, offset=at[b],
-                       strides=tuple(s * es for s in strides[b])).copy(order=order)
-            for b, bb in enumerate(boxes)]
+    return _read_boxes(hier, path_name, meta, boxes, None, t, device, as_tensor, flags, slot_budget_bytes)
 
 
 def write_ndarrays_v(hier, path_name: str, meta: ArrayMetadata, offsets, arrays, device: int = 0,
@@ -529,30 +565,15 @@ def write_ndarrays_v(hier, path_name: str, meta: ArrayMetadata, offsets, arrays,
     box 0, 1, ... in that order (a later box wins where two overlap), but every
     chunk the boxes touch is read at most once, and encoded and written once.
     `flags`: decode flags for the chunks that are read first."""
-    nd = meta.get_ndim()
-    arrays = [np.asarray(a) for a in arrays]
-    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64).reshape(-1, nd))
+    arrays = list(arrays)
+    offs = _u64(offsets, meta.get_ndim())
     B = offs.shape[0]
     if len(arrays) != B:
         raise ZarrIOError("InvalidData", "Bounding boxes and arrays differ in number")
-    order = "F" if meta.chunk_memory_layout == "F" else "C"
-    dense = []
-    for a in arrays:
-        if a.ndim != nd:
-            raise ZarrIOError("InvalidData", "Wrong number of dimensions")
-        dt = a.dtype.newbyteorder("=")
-        check_array_type(dt, meta)
-        # dense in the chunk memory order
-        dense.append(np.ascontiguousarray(a.astype(dt, copy=False).T if order == "F" else a.astype(dt, copy=False)))
-    shp = np.ascontiguousarray(np.array([a.shape for a in arrays], dtype=np.uint64).reshape(-1, nd))
-    am = _native_meta(meta, flags)
-    ctx = _native.context(device)
-    ins = (ctypes.c_void_p * max(B, 1))(*[a.ctypes.data if a.size else 0 for a in dense])
-    r = ctx.lib.zcg_store_write_boxes_v(ctx.handle, ctypes.byref(am), os.fsencode(hier.base_path),
-                                        path_name.encode(), shp.ctypes.data, offs.ctypes.data, ctypes.addressof(ins),
-                                        B, slot_budget_bytes, 16)
-    if r != _native.OK:
-        raise ZarrIOError(_native.STATUS_NAMES.get(r, str(r)), f"write_boxes: {ctx.last_error()}")
+    dense, shp, ins = _dense_inputs(meta, arrays)
+    _StoreCall(hier, path_name, meta, flags, device)(
+        "write_boxes", "zcg_store_write_boxes_v", shp.ctypes.data, offs.ctypes.data, ctypes.addressof(ins), B,
+        slot_budget_bytes, 16)
 
 
 def sboxes_tensor(offsets, shapes, steps, strides, bases, device: int = 0):
@@ -581,17 +602,7 @@ def regions_s_scratch_bytes(n_boxes: int) -> int:
 def regions_s_grid(meta: ArrayMetadata, offsets, shapes, steps):
     """zcg_regions_s_grid (host code, no GPU): the union of the grid ranges of
     the boxes' hulls (`shapes`: sample counts, `steps`: B x ndim) -> (lo, n)."""
-    L = _native.load_library()
-    nd = meta.get_ndim()
-    r = _region(meta, BoundingBox([0] * nd, _bound(shapes, nd)), 1, False, 0, [0] * nd)
-    offs = np.ascontiguousarray(np.array(offsets, dtype=np.uint64).reshape(-1, nd))
-    shp = np.ascontiguousarray(np.array(shapes, dtype=np.uint64).reshape(-1, nd))
-    stp = np.ascontiguousarray(np.array(steps, dtype=np.uint64).reshape(-1, nd))
-    lo = (ctypes.c_uint64 * _native.MAX_DIMS)()
-    n = (ctypes.c_uint64 * _native.MAX_DIMS)()
-    L.zcg_regions_s_grid(ctypes.byref(r), offs.ctypes.data, shp.ctypes.data, stp.ctypes.data, offs.shape[0],
-                         ctypes.addressof(lo), ctypes.addressof(n))
-    return [int(lo[d]) for d in range(nd)], [int(n[d]) for d in range(nd)]
+    return _grid("zcg_regions_s_grid", meta, _bound(shapes, meta.get_ndim()), offsets, shapes, steps)
 
 
 def region_s_chunks(meta: ArrayMetadata, offset, shape, step, want_touched: bool = True):
@@ -619,25 +630,6 @@ def region_s_chunks(meta: ArrayMetadata, offset, shape, step, want_touched: bool
     return lo_l, n_l, [flags[at[d]:at[d + 1]].tolist() for d in range(nd)], count
 
 
-def _regions_s(name: str, meta: ArrayMetadata, bound, es, table, table_lo, table_n, boxes, status, scratch, fill,
-               fill_value, device, stream) -> None:
-    ctx = _native.context(device)
-    nd = meta.get_ndim()
-    r = _region(meta, BoundingBox([0] * nd, bound), es, fill, fill_value, [0] * nd)
-    lo = (ctypes.c_uint64 * _native.MAX_DIMS)(*[int(x) for x in table_lo])
-    n = (ctypes.c_uint64 * _native.MAX_DIMS)(*[int(x) for x in table_n])
-    n_boxes = boxes.numel() * boxes.element_size() // ctypes.sizeof(_native.SBox) if boxes is not None else 0
-    if n_boxes and scratch is None:
-        import torch
-        scratch = torch.empty(regions_s_scratch_bytes(n_boxes), dtype=torch.uint8, device=boxes.device)
-    st = getattr(ctx.lib, name)(ctx.handle, ctypes.byref(r), ctypes.addressof(lo), ctypes.addressof(n),
-                                table.data_ptr() if table is not None else None,
-                                boxes.data_ptr() if n_boxes else None, n_boxes,
-                                scratch.data_ptr() if scratch is not None else None,
-                                status.data_ptr() if status is not None else None, _stream_handle(stream, device))
-    _raise_status(st, ctx, name[4:])
-
-
 def assemble_regions_s(meta: ArrayMetadata, bound: Sequence[int], es: int, table, table_lo, table_n, boxes, status,
                        fill: bool, fill_value: int, device: int = 0, stream=None, scratch=None) -> None:
     """Device-level call for many strided boxes (zcg_read_regions_s):
@@ -647,8 +639,8 @@ def assemble_regions_s(meta: ArrayMetadata, bound: Sequence[int], es: int, table
     entries of chunks that hold no sample are never read.  `scratch` = device
     tensor of regions_s_scratch_bytes(B) bytes (None: allocated here, which a
     captured call must not do).  Asynchronous."""
-    _regions_s("zcg_read_regions_s", meta, bound, es, table, table_lo, table_n, boxes, status, scratch, fill,
-               fill_value, device, stream)
+    _regions_vs(_native.SBox, regions_s_scratch_bytes, "zcg_read_regions_s", meta, bound, es, table, table_lo,
+                table_n, boxes, status, scratch, fill, fill_value, device, stream)
 
 
 def scatter_regions_s(meta: ArrayMetadata, bound: Sequence[int], es: int, table, table_lo, table_n, boxes, status,
@@ -659,8 +651,8 @@ def scatter_regions_s(meta: ArrayMetadata, bound: Sequence[int], es: int, table,
     chunks that hold no sample are never read.  Boxes of one call that share a
     sample leave either value; split the call with regions_s_waves where the
     later box must win.  `scratch` as for assemble_regions_s.  Asynchronous."""
-    _regions_s("zcg_write_regions_s", meta, bound, es, table, table_lo, table_n, boxes, status, scratch, False, 0,
-               device, stream)
+    _regions_vs(_native.SBox, regions_s_scratch_bytes, "zcg_write_regions_s", meta, bound, es, table, table_lo,
+                table_n, boxes, status, scratch, False, 0, device, stream)
 
 
 def regions_s_waves(meta: ArrayMetadata, offsets, shapes, steps):
@@ -668,17 +660,7 @@ def regions_s_waves(meta: ArrayMetadata, offsets, shapes, steps):
     boxes (`shapes`: sample counts, `steps`: B x ndim) -> (number of waves,
     wave index per box).  Two boxes intersect only where they share a sample,
     so interleaved boxes (even and odd planes) stay in one wave."""
-    L = _native.load_library()
-    nd = meta.get_ndim()
-    r = _region(meta, BoundingBox([0] * nd, [0] * nd), 1, False, 0, [0] * nd)
-    offs = np.ascontiguousarray(np.array(offsets, dtype=np.uint64).reshape(-1, nd))
-    shp = np.ascontiguousarray(np.array(shapes, dtype=np.uint64).reshape(-1, nd))
-    stp = np.ascontiguousarray(np.array(steps, dtype=np.uint64).reshape(-1, nd))
-    B = offs.shape[0]
-    wave_of = np.zeros(max(B, 1), np.uint32)
-    n = L.zcg_regions_s_waves(ctypes.byref(r), offs.ctypes.data, shp.ctypes.data, stp.ctypes.data, B,
-                              wave_of.ctypes.data)
-    return int(n), [int(w) for w in wave_of[:B]]
+    return _waves("zcg_regions_s_waves", meta, [0] * meta.get_ndim(), offsets, shapes, steps)
 
 
 def _steps_arg(steps, B: int, nd: int) -> np.ndarray:
@@ -709,45 +691,7 @@ def read_ndarrays_s(hier, path_name: str, meta: ArrayMetadata, boxes: Sequence[B
     sample are read and decoded, each once.  With as_tensor the result is what
     read_ndarrays_v returns: (uint8 device tensor of the boxes back to back,
     byte offset per box, element strides per box)."""
-    check_array_type(t, meta)
-    nd = meta.get_ndim()
-    for bb in boxes:
-        if len(bb.offset) != nd:
-            raise ZarrIOError("InvalidData", "Wrong number of dimensions")
-    B = len(boxes)
-    stp = _steps_arg(steps, B, nd)
-    import torch
-    dt = np.dtype(t).newbyteorder("=")
-    es = dt.itemsize
-    order = "F" if meta.chunk_memory_layout == "F" else "C"
-    offs = np.ascontiguousarray(np.array([bb.offset for bb in boxes], dtype=np.uint64).reshape(-1, nd))
-    shp = np.ascontiguousarray(np.array([bb.shape for bb in boxes], dtype=np.uint64).reshape(-1, nd))
-    strides = [_strides(bb.shape, order) for bb in boxes]
-    at = [0]
-    for bb in boxes:
-        at.append(at[-1] + int(np.prod(bb.shape, dtype=object)) * es)
-    am = _native_meta(meta, flags)
-    ctx = _native.context(device)
-    root, path = os.fsencode(hier.base_path), path_name.encode()
-    if as_tensor:
-        out = torch.empty(max(at[-1], 1), dtype=torch.uint8, device=torch.device("cuda", device))
-        outs = (ctypes.c_void_p * max(B, 1))(*[out.data_ptr() + at[b] for b in range(B)])
-        r = ctx.lib.zcg_store_read_boxes_s_device(ctx.handle, ctypes.byref(am), root, path, shp.ctypes.data,
-                                                  stp.ctypes.data, None, 1, offs.ctypes.data, ctypes.addressof(outs),
-                                                  B, slot_budget_bytes, 16)
-    else:
-        host = np.empty(max(at[-1], 1), np.uint8)
-        outs = (ctypes.c_void_p * max(B, 1))(*[host.ctypes.data + at[b] for b in range(B)])
-        r = ctx.lib.zcg_store_read_boxes_s(ctx.handle, ctypes.byref(am), root, path, shp.ctypes.data,
-                                           stp.ctypes.data, offs.ctypes.data, ctypes.addressof(outs), B,
-                                           slot_budget_bytes, 16)
-    if r != _native.OK:
-        raise ZarrIOError(_native.STATUS_NAMES.get(r, str(r)), f"read_boxes: {ctx.last_error()}")
-    if as_tensor:
-        return out[: at[-1]], at[:-1], strides
-    return [np.ndarray(tuple(bb.shape), dtype=dt, buffer=host, offset=at[b],
-                       strides=tuple(s * es for s in strides[b])).copy(order=order)
-            for b, bb in enumerate(boxes)]
+    return _read_boxes(hier, path_name, meta, boxes, steps, t, device, as_tensor, flags, slot_budget_bytes)
 
 
 def _check_hulls(meta: ArrayMetadata, shp: np.ndarray, stp: np.ndarray) -> None:
@@ -776,14 +720,12 @@ def write_ndarrays_s(hier, path_name: str, meta: ArrayMetadata, offsets, steps, 
     read first."""
     nd = meta.get_ndim()
     arrays = list(arrays)
-    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64).reshape(-1, nd))
+    offs = _u64(offsets, nd)
     B = offs.shape[0]
     if len(arrays) != B:
         raise ZarrIOError("InvalidData", "Bounding boxes and arrays differ in number")
     stp = _steps_arg(steps, B, nd)
     tensor_in = B > 0 and all(not isinstance(a, np.ndarray) and hasattr(a, "data_ptr") for a in arrays)
-    order = "F" if meta.chunk_memory_layout == "F" else "C"
-    root, path = os.fsencode(hier.base_path), path_name.encode()
     if tensor_in:
         dt = np.dtype(meta.effective_type().numpy_dtype()).newbyteorder("=")
         check_array_type(dt, meta)
@@ -792,35 +734,17 @@ def write_ndarrays_s(hier, path_name: str, meta: ArrayMetadata, offsets, steps, 
                 raise ZarrIOError("InvalidData", "Wrong number of dimensions")
             if a.element_size() != dt.itemsize:
                 raise ZarrIOError("InvalidData", "Tensor and array differ in their element size")
-        shp = np.ascontiguousarray(np.array([list(a.shape) for a in arrays], dtype=np.uint64).reshape(-1, nd))
+        shp = _u64([list(a.shape) for a in arrays], nd)
         istr = np.ascontiguousarray(np.array([list(a.stride()) for a in arrays], dtype=np.int64).reshape(-1, nd))
-        _check_hulls(meta, shp, stp)
-        am = _native_meta(meta, flags)
-        ctx = _native.context(device)
         ins = (ctypes.c_void_p * max(B, 1))(*[a.data_ptr() for a in arrays])
-        r = ctx.lib.zcg_store_write_boxes_s_device(ctx.handle, ctypes.byref(am), root, path, shp.ctypes.data,
-                                                   stp.ctypes.data, istr.ctypes.data, offs.ctypes.data,
-                                                   ctypes.addressof(ins), B, slot_budget_bytes, 16)
+        name, views = "zcg_store_write_boxes_s_device", [istr.ctypes.data]
     else:
-        arrays = [np.asarray(a) for a in arrays]
-        dense = []
-        for a in arrays:
-            if a.ndim != nd:
-                raise ZarrIOError("InvalidData", "Wrong number of dimensions")
-            dt = a.dtype.newbyteorder("=")
-            check_array_type(dt, meta)
-            # dense in the chunk memory order
-            dense.append(np.ascontiguousarray(a.astype(dt, copy=False).T if order == "F" else a.astype(dt, copy=False)))
-        shp = np.ascontiguousarray(np.array([a.shape for a in arrays], dtype=np.uint64).reshape(-1, nd))
-        _check_hulls(meta, shp, stp)
-        am = _native_meta(meta, flags)
-        ctx = _native.context(device)
-        ins = (ctypes.c_void_p * max(B, 1))(*[a.ctypes.data if a.size else 0 for a in dense])
-        r = ctx.lib.zcg_store_write_boxes_s(ctx.handle, ctypes.byref(am), root, path, shp.ctypes.data,
-                                            stp.ctypes.data, offs.ctypes.data, ctypes.addressof(ins), B,
-                                            slot_budget_bytes, 16)
-    if r != _native.OK:
-        raise ZarrIOError(_native.STATUS_NAMES.get(r, str(r)), f"write_boxes: {ctx.last_error()}")
+        dense, shp, ins = _dense_inputs(meta, arrays)
+        name, views = "zcg_store_write_boxes_s", []
+    _check_hulls(meta, shp, stp)
+    _StoreCall(hier, path_name, meta, flags, device)(
+        "write_boxes", name, shp.ctypes.data, stp.ctypes.data, *views, offs.ctypes.data, ctypes.addressof(ins), B,
+        slot_budget_bytes, 16)
 
 
 def read_ndarray_into(hier, path_name: str, meta: ArrayMetadata, bbox: BoundingBox, arr: np.ndarray, t,
@@ -954,14 +878,8 @@ def _coords_arg(coords, nd: int) -> np.ndarray:
 def points_grid(meta: ArrayMetadata, coords):
     """zcg_points_grid (host code, no GPU): the smallest grid range that holds
     every chunk a point visits -> (lo, n); regions_v_grid with shapes all 1."""
-    L = _native.load_library()
     nd = meta.get_ndim()
-    r = _region(meta, BoundingBox([0] * nd, [1] * nd), 1, False, 0, [0] * nd)
-    c = _coords_arg(coords, nd)
-    lo = (ctypes.c_uint64 * _native.MAX_DIMS)()
-    n = (ctypes.c_uint64 * _native.MAX_DIMS)()
-    L.zcg_points_grid(ctypes.byref(r), c.ctypes.data, c.shape[0], ctypes.addressof(lo), ctypes.addressof(n))
-    return [int(lo[d]) for d in range(nd)], [int(n[d]) for d in range(nd)]
+    return _grid("zcg_points_grid", meta, [1] * nd, _coords_arg(coords, nd))
 
 
 def points_last(coords) -> np.ndarray:
@@ -1025,22 +943,15 @@ def read_points(hier, path_name: str, meta: ArrayMetadata, coords, t, device: in
     c = _coords_arg(coords, nd)
     P = c.shape[0]
     dt = np.dtype(t).newbyteorder("=")
-    am = _native_meta(meta, flags)
-    ctx = _native.context(device)
-    root, path = os.fsencode(hier.base_path), path_name.encode()
+    call = _StoreCall(hier, path_name, meta, flags, device)
     threads = io_threads or 16
     if as_tensor:
         out = torch.empty(max(P, 1) * dt.itemsize, dtype=torch.uint8, device=torch.device("cuda", device))
-        r = ctx.lib.zcg_store_read_points_device(ctx.handle, ctypes.byref(am), root, path, c.ctypes.data, P, 1,
-                                                 out.data_ptr(), slot_budget_bytes, threads)
-    else:
-        host = np.empty(max(P, 1), dt)
-        r = ctx.lib.zcg_store_read_points(ctx.handle, ctypes.byref(am), root, path, c.ctypes.data, P,
-                                          host.ctypes.data, slot_budget_bytes, threads)
-    if r != _native.OK:
-        raise ZarrIOError(_native.STATUS_NAMES.get(r, str(r)), f"read_points: {ctx.last_error()}")
-    if as_tensor:
+        call("read_points", "zcg_store_read_points_device", c.ctypes.data, P, 1, out.data_ptr(), slot_budget_bytes,
+             threads)
         return out[: P * dt.itemsize].view(getattr(torch, dt.name)) if hasattr(torch, dt.name) else out[: P * dt.itemsize]
+    host = np.empty(max(P, 1), dt)
+    call("read_points", "zcg_store_read_points", c.ctypes.data, P, host.ctypes.data, slot_budget_bytes, threads)
     return host[:P]
 
 
@@ -1055,18 +966,16 @@ def write_points(hier, path_name: str, meta: ArrayMetadata, coords, values, devi
     nd = meta.get_ndim()
     c = _coords_arg(coords, nd)
     P = c.shape[0]
-    am = _native_meta(meta, flags)
-    ctx = _native.context(device)
-    root, path = os.fsencode(hier.base_path), path_name.encode()
+    call = _StoreCall(hier, path_name, meta, flags, device)
     threads = io_threads or 16
     if hasattr(values, "data_ptr"):
         if values.numel() != P:
             raise ZarrIOError("InvalidData", "Coordinates and values differ in number")
         v = values.contiguous()
-        if v.element_size() != am.array.dtype.elem_size:
+        if v.element_size() != call.am.array.dtype.elem_size:
             raise ZarrIOError("InvalidData", "Element size differs from the array's")
-        r = ctx.lib.zcg_store_write_points_device(ctx.handle, ctypes.byref(am), root, path, c.ctypes.data, P,
-                                                  v.data_ptr(), slot_budget_bytes, threads)
+        call("write_points", "zcg_store_write_points_device", c.ctypes.data, P, v.data_ptr(), slot_budget_bytes,
+             threads)
     else:
         a = np.asarray(values).reshape(-1)
         if a.shape[0] != P:
@@ -1074,7 +983,5 @@ def write_points(hier, path_name: str, meta: ArrayMetadata, coords, values, devi
         dt = a.dtype.newbyteorder("=")
         check_array_type(dt, meta)
         a = np.ascontiguousarray(a.astype(dt, copy=False))
-        r = ctx.lib.zcg_store_write_points(ctx.handle, ctypes.byref(am), root, path, c.ctypes.data, P,
-                                           a.ctypes.data if P else None, slot_budget_bytes, threads)
-    if r != _native.OK:
-        raise ZarrIOError(_native.STATUS_NAMES.get(r, str(r)), f"write_points: {ctx.last_error()}")
+        call("write_points", "zcg_store_write_points", c.ctypes.data, P, a.ctypes.data if P else None,
+             slot_budget_bytes, threads)
