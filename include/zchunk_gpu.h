@@ -722,6 +722,85 @@ int zcg_write_points(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo
                      void* const* d_chunk_table, const uint64_t* d_coords, uint64_t n_points,
                      const void* d_in, uint64_t* d_first_outside, void* stream);
 
+/* ---- an orthogonal selection: one index list per dimension -----------------
+ * numpy's a[np.ix_(rows, cols, planes)], zarr's oindex: the result is the
+ * Cartesian product of the lists.  ELEMENT (i_0, .., i_{n-1}) OF THE SELECTION
+ * IS THE POINT (L_0[i_0], .., L_{n-1}[i_{n-1}]) OF zcg_read_points /
+ * zcg_write_points, BIT FOR BIT: the visit rule, the overhang of edge chunks,
+ * fill versus untouched, NULL table entries, any uint64_t index.  What differs
+ * is the cost: sum(count) divisions instead of prod(count) * ndim, and no
+ * coordinate array.
+ *
+ * `r` gives what it gives the point calls (ndim, elem_size, chunk_order,
+ * fill_missing, fill_value, array_shape, chunk_shape); its other fields are
+ * ignored.  The table arguments are zcg_read_regions'.
+ *
+ * zcg_osel is a HOST struct.  index[d] is a DEVICE array of count[d] array
+ * indices along dimension d, in any order, with or without duplicates; the
+ * counts are host-known and size the launch.  Element (i_0, .., i_{n-1}) is at
+ * base + sum(i_d * strides[d]) elements of the DEVICE view (any strides,
+ * negative ones included).
+ *
+ * Host code, no GPU and no context:
+ *  - zcg_ortho_chunks mirrors zcg_region_s_chunks.  lists[d] is a HOST array of
+ *    count[d] indices.  lo / n receive the smallest grid range that holds every
+ *    visited chunk, per dimension; if some dimension has no visiting index
+ *    (an empty list included) all of them are 0 and so is the return value.
+ *    touched (may be NULL) is dimension-major, n[0] + .. + n[ndim-1] bytes:
+ *    1 where grid index lo[d] + j holds a visiting index of list d.  Returns
+ *    the number of touched chunks, the product of the per-dimension touched
+ *    counts (saturating).  lo and n equal zcg_points_grid's on the expanded
+ *    product.
+ *  - zcg_ortho_scratch_bytes: the device working memory of one call (a record
+ *    per list entry); a multiple of 256, non-decreasing in every count.
+ *
+ * The device calls:
+ *  - zcg_read_ortho writes exactly the elements of the view that
+ *    zcg_read_points would write for the expanded product: the chunk's element,
+ *    or fill_value with fill_missing set where the chunk is NULL or the point
+ *    visits none; with fill_missing clear such an element is untouched.  No
+ *    other byte of the view is written.
+ *  - zcg_write_ortho stores whole elements only, into chunks that are visited,
+ *    inside the table and not NULL.  With duplicate indices in a list one value
+ *    wins whole, which one is unspecified: drop the earlier duplicates per list
+ *    with zcg_points_last(list, count, 1, keep).  The view is only read.
+ *  - d_outside is a DEVICE array of ndim words.  The table is a product range,
+ *    so a chunk index outside it is a property of one list entry: word d ends
+ *    up as the lowest position in list d whose index visits (along d: it is
+ *    below array_shape[d] or no multiple of chunk_shape[d]) a grid index
+ *    outside table_lo[d] .. table_lo[d] + table_n[d], UINT64_MAX if there is
+ *    none.  An element is skipped (neither read nor written, no fill) exactly
+ *    when the point call skips its point: it visits a chunk, and that chunk is
+ *    outside the table along some dimension.  The words are reset on the stream
+ *    by a device-to-device copy from words the context owns, as
+ *    *d_first_outside is.
+ *  - A zero count returns ZCG_OK; nothing is launched and d_outside is not
+ *    written.  Argument errors are the point calls'; a NULL sel, list, base,
+ *    scratch or d_outside returns ZCG_ERR_INVALID_INPUT, and so does a
+ *    d_scratch that is not 16-byte aligned (the kernels read a record with
+ *    two 16-byte loads).  count[d] >= 2^32 or prod(count) >= 2^60 returns
+ *    ZCG_ERR_UNSUPPORTED.
+ *  - Asynchronous on `stream`: the reset and two kernel launches, whatever the
+ *    counts are.  The call allocates nothing and does not synchronize with the
+ *    host.  The lists are read when the kernels run, so a captured call replays
+ *    with new indices; the counts, strides and base are baked in. */
+typedef struct zcg_osel {
+    const uint64_t* index[ZCG_MAX_DIMS];  /* DEVICE: count[d] array indices along dim d */
+    uint64_t count[ZCG_MAX_DIMS];         /* host-known; sizes the launch               */
+    int64_t  strides[ZCG_MAX_DIMS];       /* the view's strides per array dim, elements */
+    void*    base;                        /* DEVICE element (0,..,0) of the view        */
+} zcg_osel;
+
+uint64_t zcg_ortho_chunks(const zcg_region* r, const uint64_t* const* lists, const uint64_t* count,
+                          uint64_t* lo, uint64_t* n, uint8_t* touched);
+uint64_t zcg_ortho_scratch_bytes(uint32_t ndim, const uint64_t* count);
+int zcg_read_ortho(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+                   const void* const* d_chunk_table, const zcg_osel* sel,
+                   void* d_scratch, uint64_t* d_outside, void* stream);
+int zcg_write_ortho(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+                    void* const* d_chunk_table, const zcg_osel* sel,
+                    void* d_scratch, uint64_t* d_outside, void* stream);
+
 /* ---- FilesystemHierarchy chunk files ---------------
  * The e2e path's two ends: chunk files read into pinned staging by a pool of
  * `io_threads` host threads (open + shared flock + read, as ReadableStore::get,
@@ -1073,6 +1152,55 @@ int zcg_store_write_points_device(zcg_ctx* ctx, const zcg_array_meta* meta, cons
 int zcg_store_write_points(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
                            const uint64_t* coords, uint64_t n_points, const void* in, uint64_t slot_budget_bytes,
                            uint32_t io_threads);
+
+/* ---- an orthogonal selection against the store -------------------------------
+ * The point store calls on the Cartesian product of `lists` (HOST: lists[d]
+ * holds count[d] indices along dimension d) in C order, without the product:
+ * the values are one dense array of prod(count) elements, C order over the
+ * positions in the lists, dimension 0 slowest, whatever the chunk order is.
+ *  - Plan: every list is sorted by chunk index, index and position, which costs
+ *    the sum of the lists, never the product.  The touched chunks are the
+ *    product of the per-dimension sets of visited grid indices
+ *    (zcg_ortho_chunks); only those files are opened, and each is decoded once
+ *    in the whole call.
+ *  - Groups are sub-products of runs of the sorted lists, and a chunk belongs
+ *    to one group: the longest suffix of dimensions whose touched grid indices
+ *    fit slot_budget_bytes (0: 4 GiB) is taken whole, the dimension before it
+ *    is cut into runs that fit, and the dimensions before that go one touched
+ *    grid index at a time.  A read's run of indices that visit no chunk counts
+ *    as one more grid index of its list here, so a group may hold one chunk
+ *    fewer than the budget allows.  A group's table is the bounding grid range of its
+ *    chunks (more than 2^24 entries -> ZCG_ERR_UNSUPPORTED); one zcg_read_ortho
+ *    / zcg_write_ortho launch per group.  A read's indices that visit no chunk
+ *    form a last run of their list and receive the fill value.
+ *  - Errors, absent files (NULL entries), the decode and verify flags of
+ *    `meta`, the dtype and ndim checks are the point calls'.  Before any file is
+ *    touched: an index whose chunk is beyond the array's grid returns
+ *    ZCG_ERR_INVALID_INPUT, and zcg_last_error names dimension and position.
+ *  - Read: the host call fills elements without a chunk with the fill value;
+ *    the device call does so with fill_missing set and leaves them untouched
+ *    otherwise.
+ *  - Write: the store ends up as after zcg_store_write_points on the product in
+ *    C order, so per list the last occurrence of an index wins, and indices
+ *    that visit no chunk are dropped.  Touched chunks are read first, except
+ *    those the selection covers entirely; an absent one starts as the fill
+ *    value.  Each touched chunk is encoded and written once; nothing else is
+ *    opened, created or rewritten.
+ *  - A zero count returns ZCG_OK.  count[d] >= 2^32 or 2^60 bytes of values and
+ *    more -> ZCG_ERR_UNSUPPORTED.  The host calls pass the values through one
+ *    device array of the selection's size. */
+int zcg_store_read_ortho_device(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                                const uint64_t* const* lists, const uint64_t* count, uint32_t fill_missing,
+                                void* d_out, uint64_t slot_budget_bytes, uint32_t io_threads);
+int zcg_store_read_ortho(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                         const uint64_t* const* lists, const uint64_t* count, void* out,
+                         uint64_t slot_budget_bytes, uint32_t io_threads);
+int zcg_store_write_ortho_device(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                                 const uint64_t* const* lists, const uint64_t* count, const void* d_in,
+                                 uint64_t slot_budget_bytes, uint32_t io_threads);
+int zcg_store_write_ortho(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                          const uint64_t* const* lists, const uint64_t* count, const void* in,
+                          uint64_t slot_budget_bytes, uint32_t io_threads);
 
 #ifdef __cplusplus
 }

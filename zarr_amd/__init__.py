@@ -13,11 +13,12 @@ from .metadata import ArrayMetadata, u64_ceil_div
 from .chunk import (DefaultChunk, SliceDataChunk, VecDataChunk, ZarrIOError, check_array_type,
                     read_chunks_host)
 from .storage import FilesystemHierarchy, get_chunk_key
-from .region import (BoundingBox, assemble_points, assemble_regions_s, points_grid, points_last, read_ndarray,
+from .region import (BoundingBox, assemble_ortho, assemble_points, assemble_regions_s, points_grid, points_last, read_ndarray,
                      read_ndarrays, read_ndarrays_s, read_ndarrays_v, read_points,
                      region_s_chunks, regions_s_grid, regions_s_scratch_bytes, regions_s_waves, sboxes_tensor,
                      scatter_points, scatter_regions_s, write_ndarray, write_ndarrays, write_ndarrays_s,
-                     write_ndarrays_v, write_points)
+                     write_ndarrays_v, write_points, ortho_chunks, ortho_scratch_bytes, read_ortho,
+                     scatter_ortho, write_ortho)
 from ._native import NativeUnavailable
 
 __all__ = [
@@ -30,4 +31,5 @@ __all__ = [
     "scatter_regions_s", "u64_ceil_div", "write_ndarray", "write_ndarrays", "write_ndarrays_s", "write_ndarrays_v",
     "zarr_type",
     "assemble_points", "points_grid", "points_last", "read_points", "scatter_points", "write_points",
+    "assemble_ortho", "ortho_chunks", "ortho_scratch_bytes", "read_ortho", "scatter_ortho", "write_ortho",
 ]

@@ -62,6 +62,9 @@ EXPORTED_SYMBOLS = (
     "zcg_points_grid", "zcg_points_last", "zcg_read_points", "zcg_write_points",
     "zcg_store_read_points_device", "zcg_store_read_points",
     "zcg_store_write_points_device", "zcg_store_write_points",
+    "zcg_ortho_chunks", "zcg_ortho_scratch_bytes", "zcg_read_ortho", "zcg_write_ortho",
+    "zcg_store_read_ortho_device", "zcg_store_read_ortho",
+    "zcg_store_write_ortho_device", "zcg_store_write_ortho",
 )
 
 
@@ -121,6 +124,13 @@ class SBox(ctypes.Structure):
                 ("base", ctypes.c_void_p)]
 
 
+class OSel(ctypes.Structure):
+    """zcg_osel: an orthogonal selection (per array dim a DEVICE index list, its length and the view's stride;
+    DEVICE base of the view).  A host struct."""
+    _fields_ = [("index", ctypes.c_void_p * MAX_DIMS), ("count", ctypes.c_uint64 * MAX_DIMS),
+                ("strides", ctypes.c_int64 * MAX_DIMS), ("base", ctypes.c_void_p)]
+
+
 class ArrayMeta(ctypes.Structure):
     _fields_ = [("array", Array), ("ndim", ctypes.c_uint32), ("chunk_ndim", ctypes.c_uint32),
                 ("chunk_order", ctypes.c_uint32), ("dtype_kind", ctypes.c_uint32),
@@ -136,6 +146,7 @@ assert ctypes.sizeof(Chunk) == 32
 assert ctypes.sizeof(Box) == 8 * MAX_DIMS + 8
 assert ctypes.sizeof(VBox) == 3 * 8 * MAX_DIMS + 8
 assert ctypes.sizeof(SBox) == 4 * 8 * MAX_DIMS + 8
+assert ctypes.sizeof(OSel) == 3 * 8 * MAX_DIMS + 8
 
 _lib = None
 _lock = threading.Lock()
@@ -305,6 +316,26 @@ def load_library(path: str = LIB_PATH):
         L.zcg_store_write_points.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
                                              vp, u64, vp, u64, u32]
         L.zcg_store_write_points.restype = ctypes.c_int
+        L.zcg_ortho_chunks.argtypes = [ctypes.POINTER(Region), vp, vp, vp, vp, vp]
+        L.zcg_ortho_chunks.restype = u64
+        L.zcg_ortho_scratch_bytes.argtypes = [u32, vp]
+        L.zcg_ortho_scratch_bytes.restype = u64
+        L.zcg_read_ortho.argtypes = [vp, ctypes.POINTER(Region), vp, vp, vp, vp, vp, vp, vp]
+        L.zcg_read_ortho.restype = ctypes.c_int
+        L.zcg_write_ortho.argtypes = [vp, ctypes.POINTER(Region), vp, vp, vp, vp, vp, vp, vp]
+        L.zcg_write_ortho.restype = ctypes.c_int
+        L.zcg_store_read_ortho_device.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
+                                                  vp, vp, u32, vp, u64, u32]
+        L.zcg_store_read_ortho_device.restype = ctypes.c_int
+        L.zcg_store_read_ortho.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
+                                           vp, vp, vp, u64, u32]
+        L.zcg_store_read_ortho.restype = ctypes.c_int
+        L.zcg_store_write_ortho_device.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
+                                                   vp, vp, vp, u64, u32]
+        L.zcg_store_write_ortho_device.restype = ctypes.c_int
+        L.zcg_store_write_ortho.argtypes = [vp, ctypes.POINTER(ArrayMeta), ctypes.c_char_p, ctypes.c_char_p,
+                                            vp, vp, vp, u64, u32]
+        L.zcg_store_write_ortho.restype = ctypes.c_int
         _lib = L
         return L
 

@@ -47,8 +47,9 @@ struct zcg_ctx {
     size_t h_pin_bytes = 0;
     // store pipeline slots (zcg_store.cpp), created on first use
     zcg_store_slots* store = nullptr;
-    // one device word holding UINT64_MAX: the source of the point calls' reset of
-    // *d_first_outside (a copy, not a memset: see launch_points)
+    // ZCG_MAX_DIMS device words holding UINT64_MAX: the source of the point calls'
+    // reset of *d_first_outside and of the ortho calls' reset of d_outside (a copy,
+    // not a memset: see launch_points)
     uint64_t* d_all_ones = nullptr;
 };
 
@@ -219,8 +220,8 @@ zcg_ctx* zcg_create(int device) {
         delete ctx;
         return nullptr;
     }
-    if (hipMalloc((void**)&ctx->d_all_ones, sizeof(uint64_t)) != hipSuccess ||
-        hipMemset(ctx->d_all_ones, 0xFF, sizeof(uint64_t)) != hipSuccess) {
+    if (hipMalloc((void**)&ctx->d_all_ones, ZCG_MAX_DIMS * sizeof(uint64_t)) != hipSuccess ||
+        hipMemset(ctx->d_all_ones, 0xFF, ZCG_MAX_DIMS * sizeof(uint64_t)) != hipSuccess) {
         zcg_destroy(ctx);
         return nullptr;
     }
@@ -908,4 +909,146 @@ extern "C" int zcg_write_points(zcg_ctx* ctx, const zcg_region* r, const uint64_
                                 const void* d_in, uint64_t* d_first_outside, void* stream) {
     return zcg::points_call(ctx, r, table_lo, table_n, (const void* const*)d_chunk_table, d_coords, nullptr, n_points,
                             (void*)d_in, d_first_outside, stream, 1);
+}
+
+// ---- an index list per dimension (zcg_region_o.hip) -------------------------
+// Element (i_0, .., i_{n-1}) of the selection is the point (L_0[i_0], ..,
+// L_{n-1}[i_{n-1}]), so whether an entry visits a chunk is the point rule along
+// its dimension (points_kernel), and the touched chunks are the product of the
+// per-dimension sets of visited grid indices.
+extern "C" uint64_t zcg_ortho_chunks(const zcg_region* r, const uint64_t* const* lists, const uint64_t* count,
+                                     uint64_t* lo, uint64_t* n, uint8_t* touched) {
+    if (!r || r->ndim < 1 || r->ndim > ZCG_MAX_DIMS || !lists || !count) return 0;
+    const uint32_t nd = r->ndim;
+    uint64_t glo[ZCG_MAX_DIMS], ghi[ZCG_MAX_DIMS];
+    bool every = true;
+    for (uint32_t d = 0; d < nd; d++) {
+        const uint64_t cs = r->chunk_shape[d] ? r->chunk_shape[d] : 1;
+        bool any = false;
+        for (uint64_t i = 0; i < count[d] && lists[d]; i++) {
+            const uint64_t c = lists[d][i], q = c / cs;
+            if (!(c < r->array_shape[d] || c % cs)) continue;
+            glo[d] = any ? std::min(glo[d], q) : q;
+            ghi[d] = any ? std::max(ghi[d], q) : q;
+            any = true;
+        }
+        every &= any;
+    }
+    unsigned __int128 cnt = every ? 1 : 0;
+    for (uint32_t d = 0; d < nd; d++) {
+        const uint64_t gn = every ? ghi[d] - glo[d] + 1 : 0;
+        if (lo) lo[d] = every ? glo[d] : 0;
+        if (n) n[d] = gn;
+        if (!every) continue;
+        const uint64_t cs = r->chunk_shape[d] ? r->chunk_shape[d] : 1;
+        uint64_t hit = 0;
+        if (touched) {
+            memset(touched, 0, (size_t)gn);
+            for (uint64_t i = 0; i < count[d]; i++) {
+                const uint64_t c = lists[d][i];
+                if (!(c < r->array_shape[d] || c % cs)) continue;
+                hit += touched[c / cs - glo[d]] ? 0 : 1;
+                touched[c / cs - glo[d]] = 1;
+            }
+            touched += gn;
+        } else {  // the distinct grid indices, without the flags' memory
+            std::vector<uint64_t> qs;
+            for (uint64_t i = 0; i < count[d]; i++)
+                if (lists[d][i] < r->array_shape[d] || lists[d][i] % cs) qs.push_back(lists[d][i] / cs);
+            std::sort(qs.begin(), qs.end());
+            hit = (uint64_t)(std::unique(qs.begin(), qs.end()) - qs.begin());
+        }
+        cnt *= hit;
+        if (cnt > ~0ull) cnt = ~0ull;
+    }
+    return (uint64_t)cnt;
+}
+
+extern "C" uint64_t zcg_ortho_scratch_bytes(uint32_t ndim, const uint64_t* count) {
+    unsigned __int128 sum = 0;
+    for (uint32_t d = 0; count && d < ndim && d < ZCG_MAX_DIMS; d++) sum += count[d];
+    sum = sum * zcg::ORTHO_REC_BYTES + 255;
+    return sum > ~0ull ? ~0ull & ~255ull : (uint64_t)sum & ~255ull;
+}
+
+namespace zcg {
+// zcg_read_ortho (dir 0) and zcg_write_ortho (dir 1); d_pos (per array dim a
+// DEVICE array of count[d] positions, or NULL; d_pos itself may be NULL) places
+// entry i of list d at position d_pos[d][i] of the view along d: the store
+// calls hand the kernels sorted lists without duplicates (zcg_boxes.cpp).
+int ortho_call(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+               const void* const* d_chunk_table, const zcg_osel* sel, const uint64_t* const* d_pos, void* d_scratch,
+               uint64_t* d_outside, void* stream, uint32_t dir) {
+    const int head = region_head(ctx, r);
+    if (head != ZCG_OK) return head;
+    if (!sel) return ZCG_ERR_INVALID_INPUT;
+    const uint32_t nd = r->ndim;
+    for (uint32_t d = 0; d < nd; d++)
+        if (sel->count[d] == 0) return ZCG_OK;
+    zcg_region one = *r;  // bbox_* and out_strides are ignored
+    for (uint32_t d = 0; d < nd; d++) one.bbox_shape[d] = 1;
+    RegionWalk w;
+    uint64_t entries;
+    const int rc = region_walk(ctx, &one, nullptr, table_n, "ortho: chunk extent must stay below 2^32 elements", &w,
+                               &entries);
+    if (rc != ZCG_OK) return rc;
+    if (dir) w.fill = 0;
+    if (!sel->base || !d_scratch || ((uintptr_t)d_scratch & 15) || !d_outside || (entries && !d_chunk_table))
+        return ZCG_ERR_INVALID_INPUT;
+    for (uint32_t d = 0; d < nd; d++)
+        if (!sel->index[d]) return ZCG_ERR_INVALID_INPUT;
+    uint64_t total = 1;
+    for (uint32_t d = 0; d < nd; d++) {
+        if (sel->count[d] >= (1ull << 32)) {
+            ctx->err = "ortho: a list must hold fewer than 2^32 indices";
+            return ZCG_ERR_UNSUPPORTED;
+        }
+        total = total >= (1ull << 60) / sel->count[d] + 1 ? 1ull << 60 : total * sel->count[d];
+    }
+    if (total >= (1ull << 60)) {
+        ctx->err = "ortho: the selection must hold fewer than 2^60 elements";
+        return ZCG_ERR_UNSUPPORTED;
+    }
+    BoxTable bt{};
+    PointRecip pr{}, pcount{};
+    OrthoAxes ax{};
+    auto recip = [](uint64_t x) { return x > 1 ? ~0ull / x + 1 : 0; };  // ceil(2^64 / x)
+    uint64_t rows = 1;
+    for (uint32_t k = 0; k < nd; k++) {
+        const uint32_t d = region_dim(r, k);
+        bt.dim[k] = d;
+        bt.as[k] = r->array_shape[d];
+        bt.tlo[k] = table_lo ? table_lo[d] : 0;
+        bt.tn[k] = table_n ? table_n[d] : 0;
+        pr.m[k] = recip(w.cs[k]);
+        w.bs[k] = (uint32_t)sel->count[d];
+        w.ostr[k] = sel->strides[d];
+        pcount.m[k] = recip(w.bs[k]);
+        ax.off[k + 1] = ax.off[k] + sel->count[d];
+        ax.idx[k] = sel->index[d];
+        ax.pos[k] = d_pos ? d_pos[d] : nullptr;
+        if (k) rows *= sel->count[d];
+    }
+    ax.ppr = (uint32_t)((w.bs[0] + (uint64_t)w.V - 1) / w.V);
+    ax.mppr = recip(ax.ppr);
+    w.total = rows * ax.ppr;
+    (void)hipSetDevice(ctx->device);
+    const hipError_t e = launch_ortho(w, bt, pr, pcount, ax, d_chunk_table, sel->base, d_scratch, d_outside,
+                                      ctx->d_all_ones, dir, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ctx, e, "ortho launch");
+    return ZCG_OK;
+}
+}  // namespace zcg
+
+extern "C" int zcg_read_ortho(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+                              const void* const* d_chunk_table, const zcg_osel* sel, void* d_scratch,
+                              uint64_t* d_outside, void* stream) {
+    return zcg::ortho_call(ctx, r, table_lo, table_n, d_chunk_table, sel, nullptr, d_scratch, d_outside, stream, 0);
+}
+
+extern "C" int zcg_write_ortho(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+                               void* const* d_chunk_table, const zcg_osel* sel, void* d_scratch, uint64_t* d_outside,
+                               void* stream) {
+    return zcg::ortho_call(ctx, r, table_lo, table_n, (const void* const*)d_chunk_table, sel, nullptr, d_scratch,
+                           d_outside, stream, 1);
 }

@@ -10,7 +10,9 @@
 // (a chunk two groups share is decoded in each), each group with its union
 // table range.  A strided box's chunks (the _s calls) are the touched ones
 // (zcg_region_s_chunks), not the hull's whole grid range; points are sorted by
-// chunk first, so a group is a run of sorted points.
+// chunk first, so a group is a run of sorted points.  plan_ortho sorts every
+// list of an orthogonal selection by itself; its groups are sub-products of
+// runs of the sorted lists, so no chunk is shared between two groups.
 //
 // Driver.  run_groups is the per-group loop, once for both directions and both
 // kinds of item.  It owns the stream, the group's slots and chunk files, which
@@ -42,6 +44,11 @@
 //                  word].  One launch (zcg_region_p.hip); a device caller's
 //                  values stay in the caller's order through the index array,
 //                  host values are permuted on the host.
+//   OrthoPayload:  [indices, per dimension][their positions][scratch of the
+//                  kernels][outside words].  One launch (zcg_region_o.hip) for
+//                  the group's runs of the sorted lists; the values stay in the
+//                  caller's order through the positions, a host caller's in
+//                  one device array for the whole call.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1146,4 +1153,326 @@ extern "C" int zcg_store_write_points(zcg_ctx* ctx, const zcg_array_meta* meta, 
                                       const uint64_t* coords, uint64_t n_points, const void* in,
                                       uint64_t slot_budget_bytes, uint32_t io_threads) {
     return run_points(ctx, meta, root, path, coords, n_points, 0, (void*)in, slot_budget_bytes, io_threads, true, true);
+}
+
+// ---- an index list per dimension --------------------------------------------
+// zcg_store_read_ortho / zcg_store_write_ortho: the point calls on the
+// Cartesian product of the lists, without the product.  Every list is sorted by
+// chunk index, index and position (the sum of the lists, never the product);
+// a CELL is the run of a sorted list that falls into one grid index, and the
+// touched chunks are the product of the per-dimension cells.  A group is a
+// sub-product of runs of cells, so a chunk belongs to one group and is decoded
+// once in the whole call.  The kernels (zcg_region_o.hip) get a group's runs of
+// the sorted lists with each entry's original position, and address the
+// caller's values, dense in C order over the positions, through them.
+namespace zcg {
+int ortho_call(zcg_ctx* ctx, const zcg_region* r, const uint64_t* table_lo, const uint64_t* table_n,
+               const void* const* d_chunk_table, const zcg_osel* sel, const uint64_t* const* d_pos, void* d_scratch,
+               uint64_t* d_outside, void* stream, uint32_t dir);
+}
+
+namespace {
+
+struct AxisEntry {
+    uint64_t q;  // grid index along the dimension; ~0: the index visits no chunk
+    uint64_t c;  // array index
+    uint64_t i;  // position in the caller's list
+};
+struct AxisCell {
+    uint64_t q;       // AxisEntry::q of the run
+    uint32_t e0, e1;  // the run in the sorted list
+    bool whole;       // write: every index of the chunk's nominal extent along the dimension is in the run
+};
+struct OrthoAxis {
+    std::vector<AxisEntry> ent;   // sorted by (q, c, i); the entries without a chunk last
+    std::vector<AxisCell> cells;  // ascending q
+};
+struct OrthoRange {
+    uint32_t c0[ZCG_MAX_DIMS], c1[ZCG_MAX_DIMS];  // per dimension: cells c0 .. c1
+};
+
+// plan_points for an index list per dimension.  Group::b0 indexes `ranges`.
+// write: per list the last occurrence of an index stays, and indices that
+// visit no chunk are dropped.
+int plan_ortho(zcg_ctx* ctx, const std::string& what, const zcg_array_meta* meta, const char* root, const char* path,
+               uint32_t fill_missing, const uint64_t* const* lists, const uint64_t* count, const void* buf, bool write,
+               uint64_t slot_budget_bytes, Plan& P, OrthoAxis* axes, std::vector<OrthoRange>& ranges) {
+    if (!count) return ZCG_ERR_INVALID_INPUT;
+    uint64_t some = 1;
+    for (uint32_t d = 0; meta && d < meta->ndim && d < ZCG_MAX_DIMS; d++)
+        if (count[d] == 0) some = 0;
+    const int hrc = plan_head(ctx, what, meta, root, path, lists, buf, some, "selections", fill_missing, P);
+    if (hrc != ZCG_OK || P.nothing) return hrc;
+    const uint32_t nd = P.nd;
+    uint64_t total = 1;
+    for (uint32_t d = 0; d < nd; d++) {
+        if (!lists[d]) return ZCG_ERR_INVALID_INPUT;
+        if (count[d] >= (1ull << 32)) {
+            ctx_set_error(ctx, what + ": a list must hold fewer than 2^32 indices");
+            return ZCG_ERR_UNSUPPORTED;
+        }
+        total = total >= (1ull << 60) / count[d] + 1 ? 1ull << 60 : total * count[d];
+    }
+    if (total >= (1ull << 60) / P.es) {
+        ctx_set_error(ctx, what + ": the selection holds 2^60 bytes or more");
+        return ZCG_ERR_UNSUPPORTED;
+    }
+    const int grc = plan_head_grid(ctx, what, slot_budget_bytes, P);
+    if (grc != ZCG_OK) return grc;
+    const zcg_region& r = P.r;
+
+    // every list: in-grid check (the reference panics at storage.rs:217), sort, cells
+    for (uint32_t d = 0; d < nd; d++) {
+        std::vector<AxisEntry>& ent = axes[d].ent;
+        const uint64_t cs = r.chunk_shape[d];
+        ent.reserve(count[d]);
+        for (uint64_t i = 0; i < count[d]; i++) {
+            const uint64_t c = lists[d][i];
+            const bool visits = c < r.array_shape[d] || c % cs;
+            if (visits && c / cs >= P.extent[d]) {
+                ctx_set_error(ctx, what + ": dimension " + std::to_string(d) + ", position " + std::to_string(i) +
+                                       ": index " + std::to_string(c) + " visits chunk " + std::to_string(c / cs) +
+                                       " outside the array's chunk grid");
+                return ZCG_ERR_INVALID_INPUT;
+            }
+            if (visits || !write) ent.push_back(AxisEntry{visits ? c / cs : ~0ull, c, i});
+        }
+    }
+    for (uint32_t d = 0; d < nd; d++) {
+        std::vector<AxisEntry>& ent = axes[d].ent;
+        std::sort(ent.begin(), ent.end(), [](const AxisEntry& a, const AxisEntry& b) {
+            return a.q != b.q ? a.q < b.q : a.c != b.c ? a.c < b.c : a.i < b.i;
+        });
+        if (write) {  // of the entries with one index the last position stays
+            size_t k = 0;
+            for (size_t s = 0; s < ent.size(); s++)
+                if (s + 1 == ent.size() || ent[s + 1].c != ent[s].c) ent[k++] = ent[s];
+            ent.resize(k);
+        }
+        if (ent.empty()) {  // write: no index of the list visits a chunk
+            P.nothing = true;
+            return ZCG_OK;
+        }
+        std::vector<AxisCell>& cells = axes[d].cells;
+        for (size_t s = 0; s < ent.size(); s++) {
+            if (cells.empty() || cells.back().q != ent[s].q) cells.push_back(AxisCell{ent[s].q, (uint32_t)s, 0, false});
+            cells.back().e1 = (uint32_t)s + 1;
+        }
+        // without duplicates, a run as long as the chunk extent holds every index of the chunk
+        for (AxisCell& c : cells) c.whole = write && c.e1 - c.e0 == r.chunk_shape[d];
+    }
+
+    // groups: the longest suffix of dimensions whose cells fit the budget is taken whole, the dimension
+    // before it in runs of cells that fit, the dimensions before that one cell at a time.  A read's last
+    // cell of entries without a chunk counts as a cell like the others: a group may then hold one
+    // chunk fewer than the budget allows, never more
+    const uint64_t max_chunks = std::max<uint64_t>(P.budget / std::max<uint64_t>(P.D, 1), 1);
+    uint64_t ncell[ZCG_MAX_DIMS], steps[ZCG_MAX_DIMS], suffix = 1, run = 1;
+    for (uint32_t d = 0; d < nd; d++) ncell[d] = axes[d].cells.size();
+    uint32_t j = nd;  // dimensions j .. nd-1 are whole
+    while (j > 0 && ncell[j - 1] <= max_chunks / suffix) suffix *= ncell[--j];
+    uint64_t ngroups = 1;
+    for (uint32_t d = 0; d < nd; d++) {
+        if (d + 1 == j) run = std::max<uint64_t>(max_chunks / suffix, 1);
+        steps[d] = d >= j ? 1 : d + 1 == j ? (ncell[d] + run - 1) / run : ncell[d];
+        ngroups = ngroups > (1ull << 32) / steps[d] ? 1ull << 32 : ngroups * steps[d];
+    }
+    if (ngroups >= (1ull << 32)) {
+        ctx_set_error(ctx, what + ": more than 2^32 groups of chunks; raise slot_budget_bytes or split the selection");
+        return ZCG_ERR_UNSUPPORTED;
+    }
+    ranges.resize(ngroups);
+    P.groups.resize(ngroups);
+    P.glo.assign(ngroups * ZCG_MAX_DIMS, 0);
+    P.gn.assign(ngroups * ZCG_MAX_DIMS, 0);
+    P.gentries.assign(ngroups, 0);
+    for (uint64_t g = 0; g < ngroups; g++) {
+        OrthoRange& R = ranges[g];
+        Group& G = P.groups[g];
+        G.b0 = (uint32_t)g;
+        G.b1 = (uint32_t)g + 1;
+        uint64_t rem = g, real0[ZCG_MAX_DIMS], real1[ZCG_MAX_DIMS], chunks = 1, entries = 1;
+        for (int d = (int)nd - 1; d >= 0; d--) {
+            const uint64_t s = rem % steps[d];
+            rem /= steps[d];
+            R.c0[d] = (uint32_t)((uint32_t)d >= j ? 0 : (uint32_t)d + 1 == j ? s * run : s);
+            R.c1[d] = (uint32_t)((uint32_t)d >= j ? ncell[d] : (uint32_t)d + 1 == j ? std::min(ncell[d], s * run + run) : s + 1);
+            // the cells with a chunk: all but a last one of entries that visit none
+            real0[d] = R.c0[d];
+            real1[d] = R.c1[d] - (axes[d].cells[R.c1[d] - 1].q == ~0ull ? 1 : 0);
+            chunks *= real1[d] - real0[d];
+        }
+        // the group's table: the bounding grid range of its chunks.  A read's run of entries without
+        // a chunk leaves the group without chunks and the table without entries, but the other
+        // dimensions keep their range: their entries are inside it
+        for (uint32_t d = 0; d < nd; d++) {
+            const bool real = real1[d] > real0[d];
+            const uint64_t lo = real ? axes[d].cells[real0[d]].q : 0;
+            const uint64_t n = real ? axes[d].cells[real1[d] - 1].q - lo + 1 : 0;
+            P.glo[g * ZCG_MAX_DIMS + d] = lo;
+            P.gn[g * ZCG_MAX_DIMS + d] = n;
+            entries = entries > BOXES_MAX_TABLE ? entries : entries * n;
+        }
+        P.gentries[g] = entries;
+        if (entries > BOXES_MAX_TABLE) {
+            ctx_set_error(ctx, what + ": a group's chunk table (" + std::to_string(entries) +
+                                   " entries) exceeds 2^24; split the selection over several calls");
+            return ZCG_ERR_UNSUPPORTED;
+        }
+        if (chunks == 0) continue;  // fill only
+        G.keys.reserve(chunks);
+        uint64_t at[ZCG_MAX_DIMS];
+        for (uint32_t d = 0; d < nd; d++) at[d] = real0[d];
+        for (uint64_t k = 0; k < chunks; k++) {  // dimension 0 slowest: ascending keys
+            uint64_t key = 0;
+            bool whole = true;
+            for (uint32_t d = 0; d < nd; d++) {
+                key += axes[d].cells[at[d]].q * P.gstr[d];
+                whole &= axes[d].cells[at[d]].whole;
+            }
+            G.keys.push_back(key);
+            if (write) G.read_first.push_back(whole ? 0 : 1);
+            for (int d = (int)nd - 1; d >= 0; d--) {
+                if (++at[d] < real1[d]) break;
+                at[d] = real0[d];
+            }
+        }
+    }
+    return ZCG_OK;
+}
+
+// A group's runs of the sorted lists: [indices, per dimension][positions, per
+// dimension][scratch of the kernels][the outside words].  d_vals: the values,
+// dense in C order over the caller's positions.
+struct OrthoPayload {
+    const Plan& P;
+    const std::string& what;
+    const OrthoAxis* axes;
+    const std::vector<OrthoRange>& ranges;
+    const uint64_t* count;
+    void* d_vals;
+    bool write;
+    std::vector<uint64_t> recs;
+    uint64_t len[ZCG_MAX_DIMS] = {0}, first[ZCG_MAX_DIMS] = {0}, sum = 0;
+    uint64_t outside[ZCG_MAX_DIMS];
+    uint8_t* d = nullptr;
+    size_t o_scr = 0, o_out = 0;
+
+    size_t device_bytes(const Group& G) {
+        const OrthoRange& R = ranges[G.b0];
+        sum = 0;
+        for (uint32_t k = 0; k < P.nd; k++) {
+            first[k] = axes[k].cells[R.c0[k]].e0;
+            len[k] = axes[k].cells[R.c1[k] - 1].e1 - first[k];
+            sum += len[k];
+        }
+        o_scr = up256(2 * sum * sizeof(uint64_t));
+        o_out = o_scr + zcg_ortho_scratch_bytes(P.nd, len);
+        return o_out + ZCG_MAX_DIMS * sizeof(uint64_t);
+    }
+
+    hipError_t upload(const Group&, uint8_t* d_part, hipStream_t s) {
+        d = d_part;
+        recs.resize(2 * sum);
+        size_t at = 0;
+        for (uint32_t k = 0; k < P.nd; k++)
+            for (uint64_t i = 0; i < len[k]; i++, at++) {
+                recs[at] = axes[k].ent[first[k] + i].c;
+                recs[sum + at] = axes[k].ent[first[k] + i].i;
+            }
+        return hipMemcpyAsync(d, recs.data(), recs.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s);
+    }
+
+    int launch(zcg_ctx* ctx, const Group&, const uint64_t* lo, const uint64_t* n, void* d_table, hipStream_t s) {
+        zcg_osel sel;
+        memset(&sel, 0, sizeof sel);
+        const uint64_t* pos[ZCG_MAX_DIMS] = {nullptr};
+        const uint64_t* dl = (const uint64_t*)d;
+        int64_t acc = 1;
+        for (int k = (int)P.nd - 1; k >= 0; k--) {
+            sel.strides[k] = acc;
+            acc *= (int64_t)count[k];
+        }
+        for (uint32_t k = 0; k < P.nd; k++) {
+            sel.index[k] = dl;
+            pos[k] = dl + sum;
+            sel.count[k] = len[k];
+            dl += len[k];
+        }
+        sel.base = d_vals;
+        const int rc = ortho_call(ctx, &P.r, lo, n, (const void* const*)d_table, &sel, pos, d + o_scr,
+                                  (uint64_t*)(d + o_out), (void*)s, write ? 1 : 0);
+        if (rc != ZCG_OK) return rc;
+        for (uint32_t k = 0; k < ZCG_MAX_DIMS; k++) outside[k] = ~0ull;
+        const hipError_t e = hipMemcpyAsync(outside, d + o_out, P.nd * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
+        return e == hipSuccess ? ZCG_OK : fail_hip(ctx, e, what + (write ? " scatter" : " assembly"));
+    }
+
+    int finish(zcg_ctx* ctx, const Group&) {
+        for (uint32_t k = 0; k < P.nd; k++)
+            if (outside[k] != ~0ull) {
+                ctx_set_error(ctx, what + ": dimension " + std::to_string(k) + ", sorted entry " +
+                                       std::to_string(outside[k]) + " fell outside its group's table");
+                return ZCG_ERR_RUNTIME;
+            }
+        return ZCG_OK;
+    }
+};
+
+// read_points / write_points on the product of the lists in C order.  A host
+// caller's values pass through one device array of the selection's size.
+int run_ortho(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+              const uint64_t* const* lists, const uint64_t* count, uint32_t fill_missing, void* vals,
+              uint64_t slot_budget_bytes, uint32_t io_threads, bool host, bool write) {
+    const std::string what = write ? "write_ortho" : "read_ortho";
+    Plan P;
+    OrthoAxis axes[ZCG_MAX_DIMS];
+    std::vector<OrthoRange> ranges;
+    // before any file is read or written
+    const int prc = plan_ortho(ctx, what, meta, root, path, !write && (host || fill_missing), lists, count, vals, write,
+                               slot_budget_bytes, P, axes, ranges);
+    if (prc != ZCG_OK) return prc;
+    if (P.nothing) return ZCG_OK;
+    uint64_t bytes = P.es;
+    for (uint32_t d = 0; d < P.nd; d++) bytes *= count[d];
+    DevMem stage;
+    if (host) {
+        (void)hipSetDevice(ctx_device(ctx));
+        hipError_t e = stage.alloc(bytes);
+        if (e == hipSuccess && write) e = hipMemcpy(stage.p, vals, bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail_hip(ctx, e, what + " values");
+    }
+    OrthoPayload X{P, what, axes, ranges, count, host ? stage.p : vals, write};
+    const int rc = run_groups(ctx, what, meta, root, path, P, write, io_threads, X);
+    if (rc != ZCG_OK || !host || write) return rc;
+    const hipError_t e = hipMemcpy(vals, stage.p, bytes, hipMemcpyDeviceToHost);
+    return e == hipSuccess ? ZCG_OK : fail_hip(ctx, e, what + " values");
+}
+
+}  // namespace
+
+extern "C" int zcg_store_read_ortho_device(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root,
+                                           const char* path, const uint64_t* const* lists, const uint64_t* count,
+                                           uint32_t fill_missing, void* d_out, uint64_t slot_budget_bytes,
+                                           uint32_t io_threads) {
+    return run_ortho(ctx, meta, root, path, lists, count, fill_missing, d_out, slot_budget_bytes, io_threads, false,
+                     false);
+}
+
+extern "C" int zcg_store_read_ortho(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                                    const uint64_t* const* lists, const uint64_t* count, void* out,
+                                    uint64_t slot_budget_bytes, uint32_t io_threads) {
+    return run_ortho(ctx, meta, root, path, lists, count, 1, out, slot_budget_bytes, io_threads, true, false);
+}
+
+extern "C" int zcg_store_write_ortho_device(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root,
+                                            const char* path, const uint64_t* const* lists, const uint64_t* count,
+                                            const void* d_in, uint64_t slot_budget_bytes, uint32_t io_threads) {
+    return run_ortho(ctx, meta, root, path, lists, count, 0, (void*)d_in, slot_budget_bytes, io_threads, false, true);
+}
+
+extern "C" int zcg_store_write_ortho(zcg_ctx* ctx, const zcg_array_meta* meta, const char* root, const char* path,
+                                     const uint64_t* const* lists, const uint64_t* count, const void* in,
+                                     uint64_t slot_budget_bytes, uint32_t io_threads) {
+    return run_ortho(ctx, meta, root, path, lists, count, 0, (void*)in, slot_budget_bytes, io_threads, true, true);
 }

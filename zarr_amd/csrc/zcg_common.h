@@ -292,6 +292,17 @@ struct PointRecip {
     u64 m[ZCG_MAX_DIMS];       // per dim, fast-first order: ceil(2^64 / chunk extent); unused for an extent of 1
 };
 
+// The lists of an orthogonal selection (zcg_region_o.hip), per dim in
+// fast-first order.  Entry i of dim k has record off[k] + i of the scratch.
+constexpr u32 ORTHO_REC_BYTES = 32;
+struct OrthoAxes {
+    u64 off[ZCG_MAX_DIMS + 1];        // prefix sums of the list lengths; off[nd]: all entries
+    const u64* idx[ZCG_MAX_DIMS];     // DEVICE: the list
+    const u64* pos[ZCG_MAX_DIMS];     // DEVICE: entry i's position in the view along the dim, or NULL: i
+    u32 ppr, pad;                     // 16-byte pieces per row of the selection
+    u64 mppr;                         // PointRecip's m for ppr
+};
+
 }  // namespace zcg
 
 // Internal launchers (zcg_*.hip) used by zcg_api.cpp.
@@ -430,6 +441,15 @@ hipError_t launch_regions_sw(const RegionWalk& w, const BoxTable& bt, void* cons
 hipError_t launch_points(const RegionWalk& w, const BoxTable& bt, const PointRecip& rc, uint64_t n,
                          const void* const* d_table, const uint64_t* d_coords, const uint64_t* d_order, void* d_vals,
                          uint64_t* d_first_outside, const uint64_t* d_all_ones, uint32_t dir, hipStream_t s);
+// An index list per dimension (zcg_region_o.hip): w.bs are the list lengths,
+// w.ostr the view's strides, w.total the 16-byte pieces of all rows; rcount
+// holds PointRecip's m for the list lengths.  d_scratch: ORTHO_REC_BYTES per
+// list entry.  The w.nd words at d_outside are reset by a copy from d_all_ones
+// (ZCG_MAX_DIMS words of UINT64_MAX) and word bt.dim[k] is lowered to the
+// lowest entry of dim k that visits a chunk outside the table.
+hipError_t launch_ortho(const RegionWalk& w, const BoxTable& bt, const PointRecip& rc, const PointRecip& rcount,
+                        const OrthoAxes& ax, const void* const* d_table, void* d_view, void* d_scratch,
+                        uint64_t* d_outside, const uint64_t* d_all_ones, uint32_t dir, hipStream_t s);
 // m device slots of D bytes (d_slots: DEVICE array of their bases, each a
 // multiple of `es`), filled with the element `fillv`
 hipError_t launch_slot_fill(void* const* d_slots, uint32_t m, uint64_t D, uint32_t es, uint64_t fillv,

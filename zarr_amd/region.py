@@ -985,3 +985,198 @@ def write_points(hier, path_name: str, meta: ArrayMetadata, coords, values, devi
         a = np.ascontiguousarray(a.astype(dt, copy=False))
         call("write_points", "zcg_store_write_points", c.ctypes.data, P, a.ctypes.data if P else None,
              slot_budget_bytes, threads)
+
+
+# ---- an orthogonal selection (numpy's a[np.ix_(rows, cols, planes)], zarr's oindex) ----
+
+def _sel_arg(sel, shape: Sequence[int]) -> List[np.ndarray]:
+    """`sel` as one contiguous uint64 index array per dimension.  An entry is an
+    integer array or list; a slice, resolved against the dimension's extent as
+    numpy does (a negative step is just a list); a boolean array of the
+    dimension's length, taken as flatnonzero; or an int, an axis of length 1
+    that is kept."""
+    sel = list(sel) if isinstance(sel, (tuple, list)) else [sel]
+    if len(sel) != len(shape):
+        raise ZarrIOError("InvalidData", "Wrong number of dimensions")
+    lists = []
+    for d, s in enumerate(sel):
+        if isinstance(s, slice):
+            a = np.arange(*s.indices(int(shape[d])), dtype=np.int64)
+        elif isinstance(s, (bool, np.bool_)):
+            raise TypeError("a selection entry must be integers, a slice or a boolean array")
+        elif isinstance(s, (int, np.integer)):
+            a = np.array([int(s)], dtype=object)
+        else:
+            a = np.asarray(s)
+            if a.dtype == bool:
+                if a.ndim != 1 or a.shape[0] != int(shape[d]):
+                    raise IndexError(f"boolean selection along dimension {d} has length {a.shape[0] if a.ndim else 0}, "
+                                     f"the dimension has {int(shape[d])}")
+                a = np.flatnonzero(a)
+            elif a.size == 0:
+                a = np.zeros(0, np.uint64)
+            a = a.reshape(-1)
+        if a.dtype.kind not in "iu" and a.dtype != object:
+            raise TypeError("a selection entry must be integers, a slice or a boolean array")
+        if a.size and (a.dtype.kind == "i" or a.dtype == object) and min(int(x) for x in a) < 0:
+            raise ValueError(f"negative index along dimension {d}")
+        lists.append(np.ascontiguousarray(a.astype(np.uint64)))
+    return lists
+
+
+def _list_pointers(lists):
+    """(pointer array, count array) over host index arrays or device tensors."""
+    ptrs = (ctypes.c_void_p * _native.MAX_DIMS)(*[(a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr())
+                                                  if _numel(a) else None for a in lists])
+    counts = (ctypes.c_uint64 * _native.MAX_DIMS)(*[_numel(a) for a in lists])
+    return ptrs, counts
+
+
+def _numel(a) -> int:
+    return int(a.size) if isinstance(a, np.ndarray) else int(a.numel())
+
+
+def ortho_scratch_bytes(counts: Sequence[int]) -> int:
+    """zcg_ortho_scratch_bytes: device working memory of one ortho call."""
+    c = (ctypes.c_uint64 * _native.MAX_DIMS)(*[int(x) for x in counts])
+    return int(_native.load_library().zcg_ortho_scratch_bytes(len(counts), ctypes.addressof(c)))
+
+
+def ortho_chunks(meta: ArrayMetadata, sel, want_touched: bool = True):
+    """zcg_ortho_chunks (host code, no GPU) -> (lo, n, touched, count): the
+    smallest grid range that holds every visited chunk, per dimension a list of
+    n[d] 0/1 flags (1: grid index lo[d] + j holds a visiting index of the
+    dimension's list; None without want_touched), and the number of touched
+    chunks (the product of the touched counts)."""
+    L = _native.load_library()
+    nd = meta.get_ndim()
+    lists = _sel_arg(sel, meta.shape)
+    r = _region(meta, BoundingBox([0] * nd, [1] * nd), 1, False, 0, [0] * nd)
+    ptrs, counts = _list_pointers(lists)
+    lo = (ctypes.c_uint64 * _native.MAX_DIMS)()
+    n = (ctypes.c_uint64 * _native.MAX_DIMS)()
+    args = (ctypes.byref(r), ctypes.addressof(ptrs), ctypes.addressof(counts), ctypes.addressof(lo),
+            ctypes.addressof(n))
+    count = int(L.zcg_ortho_chunks(*args, None))
+    lo_l, n_l = [int(lo[d]) for d in range(nd)], [int(n[d]) for d in range(nd)]
+    if not want_touched:
+        return lo_l, n_l, None, count
+    flags = np.zeros(max(sum(n_l), 1), np.uint8)
+    count = int(L.zcg_ortho_chunks(*args, flags.ctypes.data))
+    at = np.concatenate([[0], np.cumsum(n_l)]).astype(int)
+    return lo_l, n_l, [flags[at[d]:at[d + 1]].tolist() for d in range(nd)], count
+
+
+def _ortho(name: str, meta: ArrayMetadata, es, table, table_lo, table_n, lists, view, strides, outside, fill,
+           fill_value, device, stream, scratch) -> None:
+    ctx = _native.context(device)
+    nd = meta.get_ndim()
+    if len(lists) != nd:
+        raise ZarrIOError("InvalidData", "Wrong number of dimensions")
+    r = _region(meta, BoundingBox([0] * nd, [1] * nd), es, fill, fill_value, [0] * nd)
+    lo = (ctypes.c_uint64 * _native.MAX_DIMS)(*[int(x) for x in table_lo])
+    n = (ctypes.c_uint64 * _native.MAX_DIMS)(*[int(x) for x in table_n])
+    sel = _native.OSel()
+    for d in range(nd):
+        sel.count[d] = _numel(lists[d])
+        sel.index[d] = lists[d].data_ptr() if sel.count[d] else None
+        sel.strides[d] = int(strides[d])
+    sel.base = view.data_ptr() if view is not None else None
+    if scratch is None and all(sel.count[d] for d in range(nd)):
+        import torch
+        scratch = torch.empty(ortho_scratch_bytes([sel.count[d] for d in range(nd)]), dtype=torch.uint8,
+                              device=view.device)
+    st = getattr(ctx.lib, name)(ctx.handle, ctypes.byref(r), ctypes.addressof(lo), ctypes.addressof(n),
+                                table.data_ptr() if table is not None else None, ctypes.addressof(sel),
+                                scratch.data_ptr() if scratch is not None else None,
+                                outside.data_ptr() if outside is not None else None, _stream_handle(stream, device))
+    _raise_status(st, ctx, name[4:])
+
+
+def assemble_ortho(meta: ArrayMetadata, es: int, table, table_lo, table_n, lists, out, out_strides, outside,
+                   fill: bool = False, fill_value: int = 0, device: int = 0, stream=None, scratch=None) -> None:
+    """Device-level gather of an orthogonal selection (zcg_read_ortho): `lists`
+    = one device int64/uint64 tensor of array indices per dimension, `out` =
+    device tensor whose data_ptr() is element (0, ..., 0) of a view with
+    `out_strides` (elements, per array dimension), `outside` = device tensor of
+    ndim 64-bit words (per dimension UINT64_MAX, or the lowest position in the
+    list whose chunk lies outside the table).  Element (i_0, .., i_{n-1}) is what
+    assemble_points gives the point (lists[0][i_0], .., lists[n-1][i_{n-1}]).
+    `scratch` = device tensor of ortho_scratch_bytes(counts) bytes (None:
+    allocated here, which a captured call must not do).  Asynchronous."""
+    _ortho("zcg_read_ortho", meta, es, table, table_lo, table_n, lists, out, out_strides, outside, fill, fill_value,
+           device, stream, scratch)
+
+
+def scatter_ortho(meta: ArrayMetadata, es: int, table, table_lo, table_n, lists, values, value_strides, outside,
+                  device: int = 0, stream=None, scratch=None) -> None:
+    """Device-level inverse of assemble_ortho (zcg_write_ortho): element
+    (i_0, .., i_{n-1}) of the view goes to the chunk slot element of its point.
+    With duplicate indices in a list one value wins whole; drop the earlier
+    duplicates per list with points_last where the later one must win.
+    Asynchronous."""
+    _ortho("zcg_write_ortho", meta, es, table, table_lo, table_n, lists, values, value_strides, outside, False, 0,
+           device, stream, scratch)
+
+
+def read_ortho(hier, path_name: str, meta: ArrayMetadata, sel, t, device: int = 0, as_tensor: bool = False,
+               slot_budget_bytes: int = 0, io_threads: int = 0, flags: int = 0):
+    """a[np.ix_(*sel)] in one native call (zcg_store_read_ortho[_device]): an
+    array (with as_tensor a device tensor) whose shape is the lengths of the
+    selection's lists, element (i_0, .., i_{n-1}) being read_points at
+    (sel[0][i_0], .., sel[n-1][i_{n-1}]).  `sel` holds one entry per dimension
+    (_sel_arg).  Only the touched chunks, the product of the per-dimension
+    touched grid indices, are opened, each decoded once."""
+    import torch
+    check_array_type(t, meta)
+    lists = _sel_arg(sel, meta.shape)
+    counts = [int(a.size) for a in lists]
+    total = int(np.prod(counts, dtype=object))
+    dt = np.dtype(t).newbyteorder("=")
+    call = _StoreCall(hier, path_name, meta, flags, device)
+    threads = io_threads or 16
+    ptrs, cnt = _list_pointers(lists)
+    if as_tensor:
+        out = torch.empty(max(total, 1) * dt.itemsize, dtype=torch.uint8, device=torch.device("cuda", device))
+        call("read_ortho", "zcg_store_read_ortho_device", ctypes.addressof(ptrs), ctypes.addressof(cnt), 1,
+             out.data_ptr(), slot_budget_bytes, threads)
+        out = out[: total * dt.itemsize]
+        return out.view(getattr(torch, dt.name)).reshape(counts) if hasattr(torch, dt.name) else out
+    host = np.empty(max(total, 1), dt)
+    call("read_ortho", "zcg_store_read_ortho", ctypes.addressof(ptrs), ctypes.addressof(cnt), host.ctypes.data,
+         slot_budget_bytes, threads)
+    return host[:total].reshape(counts)
+
+
+def write_ortho(hier, path_name: str, meta: ArrayMetadata, sel, values, device: int = 0,
+                slot_budget_bytes: int = 0, io_threads: int = 0, flags: int = 0) -> None:
+    """a[np.ix_(*sel)] = values in one native call
+    (zcg_store_write_ortho[_device]): the store ends up as after write_points
+    on the product of the lists in C order, so per list the last occurrence of
+    an index wins.  `values` is a numpy array, or a device tensor, of the
+    selection's shape.  Every touched chunk is read at most once (not at all
+    where the selection covers it), and encoded and written once.  `flags`:
+    decode flags for the chunks that are read first."""
+    lists = _sel_arg(sel, meta.shape)
+    counts = [int(a.size) for a in lists]
+    total = int(np.prod(counts, dtype=object))
+    call = _StoreCall(hier, path_name, meta, flags, device)
+    threads = io_threads or 16
+    ptrs, cnt = _list_pointers(lists)
+    if hasattr(values, "data_ptr"):
+        if values.numel() != total:
+            raise ZarrIOError("InvalidData", "Selection and values differ in number")
+        v = values.contiguous()
+        if v.element_size() != call.am.array.dtype.elem_size:
+            raise ZarrIOError("InvalidData", "Element size differs from the array's")
+        call("write_ortho", "zcg_store_write_ortho_device", ctypes.addressof(ptrs), ctypes.addressof(cnt),
+             v.data_ptr(), slot_budget_bytes, threads)
+    else:
+        a = np.asarray(values)
+        if a.size != total:
+            raise ZarrIOError("InvalidData", "Selection and values differ in number")
+        dt = a.dtype.newbyteorder("=")
+        check_array_type(dt, meta)
+        a = np.ascontiguousarray(a.astype(dt, copy=False)).reshape(-1)
+        call("write_ortho", "zcg_store_write_ortho", ctypes.addressof(ptrs), ctypes.addressof(cnt),
+             a.ctypes.data if total else None, slot_budget_bytes, threads)
