@@ -51,7 +51,9 @@ enum zcg_codec {
     ZCG_CODEC_BZIP2 = 1, /* bzip.rs:16-46 */
     ZCG_CODEC_GZIP = 2,  /* gzip.rs:16-57 */
     ZCG_CODEC_LZ4 = 3,   /* lz.rs:45-93 */
-    ZCG_CODEC_XZ = 4     /* xz.rs:15-43 */
+    ZCG_CODEC_XZ = 4,    /* xz.rs:15-43 */
+    ZCG_CODEC_ZLIB = 5   /* RFC 1950 (this library's own: the reference has no such variant): a 2-byte
+                            header, the gzip codec's deflate body, a big-endian Adler-32 */
 };
 
 /* Per-chunk status words; map 1:1 onto std::io::ErrorKind of the reference. */
@@ -76,7 +78,7 @@ enum zcg_status {
  * (the decoded bytes are the same; only a corrupt checksum word changes the
  * status).
  *
- * Opt-in verification (decode only; encode ignores both flags, and a flag for
+ * Opt-in verification (decode only; encode ignores these flags, and a flag for
  * the other codec is ignored).  Every decode entry point honours them through
  * zcg_array.compression.flags: zcg_decode_batch, zcg_read_chunk,
  * zcg_read_chunks_host, zcg_store_read_chunks[_device], zcg_multi_*.
@@ -105,6 +107,20 @@ enum zcg_status {
  *   5. ISIZE != D mod 2^32 -> ZCG_ERR_INVALID_DATA;
  *   6. CRC32 of the D decoded bytes in stream order (before the byte swap and
  *      the bool rule) != the trailer's -> ZCG_ERR_INVALID_DATA.
+ * ZCG_FLAG_VERIFY_ZLIB_TRAILER (the zlib codec; the gzip and LZ4 flags are
+ * ignored on it, and it is ignored on the other codecs):
+ *   rules 1-4 of ZCG_FLAG_VERIFY_GZIP_TRAILER hold verbatim with h = 2 and a
+ *   trailer of 4 bytes at byte 2 + ceil(end_bit / 8) (fewer than 4 bytes there
+ *   -> ZCG_ERR_UNEXPECTED_EOF); there is no length word;
+ *   5. Adler-32 of the D decoded bytes in stream order (before the byte swap
+ *      and the bool rule) != the trailer read big-endian -> ZCG_ERR_INVALID_DATA.
+ * The zlib header without any flag, as zlib's inflate() reads it: fewer than 2
+ * bytes -> ZCG_ERR_UNEXPECTED_EOF; (b0 << 8 | b1) % 31 != 0, (b0 & 15) != 8 or
+ * (b0 >> 4) > 7 -> ZCG_ERR_INVALID_DATA; FDICT (b1 & 0x20) -> ZCG_ERR_UNSUPPORTED
+ * (a preset dictionary).  Any declared window of 8 to 15 bits is accepted and
+ * distances are not checked against it (zlib does so only under
+ * INFLATE_STRICT).  The body is then read exactly as the gzip codec reads it,
+ * and without the flag the trailer is never read.
  * ZCG_FLAG_VERIFY_LZ4_CONTENT:
  *   1. the frame must end exactly at D bytes: the EndMark follows the block
  *      that reaches D; a further data block (or a block that decodes past D)
@@ -119,6 +135,7 @@ enum zcg_status {
 #define ZCG_FLAG_VERIFY_GZIP_TRAILER 0x1u
 #define ZCG_FLAG_VERIFY_LZ4_CONTENT 0x2u
 #define ZCG_FLAG_SKIP_LZ4_BLOCK_CHECKSUM 0x4u
+#define ZCG_FLAG_VERIFY_ZLIB_TRAILER 0x8u
 /* Use the wave-serial inflate kernel instead of the parallel one (the two are
  * bit-identical; the serial one is kept as a differential reference). */
 #define ZCG_FLAG_SERIAL_INFLATE 0x100u
@@ -135,7 +152,7 @@ enum zcg_status {
  * stream) below 196 608, lanes from there. */
 #define ZCG_FLAG_LZ4_WAVE_PER_BLOCK 0x800u
 #define ZCG_FLAG_LZ4_LANE_PER_BLOCK 0x1000u
-/* Gzip decode kernel choice (all bit-identical).  By default a batch of at
+/* Gzip and zlib decode kernel choice (all bit-identical).  By default a batch of at
  * most 3 chunks per CU (one generation of the 256-lane kernel) runs the
  * 256-lane round kernel (fine 256-bit segments, one workgroup of 4 waves per
  * chunk: half the latency of a lone chunk), a larger one the one-wave-per-chunk
@@ -143,7 +160,9 @@ enum zcg_status {
 #define ZCG_FLAG_INFLATE_BLOCK_PAR 0x2000u
 #define ZCG_FLAG_INFLATE_WAVE 0x4000u
 /* Gzip encode at levels 1-9 is byte-identical to zlib 1.2.11 / flate2
- * (gzip.rs:54-56) by default (deflate_fast for 1-3, deflate_slow for 4-9).
+ * (gzip.rs:54-56) by default (deflate_fast for 1-3, deflate_slow for 4-9), and
+ * zlib encode to zlib 1.2.11's compress2() (header 78 01 at levels 0-1, 78 5E
+ * at 2-5, 78 9C at 6, 78 DA at 7-9).
  * This flag selects the faster segmented coder instead (16 KiB blocks, each
  * ended by an empty stored block; the stream inflates to the same data, but
  * its bytes differ from zlib's).  Level 0 always uses the segmented coder. */
@@ -157,7 +176,8 @@ enum zcg_status {
 /* CompressionType + its configuration (camelCase JSON keys in the reference). */
 typedef struct zcg_compression {
     int32_t codec;            /* enum zcg_codec                                 */
-    int32_t gzip_level;       /* gzip.rs:16-20, -1 / out of [0,9] -> 6 (28-34)  */
+    int32_t gzip_level;       /* deflate level of the GZIP and ZLIB codecs:
+                                 gzip.rs:16-20, -1 / out of [0,9] -> 6 (28-34)  */
     int32_t lz4_block_size;   /* lz.rs:45-50, rounded to 64K/256K/1M/4M (55-65) */
     int32_t bzip2_block_size; /* bzip.rs:16-21, 1..9                            */
     int32_t xz_preset;        /* xz.rs:15-20                                    */

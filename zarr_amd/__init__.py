@@ -6,7 +6,7 @@ decoded/encoded by hand-written gfx950 HIP kernels behind the C ABI in
 ``include/zchunk_gpu.h``.  The Python layer mirrors the reference's types so
 callers (and the parity tests) read like the reference's own.
 """
-from .compression import GZIP_CODEC_ID, Bzip2, CompressionType, Gzip, Lz4, Raw, Xz
+from .compression import GZIP_CODEC_ID, Bzip2, CompressionType, Gzip, Lz4, Raw, Xz, Zlib
 from .data_type import (DataType, Endian, ExtendedDataType, MetadataError, NATIVE_ENDIAN,
                         REFLECTED_TYPES, effective_type, zarr_type)
 from .metadata import ArrayMetadata, u64_ceil_div
@@ -25,7 +25,7 @@ __all__ = [
     "ArrayMetadata", "BoundingBox", "Bzip2", "CompressionType", "DataType", "DefaultChunk", "Endian",
     "ExtendedDataType", "FilesystemHierarchy", "GZIP_CODEC_ID", "Gzip", "Lz4", "MetadataError",
     "NATIVE_ENDIAN", "NativeUnavailable", "REFLECTED_TYPES", "Raw", "SliceDataChunk",
-    "VecDataChunk", "Xz", "ZarrIOError", "check_array_type", "effective_type", "get_chunk_key",
+    "VecDataChunk", "Xz", "ZarrIOError", "Zlib", "check_array_type", "effective_type", "get_chunk_key",
     "assemble_regions_s", "read_chunks_host", "read_ndarray", "read_ndarrays", "read_ndarrays_s", "read_ndarrays_v",
     "region_s_chunks", "regions_s_grid", "regions_s_scratch_bytes", "regions_s_waves", "sboxes_tensor",
     "scatter_regions_s", "u64_ceil_div", "write_ndarray", "write_ndarrays", "write_ndarrays_s", "write_ndarrays_v",

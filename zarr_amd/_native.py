@@ -24,6 +24,8 @@ FLAG_VERIFY_GZIP_TRAILER = 0x1
 FLAG_VERIFY_LZ4_CONTENT = 0x2
 FLAG_VERIFY = FLAG_VERIFY_GZIP_TRAILER | FLAG_VERIFY_LZ4_CONTENT
 FLAG_SKIP_LZ4_BLOCK_CHECKSUM = 0x4
+FLAG_VERIFY_ZLIB_TRAILER = 0x8
+FLAG_VERIFY_ALL = FLAG_VERIFY | FLAG_VERIFY_ZLIB_TRAILER  # (FLAG_VERIFY keeps its two bits)
 FLAG_SERIAL_INFLATE = 0x100
 FLAG_DEBUG_COUNTERS = 0x200
 FLAG_XZ_RING_32K = 0x400

@@ -14,7 +14,7 @@ from typing import Any, Dict, Optional
 GZIP_CODEC_ID = "https://purl.org/zarr/spec/codec/gzip/1.0"  # mod.rs:45
 
 # Numbering of include/zchunk_gpu.h (enum zcg_codec).
-CODEC_RAW, CODEC_BZIP2, CODEC_GZIP, CODEC_LZ4, CODEC_XZ = 0, 1, 2, 3, 4
+CODEC_RAW, CODEC_BZIP2, CODEC_GZIP, CODEC_LZ4, CODEC_XZ, CODEC_ZLIB = 0, 1, 2, 3, 4, 5
 
 
 @dataclasses.dataclass(frozen=True)
@@ -87,10 +87,28 @@ class Xz:
         return {"preset": self.preset}
 
 
-_BY_JSON = {"raw": Raw, "bzip2": Bzip2, GZIP_CODEC_ID: Gzip, "lz4": Lz4, "xz": Xz}
-_JSON_KEY = {Raw: "raw", Bzip2: "bzip2", Gzip: GZIP_CODEC_ID, Lz4: "lz4", Xz: "xz"}
+@dataclasses.dataclass(frozen=True)
+class Zlib:
+    """The zlib stream (RFC 1950): a 2-byte header, the Gzip variant's deflate
+    body, a big-endian Adler-32.  Not a variant of the reference's enum: the
+    container most zarr data in the field was written with.  ``level`` as Gzip."""
+
+    level: int = -1
+    codec_id = CODEC_ZLIB
+    name = "Zlib"
+
+    def effective_level(self) -> int:
+        """Outside [0, 9] -> 6, zlib's default (the Gzip variant's rule)."""
+        return 6 if self.level < 0 or self.level > 9 else self.level
+
+    def configuration(self):
+        return {"level": self.level}
+
+
+_BY_JSON = {"raw": Raw, "bzip2": Bzip2, GZIP_CODEC_ID: Gzip, "lz4": Lz4, "xz": Xz, "zlib": Zlib}
+_JSON_KEY = {Raw: "raw", Bzip2: "bzip2", Gzip: GZIP_CODEC_ID, Lz4: "lz4", Xz: "xz", Zlib: "zlib"}
 _CFG_FIELD = {Bzip2: ("blockSize", "block_size"), Gzip: ("level", "level"),
-              Lz4: ("blockSize", "block_size"), Xz: ("preset", "preset")}
+              Lz4: ("blockSize", "block_size"), Xz: ("preset", "preset"), Zlib: ("level", "level")}
 
 
 class CompressionType:
@@ -101,6 +119,7 @@ class CompressionType:
     Gzip = Gzip
     Lz4 = Lz4
     Xz = Xz
+    Zlib = Zlib
 
     @staticmethod
     def default():
@@ -110,7 +129,7 @@ class CompressionType:
     @staticmethod
     def from_str(s: str):
         """``FromStr`` (mod.rs:134-156): case-insensitive variant names."""
-        m = {"raw": Raw, "bzip2": Bzip2, "gzip": Gzip, "xz": Xz, "lz4": Lz4}
+        m = {"raw": Raw, "bzip2": Bzip2, "gzip": Gzip, "xz": Xz, "lz4": Lz4, "zlib": Zlib}
         k = s.lower()
         if k not in m:
             raise ValueError(f"InvalidInput: unknown compression {s!r}")
@@ -155,7 +174,7 @@ def to_abi_fields(c) -> Dict[str, int]:
     """Fields of ``zcg_compression`` for this variant."""
     f = {"codec": c.codec_id, "gzip_level": -1, "lz4_block_size": 65536,
          "bzip2_block_size": 9, "xz_preset": 6}
-    if isinstance(c, Gzip):
+    if isinstance(c, (Gzip, Zlib)):
         f["gzip_level"] = c.level
     elif isinstance(c, Lz4):
         f["lz4_block_size"] = c.block_size
@@ -168,7 +187,7 @@ def to_abi_fields(c) -> Dict[str, int]:
 
 def codec_param(c) -> int:
     """The single integer parameter the oracle's encoders take."""
-    if isinstance(c, Gzip):
+    if isinstance(c, (Gzip, Zlib)):
         return c.level
     if isinstance(c, Lz4):
         return c.block_size

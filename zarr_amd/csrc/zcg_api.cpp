@@ -257,6 +257,7 @@ int zcg_codec_on_gpu(int32_t codec, int encode) {
     case ZCG_CODEC_RAW: return 1;
     case ZCG_CODEC_LZ4: return 1;
     case ZCG_CODEC_GZIP: return 1;
+    case ZCG_CODEC_ZLIB: return 1;
     case ZCG_CODEC_XZ: return 1;
     case ZCG_CODEC_BZIP2: return 1;
     default: return 0;
@@ -268,6 +269,8 @@ uint64_t zcg_encode_bound(const zcg_compression* c, uint64_t n) {
     case ZCG_CODEC_RAW: return n;
     case ZCG_CODEC_GZIP:  // 16 KiB segment slots (stored worst case + sync) + header/trailer
         return 18 + ((n + 16383) / 16384) * (16384 + 128) + 64;
+    case ZCG_CODEC_ZLIB:  // the same, with the 2 + 4 frame bytes
+        return 6 + ((n + 16383) / 16384) * (16384 + 128) + 64;
     case ZCG_CODEC_LZ4: {
         const uint64_t b = (uint64_t)zcg_effective_lz4_block_size(c->lz4_block_size);
         return 15 + (n / b + 1) * (b + 8) + 8;
@@ -283,7 +286,7 @@ uint64_t zcg_workspace_bytes(const zcg_array* a, uint32_t n, int encode) {
     if (a->compression.codec == ZCG_CODEC_BZIP2)
         return encode ? bzip2_encode_ws_bytes(a, n) : bzip2_decode_ws_bytes(a, n);
     if (a->compression.codec == ZCG_CODEC_XZ && encode) return xz_encode_ws_bytes(a, n);
-    if (a->compression.codec == ZCG_CODEC_GZIP)
+    if (a->compression.codec == ZCG_CODEC_GZIP || a->compression.codec == ZCG_CODEC_ZLIB)
         return encode ? deflate_ws_bytes(a, n) : gzip_decode_ws_bytes(a, n);
     if (a->compression.codec == ZCG_CODEC_LZ4) return encode ? lz4_encode_ws_bytes(a, n) : lz4_decode_ws_bytes(a, n);
     return 0;
@@ -307,7 +310,8 @@ int zcg_decode_batch(zcg_ctx* ctx, const zcg_array* a, const zcg_chunk* d_chunks
         e = launch_lz4_decode(a, d_chunks, n, d_status, w->p, w->bytes, s, w->side, w->fork, w->join);
         break;
     }
-    case ZCG_CODEC_GZIP: {
+    case ZCG_CODEC_GZIP:
+    case ZCG_CODEC_ZLIB: {
         zcg_ctx::Ws* w = nullptr;
         const uint64_t need = gzip_decode_ws_bytes(a, n);  // (0: the serial kernel, no workspace)
         if (need) {
@@ -357,7 +361,8 @@ int zcg_encode_batch(zcg_ctx* ctx, const zcg_array* a, const zcg_chunk* d_chunks
         e = launch_lz4_encode(a, d_chunks, n, d_out_len, d_status, w->p, w->bytes, s);
         break;
     }
-    case ZCG_CODEC_GZIP: {
+    case ZCG_CODEC_GZIP:
+    case ZCG_CODEC_ZLIB: {
         zcg_ctx::Ws* w = nullptr;
         const int r = stream_ws(ctx, stream, deflate_ws_bytes(a, n), &w);
         if (r != ZCG_OK) return r;

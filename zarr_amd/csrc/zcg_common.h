@@ -369,10 +369,30 @@ hipError_t launch_inflate(const zcg_array* a, const zcg_chunk* d_chunks, uint32_
                           int32_t* d_status, void* ws, uint64_t ws_bytes, hipStream_t s);
 // Opt-in checksum verification (zcg_verify.hip), launched on the decode's
 // stream after its last kernel.  The verify area is a part of the decoder's
-// workspace: VerifyRec[n], then the CRC32 partials.  Under a verify flag the
+// workspace: VerifyRec[n], then the CRC32 (Adler-32) partials.  Under a verify flag the
 // decode kernels get a dtype without the part of the element transform that
 // the verify pass applies after it has read the bytes in stream order: bool
 // for gzip (its byte swap is undone on the fly), byte swap and bool for LZ4.
+// The zlib codec (RFC 1950) runs the gzip decoders with another member frame.
+// launch_gzip_decode and gzip_decode_ws_bytes hand everything below them the
+// array of inflate_frame_array(): for ZCG_CODEC_ZLIB the flag word carries
+// INF_FRAME_ZLIB (an internal bit, cleared on what a caller passes) and
+// ZCG_FLAG_VERIFY_ZLIB_TRAILER sits in ZCG_FLAG_VERIFY_GZIP_TRAILER's place, so
+// "verify the member's trailer" is one bit for both frames and the flags of the
+// other codecs are gone.  The launchers turn the frame bit into the kernel
+// instantiation (the serial kernel into inf_open's and inf_close's argument).
+constexpr uint32_t INF_FRAME_ZLIB = 0x80000000u;
+inline zcg_array inflate_frame_array(const zcg_array* a) {
+    zcg_array f = *a;
+    uint32_t fl = f.compression.flags & ~INF_FRAME_ZLIB;
+    if (f.compression.codec == ZCG_CODEC_ZLIB) {
+        const bool v = (fl & ZCG_FLAG_VERIFY_ZLIB_TRAILER) != 0;
+        fl &= ~(uint32_t)(ZCG_FLAG_VERIFY_GZIP_TRAILER | ZCG_FLAG_VERIFY_LZ4_CONTENT | ZCG_FLAG_VERIFY_ZLIB_TRAILER);
+        fl |= INF_FRAME_ZLIB | (v ? ZCG_FLAG_VERIFY_GZIP_TRAILER : 0u);
+    }
+    f.compression.flags = fl;
+    return f;
+}
 inline bool gzip_verify(const zcg_array* a) { return (a->compression.flags & ZCG_FLAG_VERIFY_GZIP_TRAILER) != 0; }
 inline bool lz4_verify(const zcg_array* a) { return (a->compression.flags & ZCG_FLAG_VERIFY_LZ4_CONTENT) != 0; }
 inline DType gzip_decode_dtype(const zcg_array* a) {
@@ -384,6 +404,8 @@ uint64_t verify_ws_bytes(uint32_t n);
 hipError_t verify_reset(void* varea, uint32_t n, hipStream_t s);
 hipError_t launch_crc32_verify(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n,
                                int32_t* d_status, void* varea, hipStream_t s);
+hipError_t launch_adler32_verify(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n,
+                                 int32_t* d_status, void* varea, hipStream_t s);
 hipError_t launch_xxh32_verify(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n,
                                int32_t* d_status, void* varea, hipStream_t s);
 hipError_t launch_inflate_par(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n,

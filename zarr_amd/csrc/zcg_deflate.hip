@@ -15,9 +15,13 @@
 //     pins the core on the CPU, tests/test_gpu_encode.py the kernels).
 //   * gzip_crc32: per chunk, 64 lanes CRC their slices, lane 0 combines them
 //     with a precomputed GF(2) shift operator; both coders' trailers.
+//   * The zlib codec (ZCG_CODEC_ZLIB) is the same two coders inside RFC 1950's
+//     container: a 2-byte header, and zlib_adler32 in gzip_crc32's place.  At
+//     levels 1-9 the bytes are zlib.compress(data, level)'s.
 #include "zcg_chains.h"
 #include "zcg_deflate.h"
 #include "zcg_zlib_core.h"
+#include "zcg_adler.h"
 
 namespace zcg {
 
@@ -128,6 +132,75 @@ hipError_t launch_gzip_crc32(const zcg_chunk* d_chunks, u32 n, u64 D, DType t, c
     return hipGetLastError();
 }
 
+// The zlib codec's trailer: gzip_crc32's two modes with Adler-32 (zcg_adler.h)
+// of the serialised input.  One workgroup per chunk; thread i takes the 16
+// bytes at i * 16 of every 4 KiB tile (coalesced), a short last tile is padded
+// with zero pieces; the lanes' partials add.  sum_out set: the value only (the
+// slot dz_final reads); else 4 big-endian bytes at the end of the stream.
+constexpr u32 ZA_NT = 256;
+static_assert((1ull << 31) / (ZA_NT * 16) <= ADLER_LANE_MAX_PIECES,
+              "a lane's pieces of the largest chunk (D < 2^31) stay inside the deferred-modulo bound");
+__global__ __launch_bounds__(ZA_NT) void zlib_adler32(const zcg_chunk* __restrict__ chunks, u32 n, u64 D,
+                                                      const u64* __restrict__ out_len, const i32* __restrict__ status,
+                                                      DType t, u32* __restrict__ sum_out) {
+    const u32 c = blockIdx.x, tid = threadIdx.x;
+    if (c >= n) return;
+    if (sum_out ? chunks[c].src_len < D : status[c] != ZCG_OK) return;
+    const u8* src = (const u8*)chunks[c].src;
+    constexpr u64 TILE = ZA_NT * 16;
+    const u64 ntile = (D + TILE - 1) / TILE;
+    AdlerLane al = adler_lane_open();
+    for (u64 k = 0; k < ntile; k++) {
+        const u64 p = k * TILE + tid * 16;
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (p + 16 <= D) {
+            v = transform16(ld16(src + p), t);
+        } else if (p < D) {  // the piece the chunk ends in (whole elements: D % es == 0)
+            u32 w[4] = {0u, 0u, 0u, 0u};
+            for (u64 q = p; q < D; q++) w[(q - p) >> 2] |= ser1(src, q, t) << (8 * ((q - p) & 3));
+            v = u32x4{w[0], w[1], w[2], w[3]};
+        }
+        adler_lane_piece(al, v.x, v.y, v.z, v.w);
+    }
+    u32 v = 0;
+    if (ntile) v = adler_lane_close(al, (i64)D - (i64)((ntile - 1) * TILE + tid * 16) - 16, (u32)TILE);
+    v = adler_wave_sum(v);
+    __shared__ u32 s_part[ZA_NT / 64];
+    if ((tid & 63) == 0) s_part[tid >> 6] = v;
+    __syncthreads();
+    if (tid != 0) return;
+    u32 r = 0;
+    for (u32 i = 0; i < ZA_NT / 64; i++) r = adler_add(r, s_part[i]);
+    r = adler_finish(r, D);
+    if (sum_out) {
+        sum_out[c] = r;
+        return;
+    }
+    u8* o = (u8*)chunks[c].dst + out_len[c] - 4;
+    o[0] = (u8)(r >> 24); o[1] = (u8)(r >> 16); o[2] = (u8)(r >> 8); o[3] = (u8)r;
+}
+
+hipError_t launch_zlib_adler32(const zcg_chunk* d_chunks, u32 n, u64 D, DType t, const u64* d_out_len,
+                               const i32* d_status, u32* sum_out, hipStream_t s) {
+    hipLaunchKernelGGL(zlib_adler32, dim3(n), dim3(ZA_NT), 0, s, d_chunks, n, D, d_out_len, d_status, t, sum_out);
+    return hipGetLastError();
+}
+
+// The container of a deflate stream: zhdr == 0 the gzip member (10-byte header
+// with XFL, CRC32 + ISIZE), else the zlib stream whose two header bytes are
+// zhdr (big-endian) and whose trailer is the Adler-32.  zlib 1.2.11's
+// deflate(): CMF 0x78, FLG's level bits from the level, FCHECK makes it a
+// multiple of 31.
+u32 zlib_header_word(const zcg_array* a, u32 level) {
+    if (a->compression.codec != ZCG_CODEC_ZLIB) return 0u;
+    return level <= 1 ? 0x7801u : level <= 5 ? 0x785Eu : level == 6 ? 0x789Cu : 0x78DAu;
+}
+hipError_t launch_stream_checksum(u32 zhdr, const zcg_chunk* d_chunks, u32 n, u64 D, DType t, const u64* d_out_len,
+                                  const i32* d_status, u32* sum_out, hipStream_t s) {
+    return zhdr ? launch_zlib_adler32(d_chunks, n, D, t, d_out_len, d_status, sum_out, s)
+                : launch_gzip_crc32(d_chunks, n, D, t, d_out_len, d_status, sum_out, s);
+}
+
 // ---- the zlib-exact coder ----
 namespace {
 
@@ -179,7 +252,7 @@ DzWs dz_ws(u64 D, u32 n) {
     y.off_ch = ws.take(sizeof(DzChunk) * sb);
     y.off_blk = ws.take(sizeof(DzBlock) * sb * y.nbmax);
     y.off_out = ws.take(y.outcap * sb);
-    y.off_crc = ws.take(4ull * sb);  // the super-batch's input CRC32s (dz_final writes the trailers)
+    y.off_crc = ws.take(4ull * sb);  // the super-batch's input CRC32s or Adler-32s (dz_final writes the trailers)
     y.total = ws.total();
     return y;
 }
@@ -1022,39 +1095,43 @@ __global__ __launch_bounds__(64) void dz_emit(const zcg_chunk* __restrict__ chun
     flush_to(0, true);
 }
 
-// Per chunk: gzip header, the stream, CRC32/ISIZE (the CRC from gzip_crc32 crc_out mode, run before).
+// Per chunk: the container's header (df_put_header), the stream, its trailer: CRC32/ISIZE or the
+// Adler-32 (the checksum from gzip_crc32's crc_out / zlib_adler32's sum_out mode, run before).
 __global__ __launch_bounds__(256) void dz_final(const zcg_chunk* __restrict__ chunks, u32 c0, u32 nc, u64 D,
-                                               u64 bound, u32 xfl, const DzChunk* __restrict__ cst, const u8* out,
-                                               u64 outcap, u64* __restrict__ out_len, i32* __restrict__ status,
-                                               const u32* __restrict__ crc) {
+                                               u64 bound, u32 xfl, u32 zhdr, const DzChunk* __restrict__ cst,
+                                               const u8* out, u64 outcap, u64* __restrict__ out_len,
+                                               i32* __restrict__ status, const u32* __restrict__ crc) {
     const u32 c = blockIdx.x, tid = threadIdx.x;
     if (c >= nc) return;
     const zcg_chunk ch = chunks[c0 + c];
     const DzChunk cs = cst[c];
+    const u32 H = df_header_bytes(zhdr), T = df_trailer_bytes(zhdr);
     if (ch.src_len < D) { if (tid == 0) { status[c0 + c] = ZCG_ERR_INVALID_DATA; out_len[c0 + c] = 0; } return; }
     if (cs.status != ZCG_OK) { if (tid == 0) { status[c0 + c] = (i32)cs.status; out_len[c0 + c] = 0; } return; }
-    if (ch.dst_cap < bound || ch.dst_cap < DF_HDR + cs.bytes + 8) {
+    if (ch.dst_cap < bound || ch.dst_cap < H + cs.bytes + T) {
         if (tid == 0) { status[c0 + c] = ZCG_ERR_OUTPUT_TOO_SMALL; out_len[c0 + c] = 0; }
         return;
     }
     u8* dst = (u8*)ch.dst;
     const u8* o = out + (u64)c * outcap;
-    if (tid == 0) {
-        const u8 h[10] = {0x1F, 0x8B, 8, 0, 0, 0, 0, 0, (u8)xfl, 255};
-        for (u32 i = 0; i < 10; i++) dst[i] = h[i];
-    }
+    if (tid == 0) df_put_header(dst, xfl, zhdr);
     const u64 n = cs.bytes;
     for (u64 i = (u64)tid * 16; i < n; i += 256 * 16) {
-        if (i + 16 <= n) st16(dst + DF_HDR + i, *(const u32x4*)(o + i));
-        else for (u64 j = i; j < n; j++) dst[DF_HDR + j] = o[j];
+        if (i + 16 <= n) st16(dst + H + i, *(const u32x4*)(o + i));
+        else for (u64 j = i; j < n; j++) dst[H + j] = o[j];
     }
     if (tid == 0) {
         const u32 r = crc[c], isz = (u32)D;
-        u8* tr = dst + DF_HDR + n;
-        const u8 t8[8] = {(u8)r, (u8)(r >> 8), (u8)(r >> 16), (u8)(r >> 24),
-                          (u8)isz, (u8)(isz >> 8), (u8)(isz >> 16), (u8)(isz >> 24)};
-        for (u32 i = 0; i < 8; i++) tr[i] = t8[i];
-        out_len[c0 + c] = DF_HDR + n + 8;
+        u8* tr = dst + H + n;
+        if (zhdr) {
+            const u8 t4[4] = {(u8)(r >> 24), (u8)(r >> 16), (u8)(r >> 8), (u8)r};
+            for (u32 i = 0; i < 4; i++) tr[i] = t4[i];
+        } else {
+            const u8 t8[8] = {(u8)r, (u8)(r >> 8), (u8)(r >> 16), (u8)(r >> 24),
+                              (u8)isz, (u8)(isz >> 8), (u8)(isz >> 16), (u8)(isz >> 24)};
+            for (u32 i = 0; i < 8; i++) tr[i] = t8[i];
+        }
+        out_len[c0 + c] = H + n + T;
         status[c0 + c] = ZCG_OK;
     }
 }
@@ -1067,6 +1144,7 @@ static hipError_t launch_deflate_exact(const zcg_array* a, const zcg_chunk* d_ch
     const DType t = make_dtype(a->dtype);
     const u64 D = a->chunk_num_elements * (u64)t.es;
     const u32 xfl = level >= 9 ? 2u : (level <= 1 ? 4u : 0u);
+    const u32 zhdr = zlib_header_word(a, level);
     const u64 bound = zcg_encode_bound(&a->compression, D);
     if (D >= (1ull << 31)) {  // u32 positions: every chunk UNSUPPORTED, the launch itself succeeds
         if (hipError_t e = hipMemsetD32Async((hipDeviceptr_t)d_status, ZCG_ERR_UNSUPPORTED, n, s); e != hipSuccess)
@@ -1101,7 +1179,7 @@ static hipError_t launch_deflate_exact(const zcg_array* a, const zcg_chunk* d_ch
         hipLaunchKernelGGL(dz_offsets, dim3((cnt + 63) / 64), dim3(64), 0, ts, cnt, cs, bk, y.nbmax, ot, y.outcap);
         hipLaunchKernelGGL(dz_emit, dim3((u32)nbk), dim3(64), 0, ts, d_chunks, s0 + cb, cnt, D, t, (const DzChunk*)cs,
                            (const DzBlock*)bk, y.nbmax, (const u32*)w, ot, y.outcap);
-        hipLaunchKernelGGL(dz_final, dim3(cnt), dim3(256), 0, ts, d_chunks, s0 + cb, cnt, D, bound, xfl,
+        hipLaunchKernelGGL(dz_final, dim3(cnt), dim3(256), 0, ts, d_chunks, s0 + cb, cnt, D, bound, xfl, zhdr,
                            (const DzChunk*)cs, (const u8*)ot, y.outcap, (u64*)d_out_len, (i32*)d_status,
                            (const u32*)crcb + cb);
         return hipGetLastError();
@@ -1111,7 +1189,7 @@ static hipError_t launch_deflate_exact(const zcg_array* a, const zcg_chunk* d_ch
         // a parse that does not run leaves every chunk failed, so the kernels
         // after it never read an unset record
         if (hipError_t e = hipMemsetAsync(cst, 0xFF, sizeof(DzChunk) * (size_t)scnt, s); e != hipSuccess) return e;
-        // the inputs' CRC32s: on the side stream (idle until the first parse)
+        // the inputs' checksums: on the side stream (idle until the first parse)
         // beside the first match search, else in line.  (Sorting sub-batch
         // i + 1 on the side stream beside match search i measured slower,
         // 133.7 vs 126.0 ms per C5 call: the search takes the CUs, the sort
@@ -1122,7 +1200,8 @@ static hipError_t launch_deflate_exact(const zcg_array* a, const zcg_chunk* d_ch
                 if (hipError_t e = sf.fork(); e != hipSuccess) return e;
                 cs = side;
             }
-            if (hipError_t e = launch_gzip_crc32(d_chunks + s0, scnt, D, t, nullptr, nullptr, crcb, cs); e != hipSuccess)
+            if (hipError_t e = launch_stream_checksum(zhdr, d_chunks + s0, scnt, D, t, nullptr, nullptr, crcb, cs);
+                e != hipSuccess)
                 return e;
         }
         for (u32 c0 = s0; c0 < s0 + scnt && D > 0 && !fast; c0 += y.b.m) {

@@ -497,7 +497,7 @@ __global__ __launch_bounds__(64) void deflate_segment(const zcg_chunk* __restric
 }
 
 __global__ __launch_bounds__(256) void deflate_finalize(const zcg_chunk* __restrict__ chunks, u32 n, u64 D,
-                                                        u32 nseg, u64 bound, u32 xfl,
+                                                        u32 nseg, u64 bound, u32 xfl, u32 zhdr,
                                                         u64* __restrict__ out_len, i32* __restrict__ status) {
     const u32 c = blockIdx.x, tid = threadIdx.x;
     if (c >= n) return;
@@ -505,12 +505,9 @@ __global__ __launch_bounds__(256) void deflate_finalize(const zcg_chunk* __restr
     if (ch.src_len < D) { if (tid == 0) { status[c] = ZCG_ERR_INVALID_DATA; out_len[c] = 0; } return; }
     if (ch.dst_cap < bound) { if (tid == 0) { status[c] = ZCG_ERR_OUTPUT_TOO_SMALL; out_len[c] = 0; } return; }
     u8* dst = (u8*)ch.dst;
-    if (tid == 0) {
-        const u8 h[10] = {0x1F, 0x8B, 8, 0, 0, 0, 0, 0, (u8)xfl, 255};
-        for (u32 i = 0; i < 10; i++) dst[i] = h[i];
-    }
+    if (tid == 0) df_put_header(dst, xfl, zhdr);
     __shared__ u32 s_sz;
-    u64 pos = DF_HDR;
+    u64 pos = df_header_bytes(zhdr);  // (<= DF_HDR, where the first slot starts: the copies below move down)
     if (nseg == 0) {  // empty input: one final fixed block holding only end-of-block
         if (tid == 0) { dst[pos] = 0x03; dst[pos + 1] = 0x00; }
         pos += 2;
@@ -539,7 +536,7 @@ __global__ __launch_bounds__(256) void deflate_finalize(const zcg_chunk* __restr
         pos += total;
     }
     if (tid == 0) {
-        out_len[c] = pos + 8;  // + CRC32 + ISIZE (kernel 3)
+        out_len[c] = pos + df_trailer_bytes(zhdr);  // + CRC32 + ISIZE, or the Adler-32 (kernel 3)
         status[c] = ZCG_OK;
     }
 }
@@ -631,6 +628,7 @@ hipError_t launch_deflate_seg(const zcg_array* a, const zcg_chunk* d_chunks, uin
     const u64 D = a->chunk_num_elements * (u64)t.es;
     const u32 xfl = level >= 9 ? 2u : (level <= 1 ? 4u : 0u);
     const u32 nseg = (u32)((D + DF_SEG - 1) / DF_SEG);
+    const u32 zhdr = zlib_header_word(a, level);
     const u64 bound = zcg_encode_bound(&a->compression, D);
     const DfWs y = df_ws(D, n);
     if (nseg && (ws_bytes < y.total || y.b.tot >= (1ull << 31))) return hipErrorInvalidValue;
@@ -662,9 +660,9 @@ hipError_t launch_deflate_seg(const zcg_array* a, const zcg_chunk* d_chunks, uin
                                nseg, bound, t, level, (const u32*)(w + y.off_match));
         }
     }
-    hipLaunchKernelGGL(deflate_finalize, dim3(n), dim3(256), 0, s, d_chunks, n, D, nseg, bound, xfl,
+    hipLaunchKernelGGL(deflate_finalize, dim3(n), dim3(256), 0, s, d_chunks, n, D, nseg, bound, xfl, zhdr,
                        (u64*)d_out_len, d_status);
-    return launch_gzip_crc32(d_chunks, n, D, t, (const u64*)d_out_len, (const i32*)d_status, nullptr, s);
+    return launch_stream_checksum(zhdr, d_chunks, n, D, t, (const u64*)d_out_len, (const i32*)d_status, nullptr, s);
 }
 
 }  // namespace zcg

@@ -44,7 +44,8 @@ __global__ __launch_bounds__(64) void inflate_kernel(const zcg_chunk* __restrict
     const u8* s = (const u8*)ch.src;
     const u64 n_in = ch.src_len;
     u64 h = 0;
-    st = gzip_header(s, n_in, &h);
+    const bool zlib = (vflags & INF_FRAME_ZLIB) != 0;
+    st = inf_header(s, n_in, zlib, &h);
     if (st != ZCG_OK) { if (lane == 0) status[c] = st; return; }
     const InfMember m{s + h, n_in - h, h, n_in, (u8*)ch.dst, t};
 
@@ -127,7 +128,7 @@ __global__ __launch_bounds__(64) void inflate_kernel(const zcg_chunk* __restrict
             inf_maybe_flush(o);
         }
     }
-    st = inf_close(b, m, r, o.P, D, boundary, last, after_stored, lens, &lh, ltab, &dh, dtab, vflags, vrec + c);
+    st = inf_close(b, m, r, o.P, D, boundary, last, after_stored, lens, &lh, ltab, &dh, dtab, vflags, vrec + c, zlib);
     if (st == ZCG_OK) {
         while (D - o.F > INF_FLUSH) inf_flush(o, o.F + INF_FLUSH);
         inf_flush(o, D);
@@ -158,22 +159,26 @@ static bool inflate_par_pick(const zcg_array* a, uint32_t n) {
     return n <= 3 * device_cu_count();
 }
 
-// Under ZCG_FLAG_VERIFY_GZIP_TRAILER each kernel's workspace also holds the
-// verify area (per-chunk records, CRC partials): the whole workspace of the
+// Under a trailer verify flag each kernel's workspace also holds the
+// verify area (per-chunk records, CRC or Adler partials): the whole workspace of the
 // serial kernel, after the slot-owner words of the other two.
-uint64_t gzip_decode_ws_bytes(const zcg_array* a, uint32_t n) {
+uint64_t gzip_decode_ws_bytes(const zcg_array* a0, uint32_t n) {
+    const zcg_array fa = inflate_frame_array(a0);
+    const zcg_array* const a = &fa;
     if (a->compression.flags & ZCG_FLAG_SERIAL_INFLATE) return gzip_verify(a) && n ? verify_ws_bytes(n) : 0;
     return inflate_par_pick(a, n) ? inflate_par_ws_bytes(a, n) : inflate_wave_ws_bytes(a, n);
 }
 
-hipError_t launch_gzip_decode(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n, int32_t* d_status, void* ws,
+hipError_t launch_gzip_decode(const zcg_array* a0, const zcg_chunk* d_chunks, uint32_t n, int32_t* d_status, void* ws,
                               uint64_t ws_bytes, hipStream_t s) {
     if (n == 0) return hipSuccess;
+    const zcg_array fa = inflate_frame_array(a0);  // (the frame kind and its verify flag, zcg_common.h)
+    const zcg_array* const a = &fa;
     const bool verify = gzip_verify(a);
     const bool serial = (a->compression.flags & ZCG_FLAG_SERIAL_INFLATE) != 0, par = !serial && inflate_par_pick(a, n);
     void* const varea = serial ? ws : par ? inflate_par_verify_area(ws) : inflate_wave_verify_area(ws);
     if (verify) {
-        if (!ws || ws_bytes < gzip_decode_ws_bytes(a, n)) return hipErrorInvalidValue;
+        if (!ws || ws_bytes < gzip_decode_ws_bytes(a0, n)) return hipErrorInvalidValue;
         if (hipError_t e = verify_reset(varea, n, s); e != hipSuccess) return e;
     }
     hipError_t e;
@@ -181,6 +186,7 @@ hipError_t launch_gzip_decode(const zcg_array* a, const zcg_chunk* d_chunks, uin
     else if (par) e = launch_inflate_par(a, d_chunks, n, d_status, ws, ws_bytes, s);
     else e = launch_inflate_wave(a, d_chunks, n, d_status, ws, ws_bytes, s);
     if (e != hipSuccess || !verify) return e;
+    if (fa.compression.flags & INF_FRAME_ZLIB) return launch_adler32_verify(a, d_chunks, n, d_status, varea, s);
     return launch_crc32_verify(a, d_chunks, n, d_status, varea, s);
 }
 

@@ -2,8 +2,10 @@
 // (zcg_inflate.hip), 256-lane (zcg_inflate_par.hip) and wave
 // (zcg_inflate_wave.hip) inflate kernels: Huffman tables in LDS, the
 // wave-uniform bit reader, and the gzip MEMBER FRAME that all three run their
-// own block loops inside:
-//   inf_open           guards, flate2's gzip header rules -> InfMember
+// own block loops inside (and its zlib counterpart, RFC 1950: another header
+// and trailer around the same deflate body, picked by inf_open's and
+// inf_close's `zlib` argument):
+//   inf_open           guards, flate2's gzip (zlib's) header rules -> InfMember
 //   read_block_header  BFINAL/BTYPE, stored lengths, fixed tables; the dynamic
 //                      header reader is the kernel's own (a parameter)
 //   inf_stored_copy    a stored block through a kernel's stage (256-lane, wave)
@@ -582,6 +584,29 @@ __device__ inline int gzip_header(const u8* s, u64 n_in, u64* hlen) {
     return ZCG_OK;
 }
 
+// zlib's inflate() HEAD state (RFC 1950; flate2's ZlibDecoder runs the same
+// code): two bytes, a multiple of 31, CM 8, a window of at most 15 bits; a
+// preset dictionary is not supported.  The declared window is not enforced.
+__device__ inline int zlib_header(const u8* s, u64 n_in, u64* hlen) {
+    if (n_in < 2) return ZCG_ERR_UNEXPECTED_EOF;
+    const u32 b0 = s[0], b1 = s[1];
+    if (((b0 << 8) | b1) % 31 != 0) return ZCG_ERR_INVALID_DATA;  // "incorrect header check"
+    if ((b0 & 15) != 8) return ZCG_ERR_INVALID_DATA;              // "unknown compression method"
+    if ((b0 >> 4) > 7) return ZCG_ERR_INVALID_DATA;               // "invalid window size"
+    if (b1 & 0x20) return ZCG_ERR_UNSUPPORTED;                    // FDICT
+    *hlen = 2;
+    return ZCG_OK;
+}
+
+// The header of the frame kind.  `zlib` is a compile-time constant in the wave
+// and 256-lane kernels (one instantiation per kind, picked by the launcher from
+// INF_FRAME_ZLIB in the flag word, zcg_common.h: the gzip kernels' code is then
+// what it was before the second kind existed) and that flag bit in the serial
+// kernel.  The kind is read here and in inf_close, nowhere else.
+__device__ __forceinline__ int inf_header(const u8* s, u64 n_in, bool zlib, u64* hlen) {
+    return zlib ? zlib_header(s, n_in, hlen) : gzip_header(s, n_in, hlen);
+}
+
 // ---- the member frame ----------------------------------------------------------------------
 // An open member: the deflate stream ds[0, n_ds) after h header bytes of the
 // n_in member bytes, and the output with the transform a kernel commits with
@@ -596,12 +621,12 @@ struct InfMember {
 // The guards every kernel starts with and flate2's header.  false: *st is the
 // chunk's final status (ZCG_OK for an empty chunk).  A kernel's own size
 // limits come after this.
-__device__ __forceinline__ bool inf_open(const zcg_chunk& ch, u64 D, DType t, InfMember& m, int* st) {
+__device__ __forceinline__ bool inf_open(const zcg_chunk& ch, u64 D, DType t, bool zlib, InfMember& m, int* st) {
     if (D == 0) { *st = ZCG_OK; return false; }
     if (ch.dst_cap < D) { *st = ZCG_ERR_INVALID_INPUT; return false; }
     const u8* s = (const u8*)ch.src;
     u64 h = 0;
-    *st = gzip_header(s, ch.src_len, &h);
+    *st = inf_header(s, ch.src_len, zlib, &h);
     if (*st != ZCG_OK) return false;
     m.ds = s + h;
     m.n_ds = ch.src_len - h;
@@ -617,13 +642,15 @@ __device__ __forceinline__ bool inf_open(const zcg_chunk& ch, u64 D, DType t, In
 // produced, boundary = the output filled exactly at a token boundary (then
 // zlib looks ahead, inf_lookahead, inside inf_lookahead_limit), last /
 // after_stored = the block the loop stopped in.  Returns the chunk's status.
-// Under ZCG_FLAG_VERIFY_GZIP_TRAILER (rules in zchunk_gpu.h) the look-ahead
-// walks to the member's end with the whole input as its limit, the trailer is
-// read where the stream ended, and `rec` receives the expected CRC32.
+// Under the frame's trailer verify flag (rules in zchunk_gpu.h; one bit in
+// vflags for both kinds, zcg_common.h; `zlib` picks the trailer's layout) the look-ahead walks to the member's end
+// with the whole input as its limit, the trailer is read where the stream
+// ended, and `rec` receives the expected CRC32 (zlib frame: Adler-32).
 template <int LB = INF_LBITS, u32 LCAP = INF_LTAB, int DB = INF_DBITS, u32 DCAP = INF_DTAB>
 __device__ __attribute__((always_inline)) int inf_close(BitIn& b, const InfMember& m, int r, u64 P, u64 D, bool boundary,
                                                         bool last, bool after_stored, u8* lens, HuffLds* lh, u32* ltab,
-                                                        HuffLds* dh, u32* dtab, u32 vflags, VerifyRec* rec) {
+                                                        HuffLds* dh, u32* dtab, u32 vflags, VerifyRec* rec,
+                                                        bool zlib = false) {
     const bool verify = (vflags & ZCG_FLAG_VERIFY_GZIP_TRAILER) != 0;
     int la = R_EXHAUSTED;  // (what a look-ahead that cannot start amounts to)
     bool at_end = false;
@@ -642,8 +669,13 @@ __device__ __attribute__((always_inline)) int inf_close(BitIn& b, const InfMembe
     if (la == R_EXHAUSTED) return ZCG_ERR_UNEXPECTED_EOF;
     if (!at_end) return ZCG_ERR_INVALID_DATA;         // the next step would emit a byte
     const u64 tr = m.h + (b.consumed + 7) / 8;
-    if (tr + 8 > m.n_in) return ZCG_ERR_UNEXPECTED_EOF;
     const u8* const tp = m.ds - m.h + tr;
+    if (zlib) {  // Adler-32, big-endian; no length word
+        if (tr + 4 > m.n_in) return ZCG_ERR_UNEXPECTED_EOF;
+        if (threadIdx.x == 0) *rec = VerifyRec{V_CHECK, __builtin_bswap32(ld32(tp))};
+        return ZCG_OK;
+    }
+    if (tr + 8 > m.n_in) return ZCG_ERR_UNEXPECTED_EOF;
     if (ld32(tp + 4) != (u32)D) return ZCG_ERR_INVALID_DATA;
     if (threadIdx.x == 0) *rec = VerifyRec{V_CHECK, ld32(tp)};
     return ZCG_OK;

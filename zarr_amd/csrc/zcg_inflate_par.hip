@@ -448,6 +448,7 @@ __device__ __attribute__((always_inline)) int read_dynamic_par(ParLds& L, BitIn&
     return R_OK;
 }
 
+template <bool ZLIB>  // the member frame's kind (inf_open, inf_close)
 __global__ __launch_bounds__(PI_NL, ZCG_INF_WPE) void inflate_par_kernel(const zcg_chunk* __restrict__ chunks,
                                                                u32 n, u64 D, DType t, u32 vflags,
                                                                i32* __restrict__ status,
@@ -461,7 +462,7 @@ __global__ __launch_bounds__(PI_NL, ZCG_INF_WPE) void inflate_par_kernel(const z
     const zcg_chunk ch = chunks[c];
     InfMember m;
     int st;
-    bool open = inf_open(ch, D, t, m, &st);
+    bool open = inf_open(ch, D, t, ZLIB, m, &st);
     if (open && m.n_ds >= (1ull << 28)) { st = ZCG_ERR_UNSUPPORTED; open = false; }  // u32 bit positions
     if (!open) { if (tid == 0) status[c] = st; return; }
 
@@ -937,7 +938,7 @@ __global__ __launch_bounds__(PI_NL, ZCG_INF_WPE) void inflate_par_kernel(const z
     // zlib's post-N look-ahead (all waves, identical)
     // (under the verify flag the records sit between the owner words and the pools)
     st = inf_close(b, m, r, P, D, boundary, last, after_stored, L.lens, &L.lh, L.ltab, &L.dh, L.dtab, vflags,
-                   (VerifyRec*)((u8*)owner + PI_OWNER_BYTES) + c);
+                   (VerifyRec*)((u8*)owner + PI_OWNER_BYTES) + c, ZLIB);
     if (t.isbool) {  // byte != 0 over the whole decoded chunk, after the last round
         __syncthreads();
         wave_transform<PI_NL>(dst, P < D ? P : D, DType{1, 0, 1}, tid);
@@ -982,12 +983,14 @@ hipError_t launch_inflate_par(const zcg_array* a, const zcg_chunk* d_chunks, uin
     const DType t = gzip_decode_dtype(a);
     const u64 D = a->chunk_num_elements * (u64)t.es;
     const size_t lds = sizeof(ParLds);
-    if (hipError_t e = lds_attr_once((const void*)inflate_par_kernel, (int)lds); e != hipSuccess) return e;
+    const bool zlib = (a->compression.flags & INF_FRAME_ZLIB) != 0;
+    const auto kernel = zlib ? inflate_par_kernel<true> : inflate_par_kernel<false>;
+    if (hipError_t e = lds_attr_once((const void*)kernel, (int)lds); e != hipSuccess) return e;
     u32* owner = (u32*)ws;  // the workspace is shared by the stream's codecs: clear the owners
     hipError_t e = hipMemsetAsync(owner, 0, PI_OWNER_BYTES, s);
     if (e != hipSuccess) return e;
     gu32* pools = (gu32*)((u8*)ws + PI_OWNER_BYTES + (gzip_verify(a) ? verify_ws_bytes(n) : 0));
-    hipLaunchKernelGGL(inflate_par_kernel, dim3(n), dim3(PI_NL), lds, s, d_chunks, n, D, t,
+    hipLaunchKernelGGL(kernel, dim3(n), dim3(PI_NL), lds, s, d_chunks, n, D, t,
                        a->compression.flags, d_status, owner, pools);
     return hipGetLastError();
 }

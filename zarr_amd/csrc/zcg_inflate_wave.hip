@@ -844,6 +844,7 @@ __device__ __attribute__((always_inline)) IwRound iw_h_round(IwLds& L, u32 R0, u
     return IwRound{p, ncm, chL, chS, chE, endq};
 }
 
+template <bool ZLIB>  // the member frame's kind (inf_open, inf_close)
 __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chunk* __restrict__ chunks, u32 n,
                                                                   u64 D, DType t, u32 vflags,
                                                                   i32* __restrict__ status,
@@ -858,7 +859,7 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
     const zcg_chunk ch = chunks[c];
     InfMember m;
     int st;
-    bool open = inf_open(ch, D, t, m, &st);
+    bool open = inf_open(ch, D, t, ZLIB, m, &st);
     if (open && (m.n_ds >= (1ull << 28) || D >= (1ull << 32))) { st = ZCG_ERR_UNSUPPORTED; open = false; }  // u32 positions
     if (!open) { if (lane == 0) status[c] = st; return; }
 
@@ -1404,7 +1405,7 @@ __global__ __launch_bounds__(64, ZIW_WPE) void inflate_wave_kernel(const zcg_chu
     }
     // (under the verify flag the records sit between the owner words and the pools)
     st = inf_close<W_LB, W_LCAP, W_DB, W_DCAP>(b, m, r, P, D, boundary, last, after_stored, L.u.h.lens, &L.u.h.lh, L.ltab,
-                                               &L.u.h.dh, L.dtab, vflags, (VerifyRec*)((u8*)owner + IW_OWNER_BYTES) + c);
+                                               &L.u.h.dh, L.dtab, vflags, (VerifyRec*)((u8*)owner + IW_OWNER_BYTES) + c, ZLIB);
     if (t.isbool) {  // byte != 0 over the whole decoded chunk (the committed bytes were the window)
         __syncthreads();
         wave_transform<64>(dst, P < D ? P : D, DType{1, 0, 1}, lane);
@@ -1468,13 +1469,15 @@ hipError_t launch_inflate_wave(const zcg_array* a, const zcg_chunk* d_chunks, ui
     const DType t = gzip_decode_dtype(a);
     const u64 D = a->chunk_num_elements * (u64)t.es;
     const size_t lds = sizeof(IwLds);
-    if (hipError_t e = lds_attr_once((const void*)inflate_wave_kernel, (int)lds); e != hipSuccess) return e;
+    const bool zlib = (a->compression.flags & INF_FRAME_ZLIB) != 0;
+    const auto kernel = zlib ? inflate_wave_kernel<true> : inflate_wave_kernel<false>;
+    if (hipError_t e = lds_attr_once((const void*)kernel, (int)lds); e != hipSuccess) return e;
     const u32 nslot = iw_nslot(n);
     u32* owner = (u32*)ws;
     hipError_t e = hipMemsetAsync(owner, 0, (size_t)nslot * 4, s);
     if (e != hipSuccess) return e;
     gu32* pools = (gu32*)((u8*)ws + IW_OWNER_BYTES + (gzip_verify(a) ? verify_ws_bytes(n) : 0));
-    hipLaunchKernelGGL(inflate_wave_kernel, dim3(n), dim3(64), lds, s, d_chunks, n, D, t,
+    hipLaunchKernelGGL(kernel, dim3(n), dim3(64), lds, s, d_chunks, n, D, t,
                        a->compression.flags, d_status, owner, nslot, pools);
     return hipGetLastError();
 }

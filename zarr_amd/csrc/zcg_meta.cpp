@@ -443,6 +443,9 @@ int parse_meta(const char* json, uint64_t len, zcg_array_meta* out, std::string&
         } else if (id == "https://purl.org/zarr/spec/codec/gzip/1.0") {
             c.codec = ZCG_CODEC_GZIP;
             c.gzip_level = (int32_t)cfg_int(conf, "level", -1, bad);
+        } else if (id == "zlib") {
+            c.codec = ZCG_CODEC_ZLIB;
+            c.gzip_level = (int32_t)cfg_int(conf, "level", -1, bad);
         } else if (id == "lz4") {
             c.codec = ZCG_CODEC_LZ4;
             c.lz4_block_size = (int32_t)cfg_int(conf, "blockSize", 65536, bad);

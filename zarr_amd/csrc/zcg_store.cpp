@@ -191,14 +191,14 @@ size_t store_batch_bytes(const zcg_array* a) {
     const int32_t c = a->compression.codec;
     return (c == ZCG_CODEC_XZ || c == ZCG_CODEC_BZIP2) ? 4 * STORE_BATCH_BYTES : STORE_BATCH_BYTES;
 }
-// Chunks per read sub-batch.  Gzip, xz and bzip2 decode one chunk per wave
+// Chunks per read sub-batch.  Gzip (zlib), xz and bzip2 decode one chunk per wave
 // (or workgroup), and a wave's time does not depend on how many run beside
 // it up to 16 per CU: a sub-batch needs >= 2 048 chunks (4 096 in flight over
 // the two pipeline slots) to run at the device rate, whatever D is.
 uint64_t store_read_batch_chunks(const zcg_array* a, uint64_t D) {
     const int32_t c = a->compression.codec;
     uint64_t per = D ? store_batch_bytes(a) / D : ~0ull;
-    if (c == ZCG_CODEC_GZIP || c == ZCG_CODEC_XZ || c == ZCG_CODEC_BZIP2) {
+    if (c == ZCG_CODEC_GZIP || c == ZCG_CODEC_ZLIB || c == ZCG_CODEC_XZ || c == ZCG_CODEC_BZIP2) {
         const uint64_t cap = D ? (4ull << 30) / D : ~0ull;  // <= 4 GiB of decoded bytes per slot
         per = std::max<uint64_t>(per, std::min<uint64_t>(2048, cap));
     }

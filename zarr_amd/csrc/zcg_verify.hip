@@ -1,5 +1,6 @@
 // zcg_verify.hip — opt-in checksum verification of decoded chunks
-// (ZCG_FLAG_VERIFY_GZIP_TRAILER, ZCG_FLAG_VERIFY_LZ4_CONTENT; rules in
+// (ZCG_FLAG_VERIFY_GZIP_TRAILER, ZCG_FLAG_VERIFY_ZLIB_TRAILER,
+// ZCG_FLAG_VERIFY_LZ4_CONTENT; rules in
 // include/zchunk_gpu.h).  The decoders locate the trailer and leave one
 // VerifyRec per chunk; the kernels here read each decoded byte once, in stream
 // order, checksum it, apply the part of the element transform the decoder was
@@ -27,6 +28,12 @@
 // layout; replicating the tables spreads the lanes over the same number of
 // banks and padding only renames them, so neither is done.
 //
+// adler32_verify (zlib).  The same slices, tiles and loads; Adler-32's two sums
+// do not depend on how the bytes are cut up, so a lane keeps three unreduced
+// sums over its comb (zcg_adler.h: the arithmetic and its deferred-modulo
+// bound), takes them mod 65521 once per slice, and lanes, waves and slices fold
+// by modular addition: no tables, no LDS.
+//
 // xxh32_verify (LZ4).  XXH32's four accumulators are serial over the whole
 // content, so the parallelism is across chunks: 16 chunks per wave, 4 lanes
 // (accumulators) each.  Each step the whole wave loads the next 1 KiB of every
@@ -36,6 +43,7 @@
 // accumulator) walks its chunk's row one 16-byte stripe at a time.
 #include "zcg_common.h"
 #include "zcg_crc.h"
+#include "zcg_adler.h"
 
 namespace zcg {
 
@@ -187,6 +195,67 @@ __global__ __launch_bounds__(64) void crc32_fold_kernel(u32 n, CrcArgs a, const 
     }
 }
 
+// ---- Adler-32 (zlib) ---------------------------------------------------------------------------
+// crc32_verify's slices, tiles and loads; the sums are zcg_adler.h's.  A slice
+// that is no whole number of tiles is padded with virtual zero pieces at its
+// END (they add nothing to a sum, and the front pieces then sit 16-aligned in
+// the chunk).  A wave's partial is the sum of its lanes' partials, a chunk's
+// the sum of its slices': adler32_fold adds them, compares and writes the status.
+static_assert(0x100000000ull / CV_MAX_PARTS / CV_TILE + 1 <= ADLER_LANE_MAX_PIECES,
+              "a lane's pieces of the longest slice (D < 2^32) stay inside the deferred-modulo bound");
+
+__global__ __launch_bounds__(CV_NT) void adler32_verify_kernel(const zcg_chunk* __restrict__ chunks, u32 n, u64 D,
+                                                               DType t, u32 slice, u32 nparts,
+                                                               const VerifyRec* __restrict__ rec,
+                                                               u32* __restrict__ partials) {
+    const u32 tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const u32 gpc = (nparts + 3) / 4;  // workgroup items per chunk
+    const u64 items = (u64)n * gpc;
+    for (u64 item = blockIdx.x; item < items; item += gridDim.x) {
+        const u32 c = (u32)(item / gpc);
+        const u32 part = (u32)(item % gpc) * 4 + wv;
+        if (part >= nparts || rec[c].mode != V_CHECK) continue;  // (wave-uniform; no barrier below)
+        u8* const dst = (u8*)chunks[c].dst;
+        const u64 off = (u64)part * slice;
+        const u64 end = D - off < slice ? D : off + slice;  // (of the slice, in the chunk)
+        const u32 ntile = (u32)((end - off + CV_TILE - 1) / CV_TILE);
+        const u64 base = off + lane * 16;  // my piece of tile k at base + k * CV_TILE
+        auto piece = [&](u64 p) -> u32x4 {
+            if (p + 16 <= end) return cv_load16(dst, p, t);
+            u32 w[4] = {0u, 0u, 0u, 0u};
+            for (u64 q = p; q < end; q++) {  // the piece the chunk ends in (only the last slice is short)
+                const u64 ph = swap_pos(q, t);
+                const u32 b = dst[ph];
+                w[(q - p) >> 2] |= b << (8 * ((q - p) & 3));
+                if (t.isbool && b > 1) dst[ph] = 1;
+            }
+            return u32x4{w[0], w[1], w[2], w[3]};
+        };
+        AdlerLane al = adler_lane_open();
+        u32x4 cur = piece(base);
+        for (u32 k = 0; k < ntile; k++) {
+            u32x4 nxt = {0u, 0u, 0u, 0u};
+            if (k + 1 < ntile) nxt = piece(base + (u64)(k + 1) * CV_TILE);
+            adler_lane_piece(al, cur.x, cur.y, cur.z, cur.w);
+            cur = nxt;
+        }
+        const i64 E = (i64)D - (i64)(base + (u64)(ntile - 1) * CV_TILE) - 16;
+        const u32 v = adler_wave_sum(adler_lane_close(al, E, CV_TILE));
+        if (lane == 0) partials[(u64)c * CV_MAX_PARTS + part] = v;
+    }
+}
+
+__global__ __launch_bounds__(64) void adler32_fold_kernel(u32 n, u64 D, u32 nparts, const VerifyRec* __restrict__ rec,
+                                                          const u32* __restrict__ partials,
+                                                          i32* __restrict__ status) {
+    const u32 c = blockIdx.x, lane = threadIdx.x;
+    if (c >= n) return;
+    const VerifyRec rc = rec[c];
+    if (rc.mode != V_CHECK) return;
+    const u32 v = adler_wave_sum(lane < nparts ? partials[(u64)c * CV_MAX_PARTS + lane] : 0u);
+    if (lane == 0 && adler_finish(v, D) != rc.expect) status[c] = ZCG_ERR_INVALID_DATA;
+}
+
 // ---- XXH32 -------------------------------------------------------------------------------------
 constexpr u32 XV_CPW = 16;              // chunks per wave
 constexpr u32 XV_PIECE = 1024;          // bytes of a chunk per step
@@ -281,18 +350,25 @@ hipError_t verify_reset(void* varea, uint32_t n, hipStream_t s) {
     return hipMemsetAsync(varea, 0, (size_t)n * sizeof(VerifyRec), s);
 }
 
+// The slices of a chunk of D bytes, as both checksum passes cut them.
+static bool verify_slices(u64 D, u32* slice_out, u32* nparts) {
+    u64 slice = (D + CV_MAX_PARTS - 1) / CV_MAX_PARTS;
+    slice = (slice + CV_TILE - 1) / CV_TILE * CV_TILE;
+    if (slice < CV_MIN_SLICE) slice = CV_MIN_SLICE;
+    if (slice > 0xFFFFFC00ull) return false;  // (D >= 2^32 is ZCG_ERR_UNSUPPORTED in the decoders)
+    *slice_out = (u32)slice;
+    *nparts = (u32)((D + slice - 1) / slice);
+    return true;
+}
+
 hipError_t launch_crc32_verify(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n, int32_t* d_status,
                                void* varea, hipStream_t s) {
     DType t = make_dtype(a->dtype);
     const u64 D = a->chunk_num_elements * (u64)t.es;
     if (n == 0 || D == 0) return hipSuccess;
     CrcArgs ca;
-    u64 slice = (D + CV_MAX_PARTS - 1) / CV_MAX_PARTS;
-    slice = (slice + CV_TILE - 1) / CV_TILE * CV_TILE;
-    if (slice < CV_MIN_SLICE) slice = CV_MIN_SLICE;
-    if (slice > 0xFFFFFC00ull) return hipErrorInvalidValue;  // (D >= 2^32 is ZCG_ERR_UNSUPPORTED in the decoders)
-    ca.slice = (u32)slice;
-    ca.nparts = (u32)((D + slice - 1) / slice);
+    if (!verify_slices(D, &ca.slice, &ca.nparts)) return hipErrorInvalidValue;
+    const u64 slice = ca.slice;
     ca.xz = h_xpow8n(CV_TILE - 16);
     for (int k = 0; k < 6; k++) {
         ca.lm[k] = h_xpow8n(16ull << k);
@@ -307,6 +383,25 @@ hipError_t launch_crc32_verify(const zcg_array* a, const zcg_chunk* d_chunks, ui
     hipLaunchKernelGGL(crc32_verify_kernel, dim3((u32)(items < cap ? items : cap)), dim3(CV_NT), 0, s, d_chunks, n, D,
                        t, ca, rec, partials);
     hipLaunchKernelGGL(crc32_fold_kernel, dim3(n), dim3(64), 0, s, n, ca, rec, (const u32*)partials, d_status);
+    return hipGetLastError();
+}
+
+// Two launches, like the CRC pass: the slices' partials, then one wave per
+// chunk that adds them (no atomics, no zeroed accumulators).
+hipError_t launch_adler32_verify(const zcg_array* a, const zcg_chunk* d_chunks, uint32_t n, int32_t* d_status,
+                                 void* varea, hipStream_t s) {
+    const DType t = make_dtype(a->dtype);
+    const u64 D = a->chunk_num_elements * (u64)t.es;
+    if (n == 0 || D == 0) return hipSuccess;
+    u32 slice = 0, nparts = 0;
+    if (D >> 32 || !verify_slices(D, &slice, &nparts)) return hipErrorInvalidValue;
+    const VerifyRec* rec = (const VerifyRec*)varea;
+    u32* partials = (u32*)(verify_base((u8*)varea + verify_rec_bytes(n)));
+    const u64 items = (u64)n * ((nparts + 3) / 4);
+    const u64 cap = (u64)device_cu_count() * 8;  // (no LDS; 8 workgroups of 4 waves fill a CU)
+    hipLaunchKernelGGL(adler32_verify_kernel, dim3((u32)(items < cap ? items : cap)), dim3(CV_NT), 0, s, d_chunks, n, D,
+                       t, slice, nparts, rec, partials);
+    hipLaunchKernelGGL(adler32_fold_kernel, dim3(n), dim3(64), 0, s, n, D, nparts, rec, (const u32*)partials, d_status);
     return hipGetLastError();
 }
 
